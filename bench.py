@@ -4,6 +4,7 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 outside torchrun: the bench starts its N ranks itself, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --train                             (BASELINE config 3: data-parallel training step, gradient all-reduce over RCCL)
+    python bench.py ... --dump-outputs DIR                       (also write what the last timed step returned to DIR/*.npy: same arguments, same inputs)
 
 A step = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
   32 x 10 s of 16 kHz audio -> log-mel + utterance CMVN (HIP) -> pad to 1000 frames -> Conv2d sub-sampling ->
@@ -231,10 +232,45 @@ def parse_args(argv=None):
     ap.add_argument("--no-train-dp", action="store_true", help="more than one rank: skip the config-3 training step under both gradient all-reduce schedules")
     ap.add_argument("--train-dp-batch", type=int, default=96, help="per-GPU batch of the `train_dp` record (config 3: 96)")
     ap.add_argument("--train-dp-steps", type=int, default=5, help="timed steps per schedule of the `train_dp` record")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="forward bench: after the timed steps write what the last timed step returned (CTC loss, encoder "
+                                                                        "lengths, a fixed seeded sample of the logit rows) to DIR/<name>.npy, for output-for-output comparison of two builds")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.train or args.secondary or args.dry_run):
+        ap.error("--dump-outputs covers the forward headline only (not --train, --secondary or --dry-run)")
     if args.wide_tiles is None:
         args.wide_tiles = int(args.streams >= 3)         # wide tiles leave one step alone with a quarter of the blocks per launch: they come with the lanes that fill the rest
     return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_LOGIT_BYTES = 48 << 20        # the sampled logit rows; the rest of the dump is a few KB
+
+
+def dump_outputs(dirname, last):
+    """--dump-outputs: the arrays the last timed step handed its caller, as float32 / float64 .npy files.  The fp32 logits (B, T2, V+1) are ~160 MB at the
+    headline shape, so `logits_rows` holds a fixed seeded sample of the rows inside every clip's encoder length (padding rows carry no defined value), and
+    `logits_row_index` their flat index b * T2 + t."""
+    out = last["out"]
+    logits = out["logits"]
+    B, T2, V1 = logits.shape
+    outer = out["outer_len"].cpu().numpy()
+    valid = np.concatenate([b * T2 + np.arange(int(outer[b])) for b in range(B)])
+    n = min(len(valid), DUMP_LOGIT_BYTES // (V1 * 4))
+    rows = np.sort(np.random.RandomState(0).choice(valid, n, replace=False))
+    arrays = {"ctc_loss": last["loss"].detach().float().cpu().numpy().reshape(1),
+              "outer_len": outer.astype(np.float64),
+              "logits_rows": logits.reshape(B * T2, V1)[torch.from_numpy(rows).to(logits.device)].float().cpu().numpy(),
+              "logits_row_index": rows.astype(np.float64)}
+    if out.get("lse") is not None:                 # --head-lse: the rows' log-sum-exp out of the head GEMM's epilogue, also handed to the CTC loss
+        arrays["logits_lse"] = out["lse"].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, total
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} outputs of the last timed step ({total / 2**20:.1f} MB) -> {dirname}", file=sys.stderr, flush=True)
 
 
 def launch_ranks(args) -> int:
@@ -608,17 +644,19 @@ def main():
     tables = FB.FbankTables(80)
     tables.device(dev)
 
-    def step(e=eng, w=wave, lab=labels):
+    def step(e=eng, w=wave, lab=labels, keep=None):
         feats, frames = FB.fbank_gpu(w, tables, pad_frames_to=100)
         out = e.forward(feats, frames, want_hidden=False)
         loss, _, _ = ops.ctc_loss(out["logits"], lab, out["outer_len"], reduction="mean", zero_infinity=True, lse=out["lse"])     # lse: None (a pass over the logits inside ctc_loss) unless --head-lse
+        if keep is not None:
+            keep.update(out=out, loss=loss)
         return loss
 
     batches = [(wave, labels)] + [(torch.from_numpy(synth.waveforms(100 + rank + 1000 * i, B, SR * SECONDS)).to(dev),
                                    torch.from_numpy(synth.labels(rank + 1000 * i, B, U, cfg["vocab_size"])).to(dev)) for i in range(1, nstr)]
 
-    def step_pipelined():
-        return pipe.submit(lambda e, lane: step(e, *batches[lane]))
+    def step_pipelined(keep=None):
+        return pipe.submit(lambda e, lane: step(e, *batches[lane], keep=keep))
 
     L = _lib.lib()
     use_events = not args.no_kernel_events and rank == 0
@@ -628,13 +666,16 @@ def main():
     torch.cuda.synchronize()
     pipe.reset()
     state = {}
+    last = {} if args.dump_outputs and rank == 0 else None      # the outputs of the latest timed step (held only when they are dumped)
 
     def one():
-        lane, v = step_pipelined()
+        lane, v = step_pipelined(last)
         if lane == 0:
             state["loss"] = v                # lane 0 is the batch every earlier round's line reports the loss of
     dt = PL.timed(one, args.steps, sync=torch.cuda.synchronize, device=dev)      # barrier + sync both sides, MAX over ranks
     loss_v = float(state["loss"])
+    if last is not None:
+        dump_outputs(args.dump_outputs, last)
     single = None
     if nstr > 1 and not args.no_one_step:    # the same K steps strictly one at a time (outside the timed region): what the pipelining buys
         for _ in range(2):
