@@ -27,6 +27,8 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
+from functools import partial
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -46,12 +48,28 @@ class Spec:
     decay: bool
 
 
+class Ref(NamedTuple):
+    """how one packed parameter relates to the reference's state dict: pack(sd) -> the packed tensor, pieces = [(reference key,
+    unpack(packed) -> the reference tensor, a view where the layouts allow), ...]; optional: the keys may be missing from a reference
+    state dict (pack then supplies the default) and are not exported when the last load lacked them"""
+    pack: Callable
+    pieces: list
+    optional: bool = False
+
+
+def _one(m, name, key, fwd=lambda t: t, bwd=lambda t: t):
+    """map entry of a packed parameter that is ONE reference tensor: packed = fwd(sd[key]), reference = bwd(packed)"""
+    m[name] = Ref(lambda sd: fwd(sd[key]), [(key, bwd)])
+
+
 def _al(n, a=64):
     return (n + a - 1) // a * a
 
 
 class ParamStore:
-    def __init__(self, specs: list[Spec], device):
+    """ref_map: packed name -> Ref for every parameter; import / export in the reference's names go through it."""
+
+    def __init__(self, specs: list[Spec], device, ref_map: dict | None = None):
         self.specs = {s.name: s for s in specs}
         self.order = [s.name for s in specs]
         self.device = torch.device(device)
@@ -73,6 +91,9 @@ class ParamStore:
         self.frozen_spans = []
         self.set_frozen(())
         self.step_count = 0
+        self.map = {n: Ref(*r) for n, r in (ref_map or {}).items()}
+        self._piece = {key: (name, unpack) for name, r in self.map.items() for key, unpack in r.pieces}
+        self.absent = set()             # optional reference keys the last load lacked
 
     def set_frozen(self, names):
         """Parameters that must not change: no weight decay on them (the mask AdamW reads), and their gradient spans — merged into as few
@@ -145,6 +166,53 @@ class ParamStore:
         self.flat_g.zero_()
         self.fresh = True               # every gradient is exactly zero: the next backward's grouped weight-gradient launches may WRITE their targets (EncoderCTCTrainer.dw_overwrite)
 
+    # ------------------------------------------------------------------ reference names
+    def _flat(self, which):
+        return {"p": self.flat_p, "g": self.flat_g}[which]
+
+    def pack(self, sd: dict):
+        """the fp32 masters from a reference state dict (keys this store does not map are ignored; the bf16 mirrors are left to `load`)"""
+        sd = {k: v.detach().to(self.device, F32) for k, v in sd.items() if k in self._piece and torch.is_tensor(v) and v.is_floating_point()}
+        self.absent = {key for r in self.map.values() if r.optional for key, _ in r.pieces if key not in sd}
+        for name in self.order:
+            self.p(name).copy_(self.map[name].pack(sd).reshape(self.specs[name].shape))
+
+    def load(self, sd: dict):
+        self.pack(sd)
+        self.refresh_mirrors(cast=True)
+
+    def _unpacked(self, which):
+        """(reference key, the piece in the reference's shape as a view of the packed slot where possible), optional keys the last load lacked left out"""
+        flat = self._flat(which)
+        for name in self.order:
+            t = self._view(flat, name)
+            for key, unpack in self.map[name].pieces:
+                if key not in self.absent:
+                    yield key, unpack(t)
+
+    def export(self, which: str) -> dict:
+        """parameters ("p") or gradients ("g") in the reference's names, as contiguous copies"""
+        return {key: t.clone(memory_format=torch.contiguous_format) for key, t in self._unpacked(which)}
+
+    def alias_views(self, which: str = "p", prefix: str = "") -> dict:
+        """reference name -> a tensor that ALIASES the flat parameter ("p") or gradient ("g") store in the reference's shape (possibly strided: conv2's
+        channels-last weight is a permuted view), for every piece whose reference layout is a view of the packed layout; None where it is not
+        (the front end's `out` Linear, whose columns are re-ordered): those pieces are copied."""
+        base = self._flat(which).untyped_storage().data_ptr()
+        return {prefix + key: (t if t.untyped_storage().data_ptr() == base else None) for key, t in self._unpacked(which)}
+
+    def import_piece(self, key: str, value: torch.Tensor, which: str = "p"):
+        """copy ONE reference tensor into its packed parameter ("p") or gradient ("g") slot; only parameters packed from that tensor alone"""
+        name, _ = self._piece[key]
+        if len(self.map[name].pieces) != 1:
+            raise KeyError(key)
+        self._view(self._flat(which), name).copy_(self.map[name].pack({key: value.detach().to(self.device, F32)}).reshape(self.specs[name].shape))
+
+    def export_piece(self, key: str, which: str = "p") -> torch.Tensor:
+        """the current value of ONE reference parameter ("p") or its gradient ("g"), in the reference layout"""
+        name, unpack = self._piece[key]
+        return unpack(self._view(self._flat(which), name)).clone(memory_format=torch.contiguous_format)
+
 
 def ops_cast_flat(src_f32, dst_bf16):
     n = src_f32.numel()
@@ -211,7 +279,7 @@ def encoder_specs(c: dict, head: bool = True) -> list[Spec]:
 
 
 def _enc_map(c: dict, head: bool = True):
-    """packed name -> (to_packed(sd) -> tensor, [(reference key, from_packed(tensor) -> tensor), ...])"""
+    """packed name -> Ref (the encoder's packed layouts <-> the reference's state-dict names)"""
     d, L = c["hidden_size"], c["num_hidden_layers"]
     C1, C2 = c["conv_dim"]
     K = c["conv_kernel"][0]
@@ -221,10 +289,10 @@ def _enc_map(c: dict, head: bool = True):
     fe, fp = "wav2vec2.feature_extractor.", "wav2vec2.feature_projection."
     cw = "" if c.get("is_causal", False) else ".conv"
     m = {}
-    one = lambda name, key, fwd=lambda t: t, bwd=lambda t: t: m.__setitem__(name, (lambda sd: fwd(sd[key]), [(key, bwd)]))
+    one = partial(_one, m)
     # optional in the reference (present iff mask_time_prob > 0 or mask_feature_prob > 0): absent -> zeros, not exported
-    m["masked_spec_embed"] = (lambda sd: sd["wav2vec2.masked_spec_embed"] if "wav2vec2.masked_spec_embed" in sd else torch.zeros(d),
-                              [("wav2vec2.masked_spec_embed", lambda t: t)])
+    m["masked_spec_embed"] = Ref(lambda sd: sd["wav2vec2.masked_spec_embed"] if "wav2vec2.masked_spec_embed" in sd else torch.zeros(d),
+                                 [("wav2vec2.masked_spec_embed", lambda t: t)], optional=True)
     mode = context_mode(c)
     if mode:        # ContextAwareConv2d.conv is a Gated* module: keys ...conv.N.0.conv.{conv,gate}.{weight,bias} (extractors.py:23-54)
         gkh = K * (GATE_SHARE if mode == 2 else 1)
@@ -353,7 +421,92 @@ def _u01(seed: int, stream: int) -> float:
 
 
 # ====================================================================================================== trainer
-class EncoderCTCTrainer:
+class StoreTrainer:
+    """What the trainers share: parameters in ParamStores, each holding the reference keys that start with its prefix (`_named_stores()`:
+    [(prefix, store), ...], the first match wins), gradient all-reduces in `syncs()`, one optimizer step over all of them."""
+
+    def stores(self):
+        return [st for _, st in self._named_stores()]
+
+    def load_state_dict(self, sd: dict):
+        for prefix, st in self._named_stores():
+            st.load({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)})
+
+    def _export(self, which):
+        return {prefix + k: v for prefix, st in self._named_stores() for k, v in st.export(which).items()}
+
+    def state_dict(self) -> dict:
+        return self._export("p")
+
+    def grad_dict(self) -> dict:
+        """gradients in the reference's parameter names / shapes (tests, checkpoint tooling, the autograd bridge)."""
+        return self._export("g")
+
+    def optimizer_step(self, lr=None):
+        """waits for the gradient all-reduces, clears the frozen parameters' gradients, clips by the global norm over every store, applies AdamW,
+        refreshes the bf16 mirrors.  Leaves [norm, clip coefficient, skipped] on the device in `last_step_flags`; returns the norm (device scalar)."""
+        stores, sc, hp = self.stores(), self._scal, self.hp
+        with ops.pinned_stream():
+            for sync in self.syncs():
+                sync.wait()
+            for st in stores:
+                st.zero_frozen_grads()
+            sc.zero_()
+            for st in stores:
+                T.sumsq_(sc[0:1], st.flat_g)
+            T.clip_coef(sc[0:1], hp["max_grad_norm"] if hp["max_grad_norm"] else 0.0, sc[1:4], hp.get("grad_norm_skip", 0.0))
+            for st in stores:
+                st.step_count += 1
+                T.adamw_step_(st.flat_p, st.flat_g, st.flat_m, st.flat_v, st.decay, lr=hp["lr"] if lr is None else lr, betas=hp["betas"], eps=hp["eps"],
+                              weight_decay=hp["weight_decay"], step=st.step_count, norm_coef=sc[1:4], mirror=st.flat_bf)
+                st.refresh_mirrors(cast=False)
+        self.last_step_flags = sc[1:4]
+        return sc[1]
+
+    def train_step(self, feats, feat_lengths, labels, lr=None):
+        """labels: the targets `forward_backward` takes (BEST-RQ: mask_time_indices)"""
+        for st in self.stores():
+            st.zero_grad()
+        out = self.forward_backward(feats, feat_lengths, labels)
+        out["grad_norm"] = self.optimizer_step(lr)
+        return out
+
+
+class ZeroCopyTrainer(StoreTrainer):
+    """Reference-name access to the stores' aliasing views and single tensors: the HF route's zero-copy path (autograd_bridge.HipStep selects it
+    with `hasattr(trainer, "alias_views")`; optim.StoreAdamW)."""
+
+    def _route(self, key):
+        """(the store that holds a reference key, the key in that store's names)"""
+        for prefix, st in self._named_stores():
+            if key.startswith(prefix):
+                return st, key[len(prefix):]
+        raise KeyError(key)
+
+    def alias_views(self, which: str = "p", prefix: str = "") -> dict:
+        """ParamStore.alias_views of every store: the autograd bridge makes the model's nn.Parameters these views, so the HF route neither imports the
+        state dict nor exports gradients per step (autograd_bridge.py); the pieces without a view are copied (import_piece / export_grad_piece)."""
+        return {k: v for pre, st in self._named_stores() for k, v in st.alias_views(which, prefix + pre).items()}
+
+    def import_piece(self, key: str, value: torch.Tensor):
+        st, k = self._route(key)
+        st.import_piece(k, value)
+
+    def export_piece(self, key: str) -> torch.Tensor:
+        st, k = self._route(key)
+        return st.export_piece(k)
+
+    def import_grad_piece(self, key: str, grad: torch.Tensor):
+        """the gradient of ONE (non-aliasable) reference tensor into its packed gradient slot (optim.StoreAdamW: autograd owns that `.grad`, the step reads the flat store)"""
+        st, k = self._route(key)
+        st.import_piece(k, grad, "g")
+
+    def export_grad_piece(self, key: str) -> torch.Tensor:
+        st, k = self._route(key)
+        return st.export_piece(k, "g")
+
+
+class EncoderCTCTrainer(ZeroCopyTrainer):
     """forward + backward + AdamW for Wav2Vec2EBranchformerForCTC on one GPU (one process per GPU under DP)."""
 
     def __init__(self, cfg: dict, device="cuda:0", *, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, group=None,
@@ -392,8 +545,7 @@ class EncoderCTCTrainer:
                                                                      float(c.get("mask_feature_prob", 0.0) or 0.0) > 0.0)
         self.device = torch.device(device)
         self.head = bool(head)            # False: bare encoder (BEST-RQ pre-training puts its own classifier on the last hidden state)
-        self.store = ParamStore(encoder_specs(c, self.head), self.device)
-        self.map = _enc_map(c, self.head)
+        self.store = ParamStore(encoder_specs(c, self.head), self.device, _enc_map(c, self.head))
         self.hp = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm, grad_norm_skip=grad_norm_skip)
         self.sync = GradSync(self.store.flat_g, group, enabled=dp_sync)
         self._ranges_waiting = []                 # gradient ranges whose weight-gradient GEMMs are still recorded (ops_train.TnBatch), see _range_done
@@ -412,78 +564,12 @@ class EncoderCTCTrainer:
         self._encln_names = ["enc_ln_g", "enc_ln_b"] + (["mix_w"] if self.mix else [])
         self._head_names = self._encln_names + (["head_w", "head_b"] if self.head else [])
 
-    # ------------------------------------------------------------------ weights in / out
-    def load_state_dict(self, sd: dict):
-        dev = self.device
-        sdd = {k: v.detach().to(dev, F32) for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point()}
-        self._has_mse = "wav2vec2.masked_spec_embed" in sdd
-        for name in self.store.order:
-            self.store.p(name).copy_(self.map[name][0](sdd).reshape(self.store.specs[name].shape))
-        self.store.refresh_mirrors(cast=True)
+    # ------------------------------------------------------------------ weights in / out (StoreTrainer / ZeroCopyTrainer: the reference's names)
+    def _named_stores(self):
+        return [("", self.store)]
 
-    def _export(self, view):
-        out = {}
-        for name in self.store.order:
-            if name == "masked_spec_embed" and not getattr(self, "_has_mse", True):
-                continue
-            t = view(name)
-            for key, fn in self.map[name][1]:
-                out[key] = fn(t).clone(memory_format=torch.contiguous_format)
-        return out
-
-    def state_dict(self) -> dict:
-        return self._export(self.store.p)
-
-    def alias_views(self, which: str = "p", prefix: str = "") -> dict:
-        """reference name -> a tensor that ALIASES the flat parameter ("p") or gradient ("g") store in the reference's shape (possibly strided: conv2's
-        channels-last weight is a permuted view), for every piece whose reference layout is a view of the packed layout; None where it is not
-        (the front end's `out` Linear, whose columns are re-ordered): those pieces are copied.  The autograd bridge makes the model's nn.Parameters
-        these views, so the HF route neither imports the state dict nor exports gradients per step (autograd_bridge.py)."""
-        flat = self.store.flat_p if which == "p" else self.store.flat_g
-        base = flat.untyped_storage().data_ptr()
-        out = {}
-        for name in self.store.order:
-            if name == "masked_spec_embed" and not getattr(self, "_has_mse", True):
-                continue
-            t = self.store._view(flat, name)
-            for key, fn in self.map[name][1]:
-                v = fn(t)
-                out[prefix + key] = v if v.untyped_storage().data_ptr() == base else None
-        return out
-
-    def stores(self):
-        return [self.store]
-
-    def import_piece(self, key: str, value: torch.Tensor):
-        """copy ONE reference tensor into its (non-aliasable) packed slot"""
-        for name in self.store.order:
-            if len(self.map[name][1]) == 1 and self.map[name][1][0][0] == key:
-                self.store.p(name).copy_(self.map[name][0]({key: value.detach().to(self.device, F32)}).reshape(self.store.specs[name].shape))
-                return
-        raise KeyError(key)
-
-    def export_grad_piece(self, key: str) -> torch.Tensor:
-        for name in self.store.order:
-            for k, fn in self.map[name][1]:
-                if k == key:
-                    return fn(self.store.g(name)).clone(memory_format=torch.contiguous_format)
-        raise KeyError(key)
-
-    def import_grad_piece(self, key: str, grad: torch.Tensor):
-        """the gradient of ONE (non-aliasable) reference tensor into its packed gradient slot (optim.StoreAdamW: autograd owns that `.grad`, the step reads the flat store)"""
-        for name in self.store.order:
-            if len(self.map[name][1]) == 1 and self.map[name][1][0][0] == key:
-                self.store.g(name).copy_(self.map[name][0]({key: grad.detach().to(self.device, F32)}).reshape(self.store.specs[name].shape))
-                return
-        raise KeyError(key)
-
-    def export_piece(self, key: str) -> torch.Tensor:
-        """the current master value of ONE reference tensor, in the reference layout"""
-        for name in self.store.order:
-            for k, fn in self.map[name][1]:
-                if k == key:
-                    return fn(self.store.p(name)).clone(memory_format=torch.contiguous_format)
-        raise KeyError(key)
+    def syncs(self):
+        return [self.sync]
 
     def set_frozen(self, reference_names):
         """Names (reference state-dict keys) of parameters that do not train (`requires_grad False`: `freeze_encoder()`, train_ctc_asr.py:51-52).
@@ -491,7 +577,7 @@ class EncoderCTCTrainer:
         are then skipped in the backward (their input gradients are still computed: something upstream may train).  On the native route
         (`train_step`) frozen parameters stay bit-identical: no weight decay, gradients cleared before the clip norm and AdamW."""
         ref = set(reference_names or ())
-        frozen = {name for name in self.store.order if name in self.map and self.map[name][1] and all(k in ref for k, _ in self.map[name][1])}
+        frozen = {name for name, r in self.store.map.items() if r.pieces and all(k in ref for k, _ in r.pieces)}
         if frozen != self.frozen:                 # the autograd bridge calls this every step: rebuild the device mask only when the set changes
             self.store.set_frozen(frozen)         # native route: AdamW leaves them bit-identical (no decay, zero gradient), the clip norm skips them
         self.frozen = frozen
@@ -523,10 +609,6 @@ class EncoderCTCTrainer:
         if getattr(self, "_lnred", None) is None:
             self._lnred = T.LnReduceBatch(self.device)        # the (dgamma | dbeta) reductions of a layer's LayerNorms: one launch per flush, not one per LayerNorm
         return dict(dgamma=self.store.g(gname), dbeta=self.store.g(bname), defer=self._lnred)
-
-    def grad_dict(self) -> dict:
-        """gradients in the reference's parameter names / shapes (tests, checkpoint tooling, the autograd bridge)."""
-        return self._export(self.store.g)
 
     # ------------------------------------------------------------------ tables
     def out_frames(self, Tn):
@@ -1159,30 +1241,3 @@ class EncoderCTCTrainer:
         dpb = T.colsum_cast(dpp[:, off * d:(off + Pn) * d]).view(Pn, d)
         T.gemm_tn_(G(p + "att_wpos"), dpb, pos[0], defer=self._tnb)
         return dqkv
-
-    # ------------------------------------------------------------------ optimizer
-    def optimizer_step(self, lr=None):
-        """waits for the gradient all-reduces, clips by global norm, applies AdamW, refreshes the bf16 mirrors."""
-        with ops.pinned_stream():
-            return self._optimizer_step(lr)
-
-    def _optimizer_step(self, lr=None):
-        st, hp = self.store, self.hp
-        self.sync.wait()
-        st.zero_frozen_grads()
-        sc = self._scal
-        sc.zero_()
-        T.sumsq_(sc[0:1], st.flat_g)
-        T.clip_coef(sc[0:1], hp["max_grad_norm"] if hp["max_grad_norm"] else 0.0, sc[1:4], hp.get("grad_norm_skip", 0.0))
-        st.step_count += 1
-        T.adamw_step_(st.flat_p, st.flat_g, st.flat_m, st.flat_v, st.decay, lr=hp["lr"] if lr is None else lr, betas=hp["betas"], eps=hp["eps"],
-                      weight_decay=hp["weight_decay"], step=st.step_count, norm_coef=sc[1:4], mirror=st.flat_bf)
-        st.refresh_mirrors(cast=False)
-        self.last_step_flags = sc[1:4]
-        return sc[1]          # gradient norm (device scalar)
-
-    def train_step(self, feats, feat_lengths, labels, lr=None):
-        self.store.zero_grad()
-        out = self.forward_backward(feats, feat_lengths, labels)
-        out["grad_norm"] = self.optimizer_step(lr)
-        return out

@@ -13,13 +13,14 @@ restrictions as train.py; GPT-2's embd / attn / resid dropouts use the same coun
 from __future__ import annotations
 
 import math
+from functools import partial
 
 import torch
 
 from . import ops
 from . import ops_train as T
 from .decoder import shift_tokens_right
-from .train import BF16, F32, EncoderCTCTrainer, GradSync, ParamStore, Spec
+from .train import BF16, F32, EncoderCTCTrainer, GradSync, ParamStore, Spec, ZeroCopyTrainer, _one
 
 
 def decoder_specs(c: dict, enc_dim: int, with_proj: bool) -> list[Spec]:
@@ -49,7 +50,7 @@ def decoder_specs(c: dict, enc_dim: int, with_proj: bool) -> list[Spec]:
 def _dec_map(c: dict, with_proj: bool, prefix="decoder."):
     L = c["n_layer"]
     m = {}
-    one = lambda name, key, fwd=lambda t: t, bwd=lambda t: t: m.__setitem__(name, (lambda sd: fwd(sd[key]), [(key, bwd)]))
+    one = partial(_one, m)
     tr_in = lambda t: t.t().contiguous()                   # transformers Conv1D stores (in, out); the store keeps (out, in)
     tr = lambda t: t.t()                                   # export: a transposed VIEW (alias_views hands it to the nn.Parameter; state_dict() clones it contiguous)
     if with_proj:
@@ -134,7 +135,7 @@ def attention_bwd_fused(q, k, v, ctx, dctx, lse, dq, dk, dv, B, Tq, Tk, H, *, le
     T.bgemm(ds, (*sS, 1, Ts), q, (hd, Tq * sq, 1, sq), dk, (hd, Tk * dk.stride(0), dk.stride(0)), H, B, Tk, hd, Tq, m_valid=lengths)
 
 
-class JointAEDTrainer:
+class JointAEDTrainer(ZeroCopyTrainer):
     """forward + backward + AdamW for JointCTCAttentionEncoderDecoder (E-Branchformer encoder + multi-head GPT-2 decoder)."""
 
     def __init__(self, enc_cfg: dict, dec_cfg: dict, joint_cfg: dict, device="cuda:0", *, lr=2e-3, betas=(0.9, 0.999), eps=1e-8,
@@ -152,10 +153,9 @@ class JointAEDTrainer:
                                      dp_sync=dp_sync, seed=seed)
         enc_dim = enc_cfg["hidden_size"]
         self.with_proj = (enc_dim != d) if with_proj is None else with_proj
-        self.store = ParamStore(decoder_specs(c, enc_dim, self.with_proj), self.device)
-        self.map = _dec_map(c, self.with_proj)
+        self.store = ParamStore(decoder_specs(c, enc_dim, self.with_proj), self.device, _dec_map(c, self.with_proj))
         self.sync = GradSync(self.store.flat_g, group, enabled=dp_sync)
-        self.hp = self.enc.hp
+        self.hp, self._scal = self.enc.hp, self.enc._scal
         if c.get("pos_emb_fixed", False):
             n = c.get("n_positions", 1024)
             inv = 1 / (10000 ** (torch.arange(0.0, d, 2.0) / d))
@@ -165,80 +165,17 @@ class JointAEDTrainer:
         else:
             self.pos_fixed, self.emb_scale = None, 1.0
 
-    # ------------------------------------------------------------------ weights
-    def load_state_dict(self, sd: dict):
-        self.enc.load_state_dict({k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")})
-        sdd = {k: v.detach().to(self.device, F32) for k, v in sd.items() if torch.is_tensor(v) and v.is_floating_point() and not k.startswith("encoder.")}
-        for name in self.store.order:
-            self.store.p(name).copy_(self.map[name][0](sdd).reshape(self.store.specs[name].shape))
-        self.store.refresh_mirrors(cast=True)
+    # ------------------------------------------------------------------ weights (the encoder's reference keys carry an `encoder.` prefix)
+    def _named_stores(self):
+        return [("encoder.", self.enc.store), ("", self.store)]
+
+    def syncs(self):
+        return [self.enc.sync, self.sync]
 
     def set_frozen(self, reference_names):
         """frozen encoder parameters (freeze_encoder): their weight-gradient GEMMs are skipped and, on the native route, AdamW leaves them
         untouched (train.EncoderCTCTrainer.set_frozen); decoder parameters always train"""
         self.enc.set_frozen({k[len("encoder."):] for k in (reference_names or ()) if k.startswith("encoder.")})
-
-    def _export(self, view):
-        out = {"encoder." + k: v for k, v in (self.enc.state_dict() if view == "p" else self.enc.grad_dict()).items()}
-        for name in self.store.order:
-            t = self.store.p(name) if view == "p" else self.store.g(name)
-            for key, fn in self.map[name][1]:
-                out[key] = fn(t).clone(memory_format=torch.contiguous_format)
-        return out
-
-    def state_dict(self): return self._export("p")
-    def grad_dict(self): return self._export("g")
-
-    def alias_views(self, which: str = "p") -> dict:
-        """train.EncoderCTCTrainer.alias_views for both stores (encoder keys prefixed `encoder.`)"""
-        out = self.enc.alias_views(which, prefix="encoder.")
-        flat = self.store.flat_p if which == "p" else self.store.flat_g
-        base = flat.untyped_storage().data_ptr()
-        for name in self.store.order:
-            t = self.store._view(flat, name)
-            for key, fn in self.map[name][1]:
-                v = fn(t)
-                out[key] = v if v.untyped_storage().data_ptr() == base else None
-        return out
-
-    def import_piece(self, key: str, value):
-        if key.startswith("encoder."):
-            return self.enc.import_piece(key[len("encoder."):], value)
-        for name in self.store.order:
-            if len(self.map[name][1]) == 1 and self.map[name][1][0][0] == key:
-                self.store.p(name).copy_(self.map[name][0]({key: value.detach().to(self.device, F32)}).reshape(self.store.specs[name].shape))
-                return
-        raise KeyError(key)
-
-    def export_grad_piece(self, key: str):
-        if key.startswith("encoder."):
-            return self.enc.export_grad_piece(key[len("encoder."):])
-        for name in self.store.order:
-            for k, fn in self.map[name][1]:
-                if k == key:
-                    return fn(self.store.g(name)).clone(memory_format=torch.contiguous_format)
-        raise KeyError(key)
-
-    def import_grad_piece(self, key: str, grad):
-        if key.startswith("encoder."):
-            return self.enc.import_grad_piece(key[len("encoder."):], grad)
-        for name in self.store.order:
-            if len(self.map[name][1]) == 1 and self.map[name][1][0][0] == key:
-                self.store.g(name).copy_(self.map[name][0]({key: grad.detach().to(self.device, F32)}).reshape(self.store.specs[name].shape))
-                return
-        raise KeyError(key)
-
-    def export_piece(self, key: str):
-        if key.startswith("encoder."):
-            return self.enc.export_piece(key[len("encoder."):])
-        for name in self.store.order:
-            for k, fn in self.map[name][1]:
-                if k == key:
-                    return fn(self.store.p(name)).clone(memory_format=torch.contiguous_format)
-        raise KeyError(key)
-
-    def stores(self):
-        return [self.enc.store, self.store]
 
     # ------------------------------------------------------------------ decoder forward + backward (called inside the encoder's backward)
     def _decoder(self, last_hidden, B, T2, key_len, labels, out, gs):
@@ -428,30 +365,4 @@ class JointAEDTrainer:
 
         eo = self.enc.forward_backward(feats, feat_lengths, labels, loss_scale=w, extra_hidden_grad=hook)
         out.update(enc_loss=eo["loss"], encoder_logits=eo["logits"], loss=w * eo["loss"] + (1 - w) * out["dec_loss"])
-        return out
-
-    def optimizer_step(self, lr=None):
-        with ops.pinned_stream():
-            return self._optimizer_step(lr)
-
-    def _optimizer_step(self, lr=None):
-        hp = self.hp
-        self.enc.sync.wait(); self.sync.wait()
-        self.enc.store.zero_frozen_grads()          # frozen encoder parameters (set_frozen): no update, not in the clip norm
-        sc = self.enc._scal
-        sc.zero_()
-        T.sumsq_(sc[0:1], self.enc.store.flat_g)
-        T.sumsq_(sc[0:1], self.store.flat_g)
-        T.clip_coef(sc[0:1], hp["max_grad_norm"] if hp["max_grad_norm"] else 0.0, sc[1:4], hp.get("grad_norm_skip", 0.0))
-        for st in (self.enc.store, self.store):
-            st.step_count += 1
-            T.adamw_step_(st.flat_p, st.flat_g, st.flat_m, st.flat_v, st.decay, lr=hp["lr"] if lr is None else lr, betas=hp["betas"], eps=hp["eps"],
-                          weight_decay=hp["weight_decay"], step=st.step_count, norm_coef=sc[1:4], mirror=st.flat_bf)
-            st.refresh_mirrors(cast=False)
-        return sc[1]
-
-    def train_step(self, feats, feat_lengths, labels, lr=None):
-        self.enc.store.zero_grad(); self.store.zero_grad()
-        out = self.forward_backward(feats, feat_lengths, labels)
-        out["grad_norm"] = self.optimizer_step(lr)
         return out

@@ -15,10 +15,10 @@ import torch
 
 from . import _lib, ops
 from . import ops_train as T
-from .train import BF16, F32, EncoderCTCTrainer, GradSync, ParamStore, Spec
+from .train import BF16, F32, EncoderCTCTrainer, GradSync, ParamStore, Spec, StoreTrainer, _one
 
 
-class BestRQTrainer:
+class BestRQTrainer(StoreTrainer):
     def __init__(self, cfg: dict, device="cuda:0", *, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=1.0, group=None,
                  dp_sync=True, seed=0, noise_std=0.1):
         c = self.cfg = dict(cfg)
@@ -30,39 +30,29 @@ class BestRQTrainer:
         self.enc = EncoderCTCTrainer(enc_cfg, device, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
                                      group=group, dp_sync=dp_sync, seed=seed, head=False)
         d = c["hidden_size"]
-        specs = []
+        specs, m = [], {}
         for k in range(self.nb):
             specs += [Spec(f"cls{k}_w", (self.C, d), True, True), Spec(f"cls{k}_b", (self.C,), False, False)]
-        self.store = ParamStore(specs, self.device)
+            _one(m, f"cls{k}_w", f"classifiers.{k}.weight"); _one(m, f"cls{k}_b", f"classifiers.{k}.bias")
+        self.store = ParamStore(specs, self.device, m)
         self.sync = GradSync(self.store.flat_g, group, enabled=dp_sync)
-        self.hp = self.enc.hp
+        self.hp, self._scal = self.enc.hp, self.enc._scal
         self.P = self.CB = None
 
     # ------------------------------------------------------------------ weights
-    def load_state_dict(self, sd: dict):
-        dev = self.device
-        self.enc.load_state_dict({k: v for k, v in sd.items() if k.startswith("wav2vec2.")})
-        for k in range(self.nb):
-            self.store.p(f"cls{k}_w").copy_(sd[f"classifiers.{k}.weight"].detach().to(dev, F32))
-            self.store.p(f"cls{k}_b").copy_(sd[f"classifiers.{k}.bias"].detach().to(dev, F32))
-        self.store.refresh_mirrors(cast=True)
-        self.P = sd["rpq.P"].detach().to(dev, F32).contiguous()        # (books, in_dim, cd) frozen buffers
-        self.CB = sd["rpq.CB"].detach().to(dev, F32).contiguous()      # (books, C, cd)
+    def _named_stores(self):
+        return [("", self.enc.store), ("", self.store)]
 
-    def _export(self, enc_view, view):
-        out = dict(enc_view())
-        for k in range(self.nb):
-            out[f"classifiers.{k}.weight"] = view(f"cls{k}_w").clone()
-            out[f"classifiers.{k}.bias"] = view(f"cls{k}_b").clone()
-        return out
+    def syncs(self):
+        return [self.enc.sync, self.sync]
+
+    def load_state_dict(self, sd: dict):
+        super().load_state_dict(sd)
+        self.P = sd["rpq.P"].detach().to(self.device, F32).contiguous()        # (books, in_dim, cd) frozen buffers
+        self.CB = sd["rpq.CB"].detach().to(self.device, F32).contiguous()      # (books, C, cd)
 
     def state_dict(self):
-        out = self._export(self.enc.state_dict, self.store.p)
-        out["rpq.P"], out["rpq.CB"] = self.P.clone(), self.CB.clone()
-        return out
-
-    def grad_dict(self):
-        return self._export(self.enc.grad_dict, self.store.g)
+        return super().state_dict() | {"rpq.P": self.P.clone(), "rpq.CB": self.CB.clone()}
 
     # ------------------------------------------------------------------ pieces
     def targets(self, feats, mask_time_indices):
@@ -127,25 +117,4 @@ class BestRQTrainer:
             eo = self.enc.forward_backward(feats, feat_lengths, None, backward=False, train_mode=True, noise_mask=(tm, self.noise_std))
             heads(eo["last_hidden"].reshape(B * T2, d), False)
         out.update(last_hidden=eo["last_hidden"], targets=tg)
-        return out
-
-    def optimizer_step(self, lr=None):
-        hp = self.hp
-        self.enc.sync.wait(); self.sync.wait()
-        sc = self.enc._scal
-        sc.zero_()
-        T.sumsq_(sc[0:1], self.enc.store.flat_g)
-        T.sumsq_(sc[0:1], self.store.flat_g)
-        T.clip_coef(sc[0:1], hp["max_grad_norm"] if hp["max_grad_norm"] else 0.0, sc[1:4], hp.get("grad_norm_skip", 0.0))
-        for s_ in (self.enc.store, self.store):
-            s_.step_count += 1
-            T.adamw_step_(s_.flat_p, s_.flat_g, s_.flat_m, s_.flat_v, s_.decay, lr=hp["lr"] if lr is None else lr, betas=hp["betas"], eps=hp["eps"],
-                          weight_decay=hp["weight_decay"], step=s_.step_count, norm_coef=sc[1:4], mirror=s_.flat_bf)
-            s_.refresh_mirrors(cast=False)
-        return sc[1]
-
-    def train_step(self, feats, feat_lengths, mask_time_indices, lr=None):
-        self.enc.store.zero_grad(); self.store.zero_grad()
-        out = self.forward_backward(feats, feat_lengths, mask_time_indices)
-        out["grad_norm"] = self.optimizer_step(lr)
         return out

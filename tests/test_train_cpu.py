@@ -17,17 +17,13 @@ def _sd(cfg, seed=3):
 
 @pytest.mark.parametrize("extra", [{}, {"position_embeddings_type": "rotary"}])
 def test_packed_layout_roundtrips_every_reference_parameter(extra):
+    """ParamStore's reference-name API on CPU (`pack` is `load` without the bf16 mirror refresh, which runs on the GPU)."""
     cfg = dict(shapes.TINY, **extra)
     sd = _sd(cfg)
-    specs = encoder_specs(cfg)
-    mp_ = _enc_map(cfg)
-    store = ParamStore(specs, "cpu")
-    covered = {}
-    for s in specs:
-        packed = mp_[s.name][0](sd).reshape(s.shape)
-        store.p(s.name).copy_(packed)
-        for key, back in mp_[s.name][1]:
-            covered[key] = back(store.p(s.name))
+    store = ParamStore(encoder_specs(cfg), "cpu", _enc_map(cfg))
+    assert set(store.export("p")) == set(sd)                          # before any load nothing is skipped
+    store.pack(sd)
+    covered = store.export("p")
     assert set(covered) == set(sd), (sorted(set(sd) - set(covered))[:5], sorted(set(covered) - set(sd))[:5])
     for k, v in sd.items():
         assert covered[k].shape == v.shape and torch.equal(covered[k], v), k
@@ -35,6 +31,31 @@ def test_packed_layout_roundtrips_every_reference_parameter(extra):
     offs = sorted((store.off[n], n) for n in store.order)
     for (o, n), (o2, _) in zip(offs, offs[1:]):
         assert o % 64 == 0 and o + torch.Size(store.specs[n].shape).numel() <= o2
+    # one piece in / out by reference key, parameters and gradients; a piece of a packed concatenation exports but does not import alone
+    wo, wq = "wav2vec2.encoder.layers.0.self_attn.linear_out.weight", "wav2vec2.encoder.layers.0.self_attn.linear_q.weight"
+    for which, view in (("p", store.p), ("g", store.g)):
+        new = torch.randn_like(sd[wo])
+        store.import_piece(wo, new, which)
+        assert torch.equal(view("l0.att_wo"), new) and torch.equal(store.export_piece(wo, which), new)
+    assert torch.equal(store.export_piece(wq), sd[wq])
+    for bad in ("no.such.key", wq):
+        with pytest.raises(KeyError):
+            store.import_piece(bad, sd[wq])
+    with pytest.raises(KeyError):
+        store.export_piece("no.such.key")
+    # aliasing views: every piece but the front end's re-ordered `out` Linear is a view of the flat store
+    fe_out = "wav2vec2.feature_extractor.out.weight"
+    for which, flat in (("p", store.flat_p), ("g", store.flat_g)):
+        views = store.alias_views(which, prefix="m.")
+        assert set(views) == {"m." + k for k in sd} and views["m." + fe_out] is None
+        for k, v in views.items():
+            assert k == "m." + fe_out or (v.untyped_storage().data_ptr() == flat.untyped_storage().data_ptr()
+                                         and torch.equal(v, store.export_piece(k[2:], which))), k
+    # the optional SpecAugment vector: absent from the loaded state dict -> zeros, and neither exported nor aliased
+    mse = "wav2vec2.masked_spec_embed"
+    store.pack({k: v for k, v in sd.items() if k != mse})
+    assert not store.p("masked_spec_embed").any()
+    assert set(store.export("p")) == set(sd) - {mse} and set(store.alias_views("g")) == set(sd) - {mse}
 
 
 def test_weight_decay_mask_follows_hf_trainer_rule():
@@ -95,8 +116,6 @@ def test_decoder_layout_roundtrips_reference_names():
     from huggingface_asr_amd.train_aed import _dec_map, decoder_specs
     for fixed in (False, True):
         c = dict(TINY_DEC, pos_emb_fixed=fixed, tie_word_embeddings=False)
-        specs = decoder_specs(c, 64, True)
-        mp_ = _dec_map(c, True)
         d, V, L = c["n_embd"], c["vocab_size"], c["n_layer"]
         sd = {"enc_to_dec_proj.weight": torch.randn(d, 64), "enc_to_dec_proj.bias": torch.randn(d), "decoder.lm_head.weight": torch.randn(V, d),
               "decoder.additional_lm_heads.0.weight": torch.randn(V, d), "decoder.transformer.ln_f.weight": torch.randn(d), "decoder.transformer.ln_f.bias": torch.randn(d)}
@@ -111,12 +130,9 @@ def test_decoder_layout_roundtrips_reference_names():
             for n, (i, o) in (("attn.c_attn", (d, 3 * d)), ("attn.c_proj", (d, d)), ("crossattention.q_attn", (d, d)), ("crossattention.c_attn", (d, 2 * d)),
                               ("crossattention.c_proj", (d, d)), ("mlp.c_fc", (d, 4 * d)), ("mlp.c_proj", (4 * d, d))):
                 sd[r + n + ".weight"] = torch.randn(i, o); sd[r + n + ".bias"] = torch.randn(o)
-        store = ParamStore(specs, "cpu")
-        covered = {}
-        for s_ in specs:
-            store.p(s_.name).copy_(mp_[s_.name][0](sd).reshape(s_.shape))
-            for key, back in mp_[s_.name][1]:
-                covered[key] = back(store.p(s_.name))
+        store = ParamStore(decoder_specs(c, 64, True), "cpu", _dec_map(c, True))
+        store.pack(sd)
+        covered = store.export("p")
         assert set(covered) == set(sd)
         for k, v in sd.items():
             assert torch.equal(covered[k], v), k
