@@ -417,6 +417,37 @@ def attn_bwd_probs(qkv, B, T, H, ctx, dctx, lse, dq, *, pos=None, bias_u=None, b
     return (prob, ds, dbd, su, sv, qu, qv) if qb else (prob, ds, dbd, su, sv)
 
 
+def attn_bwd_fused(qkv, B, T, H, ctx, dctx, lse, dqkv, *, lengths=None):
+    """Backward of `ops.attention_qkv(qkv, B, T, H, lengths=, lse=)` (no positions, no dropout, head size 64 / 128) with no (H, B, T, T) tensor: P and dS are
+    recomputed from Q, K and lse (attn_bwd_fused.hip).  dqkv (B*T, 3d) bf16 receives [dQ | dK | dV], every element written; bitwise reproducible."""
+    d = qkv.shape[1] // 3
+    hd = d // H
+    _req(qkv, BF16); _req(dqkv, BF16); _req(ctx, BF16); _req(dctx, BF16)
+    if dqkv.shape != (B * T, 3 * d) or qkv.shape[0] != B * T or lse.dtype != F32 or lse.numel() != B * H * T:
+        raise ValueError("attn_bwd_fused: shape mismatch")
+    ws = torch.empty(B * H * T, device=qkv.device, dtype=F32)
+    _lib.check(_L().mi_attention_qkv_bwd_fused(qkv[:, :d].data_ptr(), qkv[:, d:2 * d].data_ptr(), qkv[:, 2 * d:].data_ptr(), qkv.stride(0), _p(lengths),
+                                               ctx.data_ptr(), ctx.stride(0), dctx.data_ptr(), dctx.stride(0), lse.data_ptr(),
+                                               dqkv[:, :d].data_ptr(), dqkv[:, d:2 * d].data_ptr(), dqkv[:, 2 * d:].data_ptr(), dqkv.stride(0),
+                                               ws.data_ptr(), ws.numel() * 4, B, T, H, hd, 1.0 / math.sqrt(hd), _stream()), "mi_attention_qkv_bwd_fused")
+    return dqkv
+
+
+def attn_bwd_materialized(qkv, B, T, H, ctx, dctx, lse, dqkv, *, lengths=None):
+    """The same gradient through the materialising path (`attn_bwd_probs` writes P and dS as (H, B, T, Ts) bf16, two `bgemm`s make dV and dK): the yardstick
+    the fused kernel is measured and tested against."""
+    d = qkv.shape[1] // 3
+    hd = d // H
+    prob, ds, _, _, _ = attn_bwd_probs(qkv, B, T, H, ctx, dctx, lse, dqkv[:, :d], lengths=lengths)      # also dQ = dS K
+    Ts = prob.shape[-1]
+    sTT = (B * T * Ts, T * Ts)
+    bgemm(prob, (*sTT, 1, Ts), dctx, (hd, T * dctx.stride(0), 1, dctx.stride(0)), dqkv[:, 2 * d:], (hd, T * 3 * d, 3 * d), H, B, T, hd, T,
+          m_valid=lengths)                                                                                   # dV = P^T dctx
+    bgemm(ds, (*sTT, 1, Ts), qkv[:, :d], (hd, T * qkv.stride(0), 1, qkv.stride(0)), dqkv[:, d:2 * d], (hd, T * 3 * d, 3 * d), H, B, T, hd, T,
+          m_valid=lengths)                                                                                   # dK = dS^T q
+    return dqkv
+
+
 def pad8(n: int) -> int:
     return (n + 7) // 8 * 8
 

@@ -135,6 +135,148 @@ class WhisperEncoderEngine:
         ops.layernorm_chain(x, lna=w["lnf"], outa32=out)
         return out.view(B, T2, d)
 
+    # ---------------------------------------------------------------------------------------------------------------------------------------------
+    # Training: forward_train keeps what the backward reads; backward runs LayerNorm / GEMM dgrad + wgrad / GELU' / im2col + col2im and the attention
+    # backward (ops_train.attn_bwd_fused: no (H, B, T, T) tensor) on the HIP kernels.  Dropout is not covered (the binding hands such calls to transformers).
+    fused_attn_bwd = False      # True: ops_train.attn_bwd_fused (no (H, B, T, T) tensor); False: attn_bwd_probs + bgemm, which measured as fast at T' = 1500 (DESIGN "Whisper encoder training")
+
+    def _wT(self, key, wm):
+        """the transposed copy of a bf16 weight (N, K) -> (K, pad64(N)) for the dX GEMMs, made once per weight version (the engine is rebuilt when a parameter changes)"""
+        from . import ops_train as OT
+        cache = self.__dict__.setdefault("_wT_cache", {})
+        if key not in cache:
+            cache[key] = OT.transpose(wm)
+        return cache[key]
+
+    def forward_train(self, input_features: torch.Tensor, skip=None) -> tuple[torch.Tensor, dict]:
+        """-> (last_hidden_state (B, T/2, d) fp32, saved).  skip: per layer, True = LayerDrop skipped it."""
+        from . import ops_train as OT
+        c, w, dev = self.cfg, self.w, self.device
+        L = _lib.lib()
+        st = torch.cuda.current_stream().cuda_stream
+        d, H = c["d_model"], c["encoder_attention_heads"]
+        B, mel, T = input_features.shape
+        P = w["pos"].shape[0]
+        if T != 2 * P:
+            raise ValueError(f"Whisper expects the mel input features to be of length {2 * P}, but found {T}")
+        x32 = input_features.detach().to(torch.float32).contiguous()
+        fcl = torch.empty((B, T, mel), dtype=BF16, device=dev)
+        _lib.check(L.mi_transpose_cast_bct_btc(x32.data_ptr(), fcl.data_ptr(), B, mel, T, st), "mi_transpose_cast_bct_btc")
+        h1p = ops.conv2d_cl(fcl.view(B, T, 1, mel), w["c1w"], w["c1b"], K=(3, 1), stride=1, pad=(1, 0), act="none")
+        h1 = OT.act_fwd(h1p.view(B * T, d)).view(B, T, 1, d)
+        h2p = ops.conv2d_cl(h1, w["c2w"], w["c2b"], K=(3, 1), stride=2, pad=(1, 0), act="none")
+        T2 = h2p.shape[1]
+        M = B * T2
+        h2 = OT.act_fwd(h2p.view(M, d))
+        x = torch.empty((M, d), dtype=torch.float32, device=dev)
+        _lib.check(L.mi_add_positions(h2.data_ptr(), w["pos"].data_ptr(), x.data_ptr(), M, T2, d, st), "mi_add_positions")
+        skip = skip or [False] * len(w["layers"])
+        layers = []
+        for lw, sk in zip(w["layers"], skip):
+            if sk:
+                layers.append(None)
+                continue
+            S = dict(x_in=x)
+            a = torch.empty((M, d), dtype=BF16, device=dev)
+            ops.layernorm_chain(x, lna=lw["ln1"], outa=a)
+            S["a1"] = a
+            S["qkv"] = qkv = ops.gemm(a, lw["wqkv"], lw["bqkv"])
+            S["lse"] = lse = torch.empty((B, H, T2), dtype=torch.float32, device=dev)
+            S["ctx"] = ctx = ops.attention_qkv(qkv, B, T2, H, lse=lse)
+            xm = ops.gemm(ctx, lw["wo"], lw["bo"], out=torch.empty((M, d), dtype=torch.float32, device=dev), resid=x, alpha=1.0)
+            S["x_mid"] = xm
+            a2 = torch.empty((M, d), dtype=BF16, device=dev)
+            ops.layernorm_chain(xm, lna=lw["ln2"], outa=a2)
+            S["a2"] = a2
+            S["m_pre"], S["m"] = OT.gemm_act_fwd(a2, lw["w1"], lw["b1"], "gelu")
+            x = ops.gemm(S["m"], lw["w2"], lw["b2"], out=torch.empty((M, d), dtype=torch.float32, device=dev), resid=xm, alpha=1.0)
+            layers.append(S)
+        out = torch.empty((M, d), dtype=torch.float32, device=dev)
+        ops.layernorm_chain(x, lna=w["lnf"], outa32=out)
+        saved = dict(B=B, T=T, T2=T2, mel=mel, fcl=fcl, h1p=h1p, h1=h1, h2p=h2p, x_last=x, layers=layers)
+        return out.view(B, T2, d), saved
+
+    def backward(self, saved: dict, d_last_hidden: torch.Tensor, want) -> dict:
+        """Gradients keyed by the HF `WhisperEncoder` parameter names (`want(name)` -> bool; None for what is not wanted), fp32 in the parameters' shapes, plus
+        "input_features" when want("input_features")."""
+        from . import ops_train as OT
+        c, w, dev = self.cfg, self.w, self.device
+        d, H = c["d_model"], c["encoder_attention_heads"]
+        B, T, T2, mel = saved["B"], saved["T"], saved["T2"], saved["mel"]
+        M = B * T2
+        f32 = torch.float32
+        z = lambda *shape: torch.zeros(shape, dtype=f32, device=dev)
+        G = {}
+
+        def slot(name, *shape):
+            if want(name):
+                G[name] = z(*shape)
+                return G[name]
+            return None
+        dy = d_last_hidden.detach().reshape(M, d).to(f32).contiguous()
+        dx = torch.empty((M, d), dtype=f32, device=dev)
+        OT.layernorm_bwd(saved["x_last"], w["lnf"][0], dy, dx, accumulate=False, dgamma=slot("layer_norm.weight", d), dbeta=slot("layer_norm.bias", d))
+        for l in reversed(range(len(w["layers"]))):
+            S, lw = saved["layers"][l], w["layers"][l]
+            if S is None:                                   # LayerDrop skipped it: identity, no gradient
+                continue
+            p = f"layers.{l}."
+            ffn = lw["w1"].shape[0]
+            # FFN: x = x_mid + fc2(gelu(fc1(LN2(x_mid))))
+            dyb = OT.add_cast(dx)
+            dw2, db2 = slot(p + "fc2.weight", d, ffn), slot(p + "fc2.bias", d)
+            if dw2 is not None or db2 is not None:
+                OT.linear_bwd(dyb, S["m"], None, dw=dw2, db=db2, need_dx=False)
+            dmp = OT.gemm_act_bwd(dyb, self._wT((l, "w2"), lw["w2"]), S["m_pre"], "gelu")
+            dw1, db1 = slot(p + "fc1.weight", ffn, d), slot(p + "fc1.bias", ffn)
+            da2 = OT.linear_bwd(dmp, S["a2"], self._wT((l, "w1"), lw["w1"]), dw=dw1, db=db1)
+            OT.layernorm_bwd(S["x_mid"], lw["ln2"][0], da2, dx, accumulate=True, dgamma=slot(p + "final_layer_norm.weight", d), dbeta=slot(p + "final_layer_norm.bias", d))
+            # attention: x_mid = x_in + out_proj(attn(LN1(x_in)))
+            dyb = OT.add_cast(dx)
+            dctx = OT.linear_bwd(dyb, S["ctx"], self._wT((l, "wo"), lw["wo"]), dw=slot(p + "self_attn.out_proj.weight", d, d), db=slot(p + "self_attn.out_proj.bias", d))
+            dqkv = torch.empty((M, 3 * d), dtype=BF16, device=dev)
+            (OT.attn_bwd_fused if self.fused_attn_bwd else OT.attn_bwd_materialized)(S["qkv"], B, T2, H, S["ctx"], dctx, S["lse"], dqkv)
+            names = [p + f"self_attn.{n}_proj.weight" for n in "qkv"]
+            dwqkv = z(3 * d, d) if any(want(n) for n in names) else None
+            dbqkv = z(3 * d) if (want(p + "self_attn.q_proj.bias") or want(p + "self_attn.v_proj.bias")) else None
+            da1 = OT.linear_bwd(dqkv, S["a1"], self._wT((l, "wqkv"), lw["wqkv"]), dw=dwqkv, db=dbqkv)
+            for i, n in enumerate(names):
+                if dwqkv is not None and want(n):
+                    G[n] = dwqkv[i * d:(i + 1) * d]                 # row views of the packed [Wq; Wk; Wv] gradient
+            for i, n in ((0, "q"), (2, "v")):                       # k_proj has no bias
+                if dbqkv is not None and want(p + f"self_attn.{n}_proj.bias"):
+                    G[p + f"self_attn.{n}_proj.bias"] = dbqkv[i * d:(i + 1) * d]
+            OT.layernorm_bwd(S["x_in"], lw["ln1"][0], da1, dx, accumulate=True, dgamma=slot(p + "self_attn_layer_norm.weight", d),
+                             dbeta=slot(p + "self_attn_layer_norm.bias", d))
+        # positions add: x0 = gelu(conv2) + pos
+        if want("embed_positions.weight"):
+            G["embed_positions.weight"] = z(T2 * d)
+            OT.colsum_(G["embed_positions.weight"], dx.view(B, T2 * d))             # sum over the batch, rows in order
+            G["embed_positions.weight"] = G["embed_positions.weight"].view(T2, d)
+        dxb = OT.add_cast(dx)
+        need_conv1 = want("conv1.weight") or want("conv1.bias") or want("input_features")
+        # conv2 (K 3, stride 2, pad 1) + GELU
+        dh2p = OT.act_bwd(dxb, saved["h2p"].view(M, d))
+        h1 = saved["h1"]
+        dwc2, dbc2 = slot("conv2.weight", d, 3 * d), slot("conv2.bias", d)
+        if dwc2 is not None or dbc2 is not None:
+            OT.gemm_tn_(dwc2 if dwc2 is not None else z(d, 3 * d), dh2p, OT.im2col_geo(h1, (3, 1), (2, 1), (1, 0), T2, 1), db=dbc2)
+        if need_conv1:
+            dcol = ops.gemm(dh2p, self._wT("c2w", w["c2w"])[:, :d])
+            dh1 = OT.col2im(dcol, (B, T, 1, d), (3, 1), (2, 1), (1, 0), T2, 1)
+            dh1p = OT.act_bwd(dh1.view(B * T, d), saved["h1p"].view(B * T, d))
+            dwc1, dbc1 = slot("conv1.weight", d, 3 * mel), slot("conv1.bias", d)
+            if dwc1 is not None or dbc1 is not None:
+                OT.gemm_tn_(dwc1 if dwc1 is not None else z(d, 3 * mel), dh1p, OT.im2col_geo(saved["fcl"].view(B, T, 1, mel), (3, 1), (1, 1), (1, 0), T, 1), db=dbc1)
+            if want("input_features"):
+                dcol1 = ops.gemm(dh1p, self._wT("c1w", w["c1w"])[:, :d])
+                dfe = OT.col2im(dcol1, (B, T, 1, mel), (3, 1), (1, 1), (1, 0), T, 1)
+                G["input_features"] = dfe.view(B, T, mel).permute(0, 2, 1).to(f32)
+        for n in ("conv1.weight", "conv2.weight"):                  # (d, k*Cin) k-major -> HF (d, Cin, k)
+            if G.get(n) is not None:
+                G[n] = G[n].view(d, 3, -1).permute(0, 2, 1)
+        return G
+
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # The Whisper branch of the reference (`src/utilities/model_utils.py:183`: `AutoModelForSpeechSeq2Seq.from_pretrained(...)` on a Whisper checkpoint, e.g.
@@ -171,7 +313,7 @@ def _stock_forward(self, why, input_features, attention_mask, kwargs):
     if why not in _stock_forward.said:
         _stock_forward.said.add(why)
         warnings.warn(f"huggingface_asr_amd: WhisperEncoder.forward runs transformers' own PyTorch implementation for this call ({why}); the HIP engine covers "
-                      "inference on GPU tensors returning last_hidden_state", stacklevel=3)
+                      "inference and training (dropout 0) on GPU tensors returning last_hidden_state", stacklevel=3)
     from transformers.models.whisper import modeling_whisper as MW
     return MW.WhisperEncoder._hfasr_reference_forward(self, input_features, attention_mask=attention_mask, **kwargs)
 
@@ -179,10 +321,45 @@ def _stock_forward(self, why, input_features, attention_mask, kwargs):
 _stock_forward.said = set()
 
 
+class _WhisperEncoderFn(torch.autograd.Function):
+    """Training / gradient-wanted calls: forward = `WhisperEncoderEngine.forward_train`, backward = `WhisperEncoderEngine.backward` (every pass on the HIP kernels).
+    Inputs: (enc, skip, input_features, *parameters in `enc.named_parameters()` order)."""
+
+    @staticmethod
+    def forward(ctx, enc, skip, input_features, *params):
+        eng = _engine_for(enc)
+        out, saved = eng.forward_train(input_features, skip)
+        ctx.eng, ctx.saved_fw = eng, saved
+        ctx.names = [n for n, _ in enc.named_parameters()]
+        ctx.in_dtype = input_features.dtype
+        ctx.dtypes = [p.dtype for p in params]
+        return out.to(enc.layer_norm.weight.dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        wanted = {n for n, need in zip(ctx.names, ctx.needs_input_grad[3:]) if need}
+        if ctx.needs_input_grad[2]:
+            wanted.add("input_features")
+        G = ctx.eng.backward(ctx.saved_fw, dout, lambda n: n in wanted)
+        ctx.saved_fw = None
+        gin = G.get("input_features")
+        out = [None, None, gin.to(ctx.in_dtype) if gin is not None else None]
+        for n, dt in zip(ctx.names, ctx.dtypes):
+            g = G.get(n)
+            out.append(g.to(dt).contiguous() if g is not None else None)
+        return tuple(out)
+
+
+def _encoder_train_forward(self, input_features):
+    """LayerDrop drawn here exactly as `WhisperEncoder.forward` draws it (one `torch.rand([])` per layer in training), then the HIP training forward"""
+    skip = [bool(self.training and torch.rand([]) < self.layerdrop) for _ in range(len(self.layers))]
+    return _WhisperEncoderFn.apply(self, skip, input_features, *[p for _, p in self.named_parameters()])
+
+
 def hip_whisper_encoder_forward(self, input_features, attention_mask=None, **kwargs):
-    """`transformers.models.whisper.modeling_whisper.WhisperEncoder.forward` on the HIP engine: inference (`eval()`, or no gradient wanted) on GPU tensors returning
-    `last_hidden_state`.  Every other call — training mode (dropout / LayerDrop / autograd through the encoder: `train_enc_dec_asr.py --do_train` on a Whisper checkpoint,
-    `recipes_v0.0.1/librispeech_whisper_ctc`), attention or hidden-state outputs, head masks, CPU tensors — is handed to transformers' own forward (`_stock_forward`)."""
+    """`transformers.models.whisper.modeling_whisper.WhisperEncoder.forward` on the HIP engine, on GPU tensors returning `last_hidden_state`: inference, and training /
+    autograd through the encoder (`train_enc_dec_asr.py --do_train` on a Whisper checkpoint, `recipes_v0.0.1/librispeech_whisper_ctc`) through `_WhisperEncoderFn`,
+    LayerDrop included.  Handed to transformers' own forward (`_stock_forward`): dropout > 0 in training, attention or hidden-state outputs, head masks, CPU tensors."""
     from transformers.modeling_outputs import BaseModelOutput
     cfg = self.config
     want = {k: kwargs.get(k) for k in ("output_attentions", "output_hidden_states", "head_mask")}
@@ -191,10 +368,10 @@ def hip_whisper_encoder_forward(self, input_features, attention_mask=None, **kwa
         return _stock_forward(self, "attentions / hidden states / head mask requested", input_features, attention_mask, kwargs)
     if not input_features.is_cuda:
         return _stock_forward(self, "CPU tensors", input_features, attention_mask, kwargs)
-    if self.training:
-        return _stock_forward(self, "training mode", input_features, attention_mask, kwargs)
-    if torch.is_grad_enabled() and (input_features.requires_grad or any(p.requires_grad for p in self.parameters())):
-        return _stock_forward(self, "a gradient through the encoder is wanted (wrap inference in torch.no_grad())", input_features, attention_mask, kwargs)
+    if self.training and any(float(getattr(cfg, n, 0.0) or 0.0) > 0.0 for n in ("dropout", "attention_dropout", "activation_dropout")):
+        return _stock_forward(self, "dropout > 0 in training: the library's dropout masks cannot match torch's", input_features, attention_mask, kwargs)
+    if self.training or (torch.is_grad_enabled() and (input_features.requires_grad or any(p.requires_grad for p in self.parameters()))):
+        return BaseModelOutput(last_hidden_state=_encoder_train_forward(self, input_features))
     out = _engine_for(self).forward(input_features=input_features)                       # (B, T/2, d) fp32; same length check / message as transformers
     return BaseModelOutput(last_hidden_state=out.to(self.layer_norm.weight.dtype))
 

@@ -197,6 +197,13 @@ int mi_attention_qkv_bwd_probs_f(const void* q, long ldq, const void* k, long ld
                                   void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
                                   void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
                                   int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, int flags, mi_stream_t stream);
+/* Attention backward for the fused (B*T, 3d) projection with no (H, B, T, T) tensor in HBM (attn_bwd_fused.hip): no relative positions, no dropout, hd 64 / 128.
+ * P and dS are recomputed from q, k and the forward's lse (mi_attention_qkv_lse_bf16); dq / dk / dv are row views of one (B*T, ldg) bf16 buffer, every row written.
+ * workspace: >= B*T*H*4 bytes.  No atomics: the result is bitwise reproducible. */
+int mi_attention_qkv_bwd_fused(const void* q, const void* k, const void* v, long ldqkv, const int* lengths,
+                               const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
+                               void* dq, void* dk, void* dv, long ldg, void* workspace, size_t ws_bytes,
+                               int B, int T, int H, int hd, float scale, mi_stream_t stream);
 /* the two entries above for Tq != Tk and separate q / k / v operands, no relative positions: the GPT-2 decoder's causal self-attention and its cross-attention over the
  * encoder frames in training (multi_head_gpt2.py:80-170).  lse (B, H, Tq); prob / ds (H, B, Tq, ldsr) bf16, ldsr % 32 == 0, ldsr >= Tk rounded up to 32; dq = dS K. */
 int mi_attention_x_lse_bf16(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const int* lengths, void* out, long ldo, float* lse,
