@@ -314,6 +314,21 @@ def spec_mask_bwd_(dx, time_mask, dembed, feat_mask, T):
     _lib.check(_L().mi_spec_mask_bwd(dx.data_ptr(), dx.stride(0), _p(time_mask), _p(dembed), _p(feat_mask), T, M, N, ws, _stream()), "mi_spec_mask_bwd")
 
 
+def mask_noise_(x, time_mask, std, seed, stream_id):
+    """rows of x (M, N) f32 whose time_mask (M) uint8 entry is set -> N(0, std) noise, counter-based like the dropout masks (BEST-RQ input masking)"""
+    M, N = x.shape
+    _lib.check(_L().mi_mask_noise_f32(x.data_ptr(), x.stride(0), time_mask.data_ptr(), M, N, float(std), int(seed) & 0xFFFFFFFF, int(stream_id) & 0xFFFFFFFF,
+                                      _stream()), "mi_mask_noise_f32")
+
+
+def subsampled_lengths(lengths, K, stride, pad, tmax, layers=2):
+    """lengths (B) int32 after `layers` K / stride convolutions -> (inner: with padding `pad`, capped at tmax; outer: without padding), int32, one launch"""
+    inner, outer = torch.empty_like(lengths), torch.empty_like(lengths)
+    _lib.check(_L().mi_subsampled_lengths_i32(lengths.data_ptr(), lengths.numel(), int(K), int(stride), int(pad), int(layers), int(tmax), inner.data_ptr(),
+                                              outer.data_ptr(), _stream()), "mi_subsampled_lengths_i32")
+    return inner, outer
+
+
 def bgemm(A, a_str, B, b_str, C, c_str, Z1, Z2, M, N, K, *, alpha=1.0, accumulate=False, band=None, m_valid=None):
     """C[z1,z2][m][n] = alpha * sum_k A[..][m][k] B[..][n][k] (+C). a_str = (z1, z2, m, k) element strides, b_str = (z1, z2, n, k),
     c_str = (z1, z2, m); A/B bf16 storage, C f32|bf16 with unit column stride.

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import math
 import os
+from collections import namedtuple
 from dataclasses import dataclass
 from functools import partial
 from typing import Callable, NamedTuple
@@ -94,6 +95,7 @@ class ParamStore:
         self.map = {n: Ref(*r) for n, r in (ref_map or {}).items()}
         self._piece = {key: (name, unpack) for name, r in self.map.items() for key, unpack in r.pieces}
         self.absent = set()             # optional reference keys the last load lacked
+        self.fresh = False              # see zero_grad
 
     def set_frozen(self, names):
         """Parameters that must not change: no weight decay on them (the mask AdamW reads), and their gradient spans — merged into as few
@@ -164,7 +166,7 @@ class ParamStore:
 
     def zero_grad(self):
         self.flat_g.zero_()
-        self.fresh = True               # every gradient is exactly zero: the next backward's grouped weight-gradient launches may WRITE their targets (EncoderCTCTrainer.dw_overwrite)
+        self.fresh = True               # every gradient is exactly zero: the next backward's grouped weight-gradient launches may WRITE their targets (TnBatch.overwrite)
 
     # ------------------------------------------------------------------ reference names
     def _flat(self, which):
@@ -421,6 +423,12 @@ def _u01(seed: int, stream: int) -> float:
 
 
 # ====================================================================================================== trainer
+# what the stages of one `EncoderCTCTrainer.forward_backward` call share besides the configuration (built by `_step`): batch size, frames after each
+# sub-sampling conv (T1, T2), frequency bins after each (F1, F2), M = B * T2 rows, the dropout probabilities in force, the sub-sampled lengths
+# (inner: the encoder's mask, outer: the CTC input lengths), the position table, the layers LayerDrop skips, training mode
+_Step = namedtuple("_Step", "B T1 T2 F1 F2 M pd inner outer pos skip train")
+
+
 class StoreTrainer:
     """What the trainers share: parameters in ParamStores, each holding the reference keys that start with its prefix (`_named_stores()`:
     [(prefix, store), ...], the first match wins), gradient all-reduces in `syncs()`, one optimizer step over all of them."""
@@ -528,10 +536,6 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         self.csgu_lin = bool(c.get("csgu_use_linear_after_conv", False))
         # fused CSGU kernels cover the reference recipes' form (identity activation, no Linear); anything else runs split: conv -> [Linear] -> act * gate
         self.csgu_split = self.csgu_lin or self.csgu_act != 0
-        self.dual_ln = True                       # the two branch norms' backward in one pass (tools/train_bench.py --no-dual-ln measures the two-pass form beside it)
-        self.dw_overwrite = os.environ.get("HFASR_DW_OVERWRITE", "1") != "0"      # see _forward_backward (HFASR_DW_OVERWRITE=0 / tools/train_bench.py --no-dw-overwrite: always accumulate)
-        self.ctc_from_bwd = True                  # the CTC loss out of the backward's own alpha recursion (tools/train_bench.py --no-ctc-from-bwd: forward loss kernel + backward)
-        self.walk_qb = True                       # q + u / q + v of the attention backward from the fused walk's prologue (--no-walk-qb: the pass of their own)
         self.sparse_attn_bwd = os.environ.get("HFASR_ATTN_BWD_SPARSE", "1") != "0"       # round 5: the fused walk does not write the zeros nobody reads (ops_train.attn_bwd_probs)
         self.frozen = set()
         self.layerdrop = float(c.get("layerdrop", 0.0) or 0.0)      # tf:models/wav2vec2_conformer/modeling_wav2vec2_conformer.py:686-690
@@ -563,6 +567,25 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         self.ctx_mode = context_mode(c)                              # context-aware Conv2d front end (extractors.py:23-65): 0 plain, 1 gated, 2 gated_shared
         self._encln_names = ["enc_ln_g", "enc_ln_b"] + (["mix_w"] if self.mix else [])
         self._head_names = self._encln_names + (["head_w", "head_b"] if self.head else [])
+        self.d, self.H, self.I, self.L, self.V1 = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"], L, c["vocab_size"] + 1
+        self.ptype = c.get("position_embeddings_type", "relative")
+        self.macaron = c.get("use_macaron_ff", True)
+        self.eps_e = float(c.get("layer_norm_eps", 1e-5))
+        kc = c.get("csgu_kernel_size", 31)
+        # e_branchformer.py:153-160 hands (K-1)//2 to CausalConv1d's dilation slot: the causal CSGU conv is dilated by 15 with a left pad of (K-1)*15
+        self.cs_dil = (kc - 1) // 2 if self.causal else 1
+        self.cs_pad = (kc - 1) * self.cs_dil if self.causal else (kc - 1) // 2
+        # front end: two K x K / stride / pad Conv2d (CausalConv2d: all of the padding on the top / left, streaming_modules.py:31-55); gated: the gate conv's geometry
+        self.C1, self.C2 = c["conv_dim"]
+        self.K, self.stride, self.pad = c["conv_kernel"][0], c["conv_stride"][0], c["conv_padding"][0]
+        self.padl = 2 * self.pad if self.causal else self.pad
+        if self.ctx_mode:
+            self.share = GATE_SHARE if self.ctx_mode == 2 else 1
+            g = gate_geometry(self.K, self.stride, self.pad, self.ctx_mode)
+            self.gate_geo = g[0:2], g[2:4], g[4:6]            # (K, stride, pad) pairs (time, frequency) of the gate convs
+        self._e16, self._e32 = partial(torch.empty, device=self.device, dtype=BF16), partial(torch.empty, device=self.device, dtype=F32)
+        self._lnred = T.LnReduceBatch(self.device)          # the (dgamma | dbeta) and tap-gradient reductions of the backward: one launch per flush (_lng; the depthwise convs' and position biases' sums)
+        self._tnb = T.TnBatch()                             # the backward's weight-gradient GEMMs: grouped launches (_range_done)
 
     # ------------------------------------------------------------------ weights in / out (StoreTrainer / ZeroCopyTrainer: the reference's names)
     def _named_stores(self):
@@ -588,44 +611,34 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         then waits, with any earlier ones, for the flush that does run; the backward's last range is `final`."""
         pending = self._ranges_waiting
         pending.append((lo, hi))
-        tnb = getattr(self, "_tnb", None)
-        if tnb is None or tnb.flush(final=final):
-            if getattr(self, "_lnred", None) is not None:       # the LayerNorm reductions ride the same cadence (a full batch flushes itself): fewer, fuller launches
-                self._lnred.flush()
+        if self._tnb.flush(final=final):
+            self._lnred.flush()             # the LayerNorm reductions ride the same cadence (a full batch flushes itself): fewer, fuller launches
             for r in pending:
                 self.sync.launch(*r)
             pending.clear()
-
-    def _dwred(self):
-        """the batch the depthwise-conv backward passes defer their tap-gradient reductions to (the LayerNorm one: flushed in _range_done, before a range is handed on)"""
-        if getattr(self, "_lnred", None) is None:
-            self._lnred = T.LnReduceBatch(self.device)
-        return self._lnred
 
     def _lng(self, gname, bname):
         """gradient targets of a LayerNorm's affine pair: none when both are frozen (the cross-row reduction is then skipped)"""
         if gname in self.frozen and bname in self.frozen:
             return dict(dgamma=None, dbeta=None)
-        if getattr(self, "_lnred", None) is None:
-            self._lnred = T.LnReduceBatch(self.device)        # the (dgamma | dbeta) reductions of a layer's LayerNorms: one launch per flush, not one per LayerNorm
         return dict(dgamma=self.store.g(gname), dbeta=self.store.g(bname), defer=self._lnred)
 
+    def _gl(self, name, sl=None):
+        """gradient of a linear's weight / bias (or a slice of it), None when frozen"""
+        return None if name in self.frozen else (self.store.g(name) if sl is None else self.store.g(name)[sl])
+
     # ------------------------------------------------------------------ tables
+    def _conv_out(self, n):
+        """frames / bins after one sub-sampling conv"""
+        return (n + 2 * self.pad - self.K) // self.stride + 1
+
     def out_frames(self, Tn):
-        c = self.cfg
-        k, s, p = c["conv_kernel"][0], c["conv_stride"][0], c["conv_padding"][0]
-        out = []
-        for _ in range(2):
-            Tn = (Tn + 2 * p - k) // s + 1
-            out.append(Tn)
-        return out
+        return [self._conv_out(Tn), self._conv_out(self._conv_out(Tn))]
 
     def _pos_table(self, T2):
-        c = self.cfg
-        ptype = c.get("position_embeddings_type", "relative")
+        ptype, d, H = self.ptype, self.d, self.H
         key = (ptype, T2)
         if key not in self._pos:
-            d, H = c["hidden_size"], c["num_attention_heads"]
             if ptype == "relative":
                 pos = torch.arange(T2 - 1, -T2, -1, dtype=F32)[:, None]
                 div = torch.exp(torch.arange(0, d, 2, dtype=torch.int64).float() * -(math.log(10000.0) / d))
@@ -635,7 +648,7 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
                 self._pos[key] = (t,)
             elif ptype == "rotary":
                 hd = d // H
-                inv = 1.0 / (c.get("rotary_embedding_base", 10000) ** (torch.arange(0, hd, 2, dtype=torch.int64).float() / hd))
+                inv = 1.0 / (self.cfg.get("rotary_embedding_base", 10000) ** (torch.arange(0, hd, 2, dtype=torch.int64).float() / hd))
                 fr = torch.einsum("i,j->ij", torch.arange(T2).float(), inv)
                 emb = torch.cat((fr, fr), dim=-1)
                 self._pos[key] = (emb.cos().contiguous().to(self.device), emb.sin().contiguous().to(self.device), (-emb.sin()).contiguous().to(self.device))
@@ -660,72 +673,84 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         `skip_layers`: LayerDrop decisions for this step (iterable of layer indices that are skipped: the layer is the identity and its
         parameters get no gradient).  None = draw them as the reference does — one uniform number per layer and step, layer skipped when it
         is below `config.layerdrop` (every rank draws its own, from its dropout seed) — in training mode; nothing is skipped in eval."""
-        c, st = self.cfg, self.store
-        if getattr(self, "_lnred", None) is not None:
-            self._lnred.items, self._lnred.keep = [], []              # a step that raised part-way leaves deferred LayerNorm reductions behind: they must not land in this step's gradients
-        if getattr(self, "_tnb", None) is None:
-            self._tnb = T.TnBatch()
+        self._lnred.items, self._lnred.keep = [], []      # a step that raised part-way leaves deferred LayerNorm reductions behind: they must not land in this step's gradients
         self._tnb.items = []
         # first backward after zero_grad: every layer matrix is the target of exactly one weight-gradient problem, so the grouped launches write dW / db instead of adding
         # into the zeros (their epilogue otherwise ends with a dependent read of the output tile: 516 MB per step at the base size); any later backward accumulates
-        self._tnb.overwrite = bool(backward and self.dw_overwrite and getattr(self.store, "fresh", False))
+        self._tnb.overwrite = bool(backward and self.store.fresh)
         if backward:
             self.store.fresh = False
         self._ranges_waiting = []
-        P, G, W, WT = st.p, st.g, st.bf, st.bfT
-        GL = lambda n, sl=None: None if n in self.frozen else (st.g(n) if sl is None else st.g(n)[sl])      # gradient of a linear's weight / bias, None when frozen
-        dev = self.device
         feats = feats.to(F32).contiguous()
+        sp = self._step(feats, feat_lengths, backward or train_mode, step_index, skip_layers)
+        x, Sf = self._front_fwd(feats, sp, noise_mask)
+        hs = [] if self.mix else None       # HF's `hidden_states` tuple: the INPUT of every layer, then the final LayerNorm's output (tf:679-680,714-715)
+        saved = []
+        for l in range(self.L):
+            if hs is not None:
+                hs.append(x)
+            if l in sp.skip:                # LayerDrop: identity, nothing saved, no gradient
+                saved.append(None)
+                continue
+            x, S = self._layer_fwd(x, l, sp)
+            saved.append(S)
+        Sh = self._head_fwd(x, hs, sp, labels, backward, extra_hidden_grad)
+        out = dict(loss=Sh["loss"], logits=Sh["logits"], outer_len=sp.outer, inner_len=sp.inner,
+                   last_hidden=Sh["last_hidden"].view(sp.B, sp.T2, self.d) if keep_hidden or extra_hidden_grad or not self.head else None)
+        if not backward:
+            return out
+        dx, dmix = self._head_bwd(Sh, sp, labels, loss_scale, extra_hidden_grad, out)
+        for l in range(self.L - 1, -1, -1):
+            if saved[l] is not None:        # (a dropped layer: dx passes through, its gradient range stays zero — still reduced: other ranks may have run it)
+                dx = self._layer_bwd(dx, saved[l], l, sp)
+            if dmix is not None:            # layer mixing: hidden_states[l] is this layer's input
+                T.axpy_dev_(dx, dmix, Sh["sw"][l:l + 1])
+            self._range_done(*self.store.range_of(self._layer_names[l]))
+        self._front_bwd(dx, feats, Sf, sp, noise_mask)
+        return out
+
+    def _step(self, feats, feat_lengths, train, step_index, skip_layers):
+        """the call's `_Step` record; advances the dropout step counter and draws the LayerDrop decisions"""
         B, Tn, Fq = feats.shape
-        d, H, I, L, V1 = c["hidden_size"], c["num_attention_heads"], c["intermediate_size"], c["num_hidden_layers"], c["vocab_size"] + 1
-        C1, C2 = c["conv_dim"]
-        K, s_, pad = c["conv_kernel"][0], c["conv_stride"][0], c["conv_padding"][0]
         T1, T2 = self.out_frames(Tn)
-        F1 = (Fq + 2 * pad - K) // s_ + 1
-        F2 = (F1 + 2 * pad - K) // s_ + 1
-        M, hd = B * T2, d // H
-        ptype = c.get("position_embeddings_type", "relative")
-        macaron = c.get("use_macaron_ff", True)
-        eps_e = float(c.get("layer_norm_eps", 1e-5))
-        kc = c.get("csgu_kernel_size", 31)
-        scale = 1.0 / math.sqrt(hd)
+        F1 = self._conv_out(Fq)
+        F2 = self._conv_out(F1)
         if feat_lengths is not None:
-            feat_lengths = feat_lengths.to(device=dev, dtype=torch.int32).contiguous()
-            inner, outer = self._lengths(feat_lengths, T2)
+            feat_lengths = feat_lengths.to(device=self.device, dtype=torch.int32).contiguous()
+            inner, outer = T.subsampled_lengths(feat_lengths, self.K, self.stride, self.pad, T2)
         else:
             inner = None
-            outer = torch.full((B,), self._outer_len(Tn), dtype=torch.int32, device=dev)
-        e32 = lambda *sh: torch.empty(sh, device=dev, dtype=F32)
-        e16 = lambda *sh: torch.empty(sh, device=dev, dtype=BF16)
-        LN = ops.layernorm_chain
-        pd, seed = (self.pdrop if (backward or train_mode) else dict.fromkeys(self.pdrop, 0.0)), self.seed
+            outer = torch.full((B,), self._outer_len(Tn), dtype=torch.int32, device=self.device)
+        pd = self.pdrop if train else dict.fromkeys(self.pdrop, 0.0)
         self._step_idx = self.train_steps_seen if step_index is None else int(step_index)
-        if backward or train_mode:
+        if train:
             self.train_steps_seen += 1
+        if skip_layers is None:
+            skip_layers = [l for l in range(self.L) if _u01(self.seed, self._sid(l, 15)) < self.layerdrop] if (self.layerdrop > 0 and train) else []
+        skip = set(int(l) for l in skip_layers)
+        self.last_skipped = sorted(skip)
+        return _Step(B, T1, T2, F1, F2, B * T2, pd, inner, outer, self._pos_table(T2), skip, train)
 
-        # ---------------- front end
-        causal = self.causal
-        padl = 2 * pad if causal else pad                  # CausalConv2d: all of the padding on the top / left (streaming_modules.py:31-55)
-        # e_branchformer.py:153-160 hands (K-1)//2 to CausalConv1d's dilation slot: the causal CSGU conv is dilated by 15 with a left pad of (K-1)*15
-        cs_dil = (kc - 1) // 2 if causal else 1
-        cs_pad = (kc - 1) * cs_dil if causal else (kc - 1) // 2
-        cm = self.ctx_mode
+    def _front_fwd(self, feats, sp, noise_mask):
+        """Conv2d sub-sampling, feature projection, input masking and dropout -> (x (M, d) f32, what the backward reads)"""
+        P, W, pd, seed, L = self.store.p, self.store.bf, sp.pd, self.seed, self.L
+        B, T1, T2, F1, F2, M = sp.B, sp.T1, sp.T2, sp.F1, sp.F2, sp.M
+        K, s_, pad, C1, C2, cm = self.K, self.stride, self.pad, self.C1, self.C2, self.ctx_mode
+        pre2 = z1 = g1 = z2 = g2 = None
         if cm == 0:
-            act1 = ops.conv2d_first_gelu(feats, P("conv1_w"), P("conv1_b"), stride=s_, pad=pad, causal=causal)
-            pre2 = ops.conv2d_cl(act1, W("conv2_w"), P("conv2_b"), K=K, stride=s_, pad=pad, causal=causal, act="none").view(B * T2 * F2, C2)
+            act1 = ops.conv2d_first_gelu(feats, P("conv1_w"), P("conv1_b"), stride=s_, pad=pad, causal=self.causal)
+            pre2 = ops.conv2d_cl(act1, W("conv2_w"), P("conv2_b"), K=K, stride=s_, pad=pad, causal=self.causal, act="none").view(B * T2 * F2, C2)
             act2 = T.act_fwd(pre2).view(M, F2 * C2)
         else:
             # GatedConv2d / GatedConv2dShared (extractors.py:23-54): GELU(conv(x) * sigmoid(gate(x))), the shared gate being one row per four conv rows from a
             # (4K, K) / stride (4s, s) / padding (4p, p) conv.  Training keeps the raw conv / gate outputs (bf16) for the backward: un-fused passes.
-            share = GATE_SHARE if cm == 2 else 1
-            gkh, gkw, gst, gsf, gpt, gpf = gate_geometry(K, s_, pad, cm)
-            gK, gS, gP, cK, cS, cP = (gkh, gkw), (gst, gsf), (gpt, gpf), (K, K), (s_, s_), (pad, pad)
+            share, (gK, gS, gP) = self.share, self.gate_geo
             if cm == 2:
-                for Tc, Tg in ((T1, (Tn + 2 * gpt - gkh) // gst + 1), (T2, (T1 + 2 * gpt - gkh) // gst + 1)):
+                for Tc, Tg in ((T1, (feats.shape[1] + 2 * gP[0] - gK[0]) // gS[0] + 1), (T2, (T1 + 2 * gP[0] - gK[0]) // gS[0] + 1)):
                     if Tc % share or Tc // share != Tg:
                         raise RuntimeError(f"gated_shared front end: conv time axis {Tc} vs gate {Tg}: the reference's view(B, C, -1, {share}, F) * gate needs "
                                            f"{Tc} % {share} == 0 and {Tc} // {share} == {Tg} (extractors.py:49-54)")
-            z1 = ops.conv2d_first_geo(feats, P("conv1_w"), P("conv1_b"), K=cK, stride=cS, pad=cP, act="none")
+            z1 = ops.conv2d_first_geo(feats, P("conv1_w"), P("conv1_b"), K=(K, K), stride=(s_, s_), pad=(pad, pad), act="none")
             g1 = ops.conv2d_first_geo(feats, P("gate1_w"), P("gate1_b"), K=gK, stride=gS, pad=gP, act="none")
             act1 = ops.gated_act(z1, g1, B, T1, F1, C1, share).view(B, T1, F1, C1)
             if cm == 1:
@@ -736,280 +761,269 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
                 g2 = ops.conv2d_cl_geo(act1, W("gate2_w"), P("gate2_b"), K=gK, stride=gS, pad=gP, act="none").view(-1, C2)
             act2 = ops.gated_act(z2, g2, B, T2, F2, C2, share).view(M, F2 * C2)
         feo = ops.gemm(act2, W("feout_w"), P("feout_b"), out_dtype=F32)
-        a_fp = e16(M, d)
-        LN(feo, lna=(P("fp_ln_g"), P("fp_ln_b")), eps2=eps_e, outa=a_fp)
+        a_fp = self._e16(M, self.d)
+        ops.layernorm_chain(feo, lna=(P("fp_ln_g"), P("fp_ln_b")), eps2=self.eps_e, outa=a_fp)
         x = ops.gemm(a_fp, W("fp_w"), P("fp_b"), out_dtype=F32)
         if pd["fp"] > 0:
             T.dropout_(x, pd["fp"], seed, self._sid(L, 0))
         tmask = fmask = None
         if noise_mask is not None:
-            from . import _lib
-            nm, nstd = noise_mask
-            _lib.check(_lib.lib().mi_mask_noise_f32(x.data_ptr(), x.stride(0), nm.data_ptr(), M, d, float(nstd), seed, self._sid(L, 3),
-                                                    torch.cuda.current_stream().cuda_stream), "mi_mask_noise_f32")
-        elif self.specaug and (backward or train_mode):
-            tmask, fmask = self._spec_masks(B, T2, d, inner)
+            T.mask_noise_(x, noise_mask[0], noise_mask[1], seed, self._sid(L, 3))
+        elif self.specaug and sp.train:
+            tmask, fmask = self._spec_masks(B, T2, self.d, sp.inner)
             T.spec_mask_apply_(x, tmask, P("masked_spec_embed"), fmask, T2)
-        if inner is not None:
-            T.mask_rows_(x, inner, T2)
+        if sp.inner is not None:
+            T.mask_rows_(x, sp.inner, T2)
         if pd["hidden"] > 0:
             T.dropout_(x, pd["hidden"], seed, self._sid(L, 1))
-        pos = self._pos_table(T2)
-        saved = []
-        if skip_layers is None:
-            skip_layers = [l for l in range(L) if _u01(seed, self._sid(l, 15)) < self.layerdrop] if (self.layerdrop > 0 and (backward or train_mode)) else []
-        skip = set(int(l) for l in skip_layers)
-        self.last_skipped = sorted(skip)
-        # ---------------- layers
-        def layer_fwd(x, l):
-            p, sl = f"l{l}.", l + int(l >= L)          # sl: dropout-stream layer id (L itself names the global sites; the additional layer takes L + 1)
-            S = {"x_in": x}
-            if macaron:
-                x, S["ff1"] = self._ffn_fwd(x, p + "ff1", LN, e16, pd, sl, (0, 1))
-            S["x1"] = x
-            a1, a2 = e16(M, d), e16(M, d)
-            LN(x, lna=(P(p + "att_ln_g"), P(p + "att_ln_b")), outa=a1, lnb=(P(p + "mlp_ln_g"), P(p + "mlp_ln_b")), outb=a2)
-            cat = e16(M, 2 * d)
-            # global branch
-            qkv = e16(M, 3 * d)
-            if ptype == "rotary":
-                a1r = ops.rotary(a1, pos[0].reshape(-1), pos[1].reshape(-1), T2, H)
-                ops.gemm(a1r, W(p + "att_wqkv")[:2 * d], P(p + "att_bqkv")[:2 * d], out=qkv[:, :2 * d])
-                ops.gemm(a1, W(p + "att_wqkv")[2 * d:], P(p + "att_bqkv")[2 * d:], out=qkv[:, 2 * d:])
-                S["a1r"] = a1r
-            else:
-                ops.gemm(a1, W(p + "att_wqkv"), P(p + "att_bqkv"), out=qkv)
-            posp = None
-            if ptype == "relative":
-                posp = ops.gemm(pos[0], W(p + "att_wpos"))
-            ctx = self._attention_fwd(qkv, posp, P(p + "att_u") if posp is not None else None, P(p + "att_v") if posp is not None else None,
-                                      inner, B, T2, H, S, (pd["att"], seed, self._sid(sl, 2)) if pd["att"] > 0 else None)
-            if pd["att"] > 0:       # linear_out + self_attn_dropout (e_branchformer.py:288): the dropout rides the GEMM's epilogue
-                T.gemm_dropout(ctx, W(p + "att_wo"), P(p + "att_bo"), pd["att"], seed, self._sid(sl, 3), out=cat[:, :d])
-            else:
-                ops.gemm(ctx, W(p + "att_wo"), P(p + "att_bo"), out=cat[:, :d])
-            # local branch (cgMLP)
-            hp, h = T.gemm_act_fwd(a2, W(p + "mlp_w1"), P(p + "mlp_b1"))
-            stats = ops.row_stats(h[:, I // 2:])
-            cv = lin = None
-            if self.csgu_split:                              # e_branchformer.py:196-201: conv -> [Linear] -> act -> gate
-                cv = lin = ops.csgu_conv(h, stats, P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), B, T2, pad_left=cs_pad, dilation=cs_dil)
-                if self.csgu_lin:
-                    lin = ops.gemm(cv, W(p + "csgu_lin_w"), P(p + "csgu_lin_b"))
-                sg = ops.gate_act_mul(h[:, :I // 2], lin, self.csgu_act)
-            else:
-                sg = ops.csgu(h, P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), B, T2, pad_left=cs_pad, dilation=cs_dil, stats=stats)
-            if pd["csgu"] > 0:
-                T.dropout_(sg, pd["csgu"], seed, self._sid(sl, 4))
-            ops.gemm(sg, W(p + "mlp_w2"), P(p + "mlp_b2"), out=cat[:, d:])
-            # merge
-            m2 = ops.dwconv_residual(cat, P(p + "mrg_dw_w"), P(p + "mrg_dw_b"), B, T2)
-            if pd["att"] > 0:       # the layer's `final_dropout` module takes config.attention_dropout (e_branchformer.py:229,246)
-                x2 = T.gemm_dropout(m2, W(p + "mrg_w"), P(p + "mrg_b"), pd["att"], seed, self._sid(sl, 5), resid=x, alpha=1.0)
-            else:
-                x2 = ops.gemm(m2, W(p + "mrg_w"), P(p + "mrg_b"), out_dtype=F32, resid=x, alpha=1.0)
-            S.update(a1=a1, a2=a2, qkv=qkv, posp=posp, ctx=ctx, hp=hp, h=h, stats=stats, sg=sg, cat=cat, m2=m2, x2=x2, cv=cv, lin=lin)
-            x = x2
-            if macaron:
-                x, S["ff2"] = self._ffn_fwd(x, p + "ff2", LN, e16, pd, sl, (6, 7))
-            S["x3"] = x
-            xo = e32(M, d)
-            LN(x, ln1=(P(p + "fin_ln_g"), P(p + "fin_ln_b")), store_y=xo)
-            x = xo
-            return x, S
+        return x, dict(act1=act1, pre2=pre2, act2=act2, z1=z1, g1=g1, z2=z2, g2=g2, feo=feo, a_fp=a_fp, tmask=tmask, fmask=fmask)
 
-        hs = [] if self.mix else None       # HF's `hidden_states` tuple: the INPUT of every layer, then the final LayerNorm's output (tf:679-680,714-715)
-        for l in range(L):
-            if hs is not None:
-                hs.append(x)
-            if l in skip:                   # LayerDrop: identity, nothing saved, no gradient
-                saved.append(None)
-                continue
-            x, S = layer_fwd(x, l)
-            saved.append(S)
-        # ---------------- head + CTC
-        hid = e16(M, d)
-        last_hidden = e32(M, d)
-        LN(x, lna=(P("enc_ln_g"), P("enc_ln_b")), eps2=eps_e, outa=hid, outa32=last_hidden)
-        sw = mixed = S_extra = None
+    def _layer_fwd(self, x, l, sp):
+        """one E-Branchformer layer (l = num_hidden_layers: the fine-tuning head's additional layer) -> (output, what its backward reads)"""
+        P, W, pd, seed, pos = self.store.p, self.store.bf, sp.pd, self.seed, sp.pos
+        B, T2, M, d, H, I = sp.B, sp.T2, sp.M, self.d, self.H, self.I
+        p, sl = f"l{l}.", l + int(l >= self.L)          # sl: dropout-stream layer id (L itself names the global sites; the additional layer takes L + 1)
+        S = {"x_in": x}
+        if self.macaron:
+            x, S["ff1"] = self._ffn_fwd(x, p + "ff1", pd, sl, (0, 1))
+        S["x1"] = x
+        a1, a2 = self._e16(M, d), self._e16(M, d)
+        ops.layernorm_chain(x, lna=(P(p + "att_ln_g"), P(p + "att_ln_b")), outa=a1, lnb=(P(p + "mlp_ln_g"), P(p + "mlp_ln_b")), outb=a2)
+        cat = self._e16(M, 2 * d)
+        # global branch
+        qkv = self._e16(M, 3 * d)
+        if self.ptype == "rotary":
+            a1r = ops.rotary(a1, pos[0].reshape(-1), pos[1].reshape(-1), T2, H)
+            ops.gemm(a1r, W(p + "att_wqkv")[:2 * d], P(p + "att_bqkv")[:2 * d], out=qkv[:, :2 * d])
+            ops.gemm(a1, W(p + "att_wqkv")[2 * d:], P(p + "att_bqkv")[2 * d:], out=qkv[:, 2 * d:])
+            S["a1r"] = a1r
+        else:
+            ops.gemm(a1, W(p + "att_wqkv"), P(p + "att_bqkv"), out=qkv)
+        posp = None
+        if self.ptype == "relative":
+            posp = ops.gemm(pos[0], W(p + "att_wpos"))
+        ctx = self._attention_fwd(qkv, posp, P(p + "att_u") if posp is not None else None, P(p + "att_v") if posp is not None else None,
+                                  sp.inner, B, T2, H, S, (pd["att"], seed, self._sid(sl, 2)) if pd["att"] > 0 else None)
+        if pd["att"] > 0:       # linear_out + self_attn_dropout (e_branchformer.py:288): the dropout rides the GEMM's epilogue
+            T.gemm_dropout(ctx, W(p + "att_wo"), P(p + "att_bo"), pd["att"], seed, self._sid(sl, 3), out=cat[:, :d])
+        else:
+            ops.gemm(ctx, W(p + "att_wo"), P(p + "att_bo"), out=cat[:, :d])
+        # local branch (cgMLP)
+        hp, h = T.gemm_act_fwd(a2, W(p + "mlp_w1"), P(p + "mlp_b1"))
+        stats = ops.row_stats(h[:, I // 2:])
+        cv = lin = None
+        if self.csgu_split:                              # e_branchformer.py:196-201: conv -> [Linear] -> act -> gate
+            cv = lin = ops.csgu_conv(h, stats, P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), B, T2, pad_left=self.cs_pad,
+                                     dilation=self.cs_dil)
+            if self.csgu_lin:
+                lin = ops.gemm(cv, W(p + "csgu_lin_w"), P(p + "csgu_lin_b"))
+            sg = ops.gate_act_mul(h[:, :I // 2], lin, self.csgu_act)
+        else:
+            sg = ops.csgu(h, P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), B, T2, pad_left=self.cs_pad, dilation=self.cs_dil, stats=stats)
+        if pd["csgu"] > 0:
+            T.dropout_(sg, pd["csgu"], seed, self._sid(sl, 4))
+        ops.gemm(sg, W(p + "mlp_w2"), P(p + "mlp_b2"), out=cat[:, d:])
+        # merge
+        m2 = ops.dwconv_residual(cat, P(p + "mrg_dw_w"), P(p + "mrg_dw_b"), B, T2)
+        if pd["att"] > 0:       # the layer's `final_dropout` module takes config.attention_dropout (e_branchformer.py:229,246)
+            x2 = T.gemm_dropout(m2, W(p + "mrg_w"), P(p + "mrg_b"), pd["att"], seed, self._sid(sl, 5), resid=x, alpha=1.0)
+        else:
+            x2 = ops.gemm(m2, W(p + "mrg_w"), P(p + "mrg_b"), out_dtype=F32, resid=x, alpha=1.0)
+        S.update(a1=a1, a2=a2, qkv=qkv, posp=posp, ctx=ctx, hp=hp, h=h, stats=stats, sg=sg, cat=cat, m2=m2, x2=x2, cv=cv, lin=lin)
+        x = x2
+        if self.macaron:
+            x, S["ff2"] = self._ffn_fwd(x, p + "ff2", pd, sl, (6, 7))
+        S["x3"] = x
+        xo = self._e32(M, d)
+        ops.layernorm_chain(x, ln1=(P(p + "fin_ln_g"), P(p + "fin_ln_b")), store_y=xo)
+        return xo, S
+
+    def _head_fwd(self, x, hs, sp, labels, backward, extra_hidden_grad):
+        """encoder LayerNorm, [layer mixing, additional layer], CTC head; the CTC loss here only when no backward pass computes it (other reductions, eval)"""
+        P, W, pd, M, d = self.store.p, self.store.bf, sp.pd, sp.M, self.d
+        hid, last_hidden = self._e16(M, d), self._e32(M, d)
+        ops.layernorm_chain(x, lna=(P("enc_ln_g"), P("enc_ln_b")), eps2=self.eps_e, outa=hid, outa32=last_hidden)
+        S = dict(x=x, last_hidden=last_hidden, hs=hs, sw=None, mixed=None, S_extra=None, loss=None, logits=None, lse=None, nll=None)
         if self.mix or self.extra:
             if extra_hidden_grad is not None:
                 raise NotImplementedError("layer mixing / additional layer: CTC fine-tuning head only (no attention decoder on top)")
             top = last_hidden
             if self.mix:            # bestrq.py:239-245 — the weights never leave the device
                 hs.append(last_hidden)
-                sw = T.softmax_vec(P("mix_w"))
-                mixed = e32(M, d)
+                S["sw"] = sw = T.softmax_vec(P("mix_w"))
+                S["mixed"] = top = self._e32(M, d)
                 for i, h in enumerate(hs):
-                    T.axpy_dev_(mixed, h, sw[i:i + 1], overwrite=(i == 0))
-                top = mixed
+                    T.axpy_dev_(top, h, sw[i:i + 1], overwrite=(i == 0))
             if self.extra:          # bestrq.py:247-274: padded frames zeroed, then one more layer with the encoder's mask and position table; no LayerNorm after it
-                xin = top if top is mixed else top.clone()
-                if inner is not None:
-                    T.mask_rows_(xin, inner, T2)
-                top, S_extra = layer_fwd(xin, L)
+                xin = top if self.mix else top.clone()
+                if sp.inner is not None:
+                    T.mask_rows_(xin, sp.inner, sp.T2)
+                top, S["S_extra"] = self._layer_fwd(xin, self.L, sp)
             hid = T.add_cast(top)
-        loss = logits = lse = nll = None
-        red = c.get("ctc_loss_reduction", "mean")
-        ldl = T.pad64(V1)
+        S["hid"] = hid
         if self.head:
             if pd["final"] > 0:
-                T.dropout_(hid, pd["final"], seed, self._sid(L, 2))
-            lbuf = e32(B, T2, ldl)
-            if os.environ.get("HFASR_TRAIN_HEAD_LSE", "1") != "0":
-                lse = ops.gemm_lse(hid, W("head_w"), P("head_b"), lbuf.view(M, ldl))       # logits and their row log-sum-exp from one pass (the GEMM's epilogue)
-            else:                                                                          # (the two passes: A/B and trajectory comparisons)
-                ops.gemm(hid, W("head_w"), P("head_b"), out=lbuf.view(M, ldl))
-                lse = ops.row_lse(lbuf.view(M, ldl)[:, :V1])
-            logits = lbuf[..., :V1]
+                T.dropout_(hid, pd["final"], self.seed, self._sid(self.L, 2))
+            ldl = T.pad64(self.V1)
+            lbuf = self._e32(sp.B, sp.T2, ldl)
+            S["lse"] = ops.gemm_lse(hid, W("head_w"), P("head_b"), lbuf.view(M, ldl))       # logits and their row log-sum-exp from one pass (the GEMM's epilogue)
+            S["logits"] = lbuf[..., :self.V1]
             if labels is not None:
-                if not (backward and self.ctc_from_bwd and red in ("mean", "sum")):       # with a backward pass the loss comes out of ITS alpha recursion (below): no forward loss kernel
-                    loss, nll, _ = ops.ctc_loss(logits, labels, outer, reduction=red, zero_infinity=bool(c.get("ctc_zero_infinity", False)), lse=lse)
+                red = self.cfg.get("ctc_loss_reduction", "mean")
+                if not (backward and red in ("mean", "sum")):       # with a backward pass the loss comes out of ITS alpha recursion (_head_bwd): no forward loss kernel
+                    S["loss"], S["nll"], _ = ops.ctc_loss(S["logits"], labels, sp.outer, reduction=red, zero_infinity=bool(self.cfg.get("ctc_zero_infinity", False)),
+                                                          lse=S["lse"])
             elif backward:
                 raise ValueError("forward_backward: the backward pass of the CTC head needs `labels`")
-        out = dict(loss=loss, logits=logits, outer_len=outer, inner_len=inner,
-                   last_hidden=last_hidden.view(B, T2, d) if keep_hidden or extra_hidden_grad or not self.head else None)
-        if not backward:
-            return out
+        return S
 
-        # =================================================================== backward
-        def layer_bwd(dx, S, l):
-            p, sl = f"l{l}.", l + int(l >= L)
-            # final_layer_norm
-            # Every LayerNorm backward whose dx is next turned into a bf16 GEMM operand (scaled, dropped) writes that operand itself (`cast=`): no pass of its own
-            hdrop = lambda site: (pd["hidden"], seed, self._sid(sl, site)) if pd["hidden"] > 0 else None
-            mdrop = (pd["att"], seed, self._sid(sl, 5)) if pd["att"] > 0 else None
-            d3 = e32(M, d)
-            if macaron:
-                _, dyb = T.layernorm_bwd(S["x3"], P(p + "fin_ln_g"), dx, d3, accumulate=False, **self._lng(p + "fin_ln_g", p + "fin_ln_b"), cast=(0.5, hdrop(7)))
-                dx = d3
-                dyb = self._ffn_bwd(dx, S["x2"], S["ff2"], p + "ff2", pd, sl, (6, 7), dyb=dyb, cast_next=(1.0, mdrop))
-            else:
-                _, dyb = T.layernorm_bwd(S["x3"], P(p + "fin_ln_g"), dx, d3, accumulate=False, **self._lng(p + "fin_ln_g", p + "fin_ln_b"), cast=(1.0, mdrop))
-                dx = d3
-            # merge:  x2 = x1 + dropout(merge_proj(m2));  dyb = dropout(dx) as bf16
-            dm2 = T.linear_bwd(dyb, S["m2"], WT(p + "mrg_w"), dw=GL(p + "mrg_w"), db=GL(p + "mrg_b"), defer=self._tnb)
-            dcat = e16(M, 2 * d)
-            dwred = self._dwred()                       # the depthwise convs' cross-utterance tap-gradient sums ride the deferred LayerNorm reductions' launches
-            T.dwconv_residual_bwd(S["cat"], P(p + "mrg_dw_w"), dm2, dcat, G(p + "mrg_dw_w"), G(p + "mrg_dw_b"), B, T2, defer=dwred)
-            # local branch
-            dsg = T.linear_bwd(dcat[:, d:], S["sg"], WT(p + "mlp_w2"), dw=GL(p + "mlp_w2"), db=GL(p + "mlp_b2"), defer=self._tnb)
-            if pd["csgu"] > 0:
-                T.dropout_(dsg, pd["csgu"], seed, self._sid(sl, 4))
-            dh = e16(M, I)
-            dgn = e16(M, I // 2)
-            if self.csgu_split:
-                dlin = T.gate_act_mul_bwd(S["h"][:, :I // 2], S["lin"], dsg, dh[:, :I // 2], self.csgu_act)
-                dcv = T.linear_bwd(dlin, S["cv"], WT(p + "csgu_lin_w"), dw=GL(p + "csgu_lin_w"), db=GL(p + "csgu_lin_b"), defer=self._tnb) if self.csgu_lin else dlin
-                T.csgu_bwd(S["h"], S["stats"], P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), dcv, None, dgn,
-                           G(p + "csgu_w"), G(p + "csgu_b"), B, T2, pad_left=cs_pad, dilation=cs_dil, defer=dwred)
-            else:
-                T.csgu_bwd(S["h"], S["stats"], P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), dsg, dh[:, :I // 2], dgn,
-                           G(p + "csgu_w"), G(p + "csgu_b"), B, T2, pad_left=cs_pad, dilation=cs_dil, defer=dwred)
-            T.layernorm_bwd(S["h"][:, I // 2:], P(p + "csgu_ln_g"), dgn, dh[:, I // 2:], accumulate=False, **self._lng(p + "csgu_ln_g", p + "csgu_ln_b"))
-            dhp = T.act_bwd(dh, S["hp"])       # (folding this pass into the two kernels above was built and measured: each slows by what its share of this one costs — DESIGN §7)
-            da2 = T.linear_bwd(dhp, S["a2"], WT(p + "mlp_w1"), dw=GL(p + "mlp_w1"), db=GL(p + "mlp_b1"), defer=self._tnb)
-            # the two branch norms read the same x1: one pass for both when their affine pairs train (the gradient w.r.t. x1 is linear in dy * gamma)
-            lng_m, lng_a = self._lng(p + "mlp_ln_g", p + "mlp_ln_b"), self._lng(p + "att_ln_g", p + "att_ln_b")
-            dual = self.dual_ln and ptype != "rotary" and d <= 512 and lng_m["dgamma"] is not None and lng_a["dgamma"] is not None
-            if not dual:
-                T.layernorm_bwd(S["x1"], P(p + "mlp_ln_g"), da2, dx, accumulate=True, **lng_m)
-            # global branch
-            if pd["att"] > 0:
-                T.dropout_(dcat[:, :d], pd["att"], seed, self._sid(sl, 3))
-            dctx = T.linear_bwd(dcat[:, :d], S["ctx"], WT(p + "att_wo"), dw=GL(p + "att_wo"), db=GL(p + "att_bo"), defer=self._tnb)
-            dqkv = self._attention_bwd(dctx, S, p, pos, inner, B, T2, H, (pd["att"], seed, self._sid(sl, 2)) if pd["att"] > 0 else None)
-            if ptype == "rotary":
-                wt = WT(p + "att_wqkv")
-                da1r = T.linear_bwd(dqkv[:, :2 * d], S["a1r"], wt[:, :2 * d], dw=GL(p + "att_wqkv", slice(0, 2 * d)), db=GL(p + "att_bqkv", slice(0, 2 * d)), defer=self._tnb)
-                da1 = T.linear_bwd(dqkv[:, 2 * d:], S["a1"], wt[:, 2 * d:3 * d], dw=GL(p + "att_wqkv", slice(2 * d, None)), db=GL(p + "att_bqkv", slice(2 * d, None)), dx_dtype=F32, defer=self._tnb)
-                rot = ops.rotary(da1r, pos[0].reshape(-1), pos[2].reshape(-1), T2, H)             # R^T = rotation by -theta
-                T.layernorm_bwd(S["x1"], P(p + "att_ln_g"), da1, dx, accumulate=True, **self._lng(p + "att_ln_g", p + "att_ln_b"))
-                last = dict(x=S["x1"], g=P(p + "att_ln_g"), dy=rot)
-            else:
-                da1 = T.linear_bwd(dqkv, S["a1"], WT(p + "att_wqkv")[:, :3 * d], dw=GL(p + "att_wqkv"), db=GL(p + "att_bqkv"), defer=self._tnb)
-                last = dict(x=S["x1"], g=P(p + "att_ln_g"), dy=da1)
-                if dual:
-                    r = T.layernorm_bwd_dual(S["x1"], P(p + "att_ln_g"), da1, P(p + "mlp_ln_g"), da2, dx, accumulate=True, dgamma=lng_a["dgamma"], dbeta=lng_a["dbeta"],
-                                             dgamma2=lng_m["dgamma"], dbeta2=lng_m["dbeta"], defer=lng_a["defer"], cast=(0.5, hdrop(1)) if macaron else None)
-                    if macaron:
-                        self._ffn_bwd(dx, S["x_in"], S["ff1"], p + "ff1", pd, sl, (0, 1), dyb=r[1])
-                    return dx
-            if macaron:             # the layer's last accumulation into dx also leaves the first FFN's bf16 operand
-                _, dyb = T.layernorm_bwd(last["x"], last["g"], last["dy"], dx, accumulate=True, **self._lng(p + "att_ln_g", p + "att_ln_b"), cast=(0.5, hdrop(1)))
-                self._ffn_bwd(dx, S["x_in"], S["ff1"], p + "ff1", pd, sl, (0, 1), dyb=dyb)
-            else:
-                T.layernorm_bwd(last["x"], last["g"], last["dy"], dx, accumulate=True, **self._lng(p + "att_ln_g", p + "att_ln_b"))
-            return dx
-
+    def _head_bwd(self, S, sp, labels, loss_scale, extra_hidden_grad, out):
+        """the CTC head's backward (leaves the loss in out["loss"] when the forward did not compute it), then [additional layer, layer mixing] and the encoder
+        LayerNorm -> (gradient at the last layer's output (M, d) f32, the gradient at the mixed hidden states or None)"""
+        st, P, G, WT, pd, M, d, L = self.store, self.store.p, self.store.g, self.store.bfT, sp.pd, sp.M, self.d, self.L
+        x = S["x"]
         gs = float(loss_scale) / self.sync.world
         dhid = None
         if self.head:
+            logits, lse, nll, red, ldl = S["logits"], S["lse"], S["nll"], self.cfg.get("ctc_loss_reduction", "mean"), T.pad64(self.V1)
             dlog = None
             if nll is None:         # loss, per-utterance nll and the gradient from one pair of recursions; a target too long for that kernel takes the two calls
-                zi = bool(c.get("ctc_zero_infinity", False))
-                r = T.ctc_loss_bwd_nll(logits, lse, labels, outer, reduction=red, zero_infinity=zi, gscale=gs, ldo=ldl)
+                zi = bool(self.cfg.get("ctc_zero_infinity", False))
+                r = T.ctc_loss_bwd_nll(logits, lse, labels, sp.outer, reduction=red, zero_infinity=zi, gscale=gs, ldo=ldl)
                 if r is not None:
                     dlog, loss, nll = r
                 else:
-                    loss, nll, _ = ops.ctc_loss(logits, labels, outer, reduction=red, zero_infinity=zi, lse=lse)
+                    loss, nll, _ = ops.ctc_loss(logits, labels, sp.outer, reduction=red, zero_infinity=zi, lse=lse)
                 out["loss"] = loss
             if dlog is None:
-                dlog = T.ctc_loss_bwd(logits, lse, labels, outer, nll, reduction=red, gscale=gs, ldo=ldl)         # (M, ldl) bf16
+                dlog = T.ctc_loss_bwd(logits, lse, labels, sp.outer, nll, reduction=red, gscale=gs, ldo=ldl)         # (M, ldl) bf16
             dhid = T.gemm(dlog, WT("head_w"), out_dtype=F32 if (self.mix or self.extra) else BF16)           # (M, d)
             if pd["final"] > 0:
-                T.dropout_(dhid, pd["final"], seed, self._sid(L, 2))
-            T.gemm_tn_(G("head_w"), dlog, hid, n_store=V1, db=G("head_b"))
-        dx = e32(M, d)
+                T.dropout_(dhid, pd["final"], self.seed, self._sid(L, 2))
+            T.gemm_tn_(G("head_w"), dlog, S["hid"], n_store=self.V1, db=G("head_b"))
+        dx = self._e32(M, d)
         dmix = None
         if self.mix or self.extra:
             self._range_done(*st.range_of(["head_w", "head_b"]))
             dtop = dhid                                               # f32: gradient at the head's input
             if self.extra:
-                dtop = layer_bwd(dtop, S_extra, L)
-                if inner is not None:
-                    T.mask_rows_(dtop, inner, T2)
+                dtop = self._layer_bwd(dtop, S["S_extra"], L, sp)
+                if sp.inner is not None:
+                    T.mask_rows_(dtop, sp.inner, sp.T2)
                 self._range_done(*st.range_of(self._layer_names[L]))
             if self.mix:            # d hidden_l = s_l * d mixed;  d per_layer_weights = s * (g - <s, g>),  g_l = <d mixed, hidden_l>
-                dmix = dtop
-                gdot = torch.zeros(L + 1, device=dev, dtype=F32)
-                for i, h in enumerate(hs):
+                dmix, sw = dtop, S["sw"]
+                gdot = torch.zeros(L + 1, device=self.device, dtype=F32)
+                for i, h in enumerate(S["hs"]):
                     T.dot_(gdot[i:i + 1], dmix, h.reshape(M, d))
                 T.softmax_vec_bwd_(G("mix_w"), sw, gdot)
-                dtop = T.axpy_dev_(e32(M, d), dmix, sw[L:L + 1], overwrite=True)
-            T.layernorm_bwd(x, P("enc_ln_g"), dtop, dx, accumulate=False, **self._lng("enc_ln_g", "enc_ln_b"), eps=eps_e)
+                dtop = T.axpy_dev_(self._e32(M, d), dmix, sw[L:L + 1], overwrite=True)
+            T.layernorm_bwd(x, P("enc_ln_g"), dtop, dx, accumulate=False, **self._lng("enc_ln_g", "enc_ln_b"), eps=self.eps_e)
         elif dhid is not None:
-            T.layernorm_bwd(x, P("enc_ln_g"), dhid, dx, accumulate=False, **self._lng("enc_ln_g", "enc_ln_b"), eps=eps_e)
+            T.layernorm_bwd(x, P("enc_ln_g"), dhid, dx, accumulate=False, **self._lng("enc_ln_g", "enc_ln_b"), eps=self.eps_e)
         if extra_hidden_grad is not None:
-            dh32 = extra_hidden_grad(last_hidden, outer)
+            dh32 = extra_hidden_grad(S["last_hidden"], sp.outer)
             if dh32 is not None:
-                T.layernorm_bwd(x, P("enc_ln_g"), dh32, dx, accumulate=dhid is not None, **self._lng("enc_ln_g", "enc_ln_b"), eps=eps_e)
+                T.layernorm_bwd(x, P("enc_ln_g"), dh32, dx, accumulate=dhid is not None, **self._lng("enc_ln_g", "enc_ln_b"), eps=self.eps_e)
             elif dhid is None:
                 dx.zero_()
         self._range_done(*st.range_of(self._encln_names if (self.mix or self.extra) else self._head_names))
-        for l in range(L - 1, -1, -1):
-            S = saved[l]
-            if S is not None:               # (a dropped layer: dx passes through, its gradient range stays zero — still reduced: other ranks may have run it)
-                dx = layer_bwd(dx, S, l)
-            if dmix is not None:            # layer mixing: hidden_states[l] is this layer's input
-                T.axpy_dev_(dx, dmix, sw[l:l + 1])
-            self._range_done(*st.range_of(self._layer_names[l]))
-        # ---------------- front end
+        return dx, dmix
+
+    def _layer_bwd(self, dx, S, l, sp):
+        """gradient at a layer's output -> gradient at its input; parameter gradients accumulate into the store (weight-gradient GEMMs deferred to `_tnb`)"""
+        P, G, WT, GL, pd, seed = self.store.p, self.store.g, self.store.bfT, self._gl, sp.pd, self.seed
+        B, T2, M, d, I, pos = sp.B, sp.T2, sp.M, self.d, self.I, sp.pos
+        p, sl = f"l{l}.", l + int(l >= self.L)
+        # final_layer_norm
+        # Every LayerNorm backward whose dx is next turned into a bf16 GEMM operand (scaled, dropped) writes that operand itself (`cast=`): no pass of its own
+        hdrop = lambda site: (pd["hidden"], seed, self._sid(sl, site)) if pd["hidden"] > 0 else None
+        mdrop = (pd["att"], seed, self._sid(sl, 5)) if pd["att"] > 0 else None
+        d3 = self._e32(M, d)
+        if self.macaron:
+            _, dyb = T.layernorm_bwd(S["x3"], P(p + "fin_ln_g"), dx, d3, accumulate=False, **self._lng(p + "fin_ln_g", p + "fin_ln_b"), cast=(0.5, hdrop(7)))
+            dx = d3
+            dyb = self._ffn_bwd(dx, S["x2"], S["ff2"], p + "ff2", pd, sl, (6, 7), dyb=dyb, cast_next=(1.0, mdrop))
+        else:
+            _, dyb = T.layernorm_bwd(S["x3"], P(p + "fin_ln_g"), dx, d3, accumulate=False, **self._lng(p + "fin_ln_g", p + "fin_ln_b"), cast=(1.0, mdrop))
+            dx = d3
+        # merge:  x2 = x1 + dropout(merge_proj(m2));  dyb = dropout(dx) as bf16
+        dm2 = T.linear_bwd(dyb, S["m2"], WT(p + "mrg_w"), dw=GL(p + "mrg_w"), db=GL(p + "mrg_b"), defer=self._tnb)
+        dcat = self._e16(M, 2 * d)
+        # the depthwise convs' cross-utterance tap-gradient sums ride the deferred LayerNorm reductions' launches
+        T.dwconv_residual_bwd(S["cat"], P(p + "mrg_dw_w"), dm2, dcat, G(p + "mrg_dw_w"), G(p + "mrg_dw_b"), B, T2, defer=self._lnred)
+        # local branch
+        dsg = T.linear_bwd(dcat[:, d:], S["sg"], WT(p + "mlp_w2"), dw=GL(p + "mlp_w2"), db=GL(p + "mlp_b2"), defer=self._tnb)
+        if pd["csgu"] > 0:
+            T.dropout_(dsg, pd["csgu"], seed, self._sid(sl, 4))
+        dh = self._e16(M, I)
+        dgn = self._e16(M, I // 2)
+        if self.csgu_split:
+            dlin = T.gate_act_mul_bwd(S["h"][:, :I // 2], S["lin"], dsg, dh[:, :I // 2], self.csgu_act)
+            dcv = T.linear_bwd(dlin, S["cv"], WT(p + "csgu_lin_w"), dw=GL(p + "csgu_lin_w"), db=GL(p + "csgu_lin_b"), defer=self._tnb) if self.csgu_lin else dlin
+            T.csgu_bwd(S["h"], S["stats"], P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), dcv, None, dgn,
+                       G(p + "csgu_w"), G(p + "csgu_b"), B, T2, pad_left=self.cs_pad, dilation=self.cs_dil, defer=self._lnred)
+        else:
+            T.csgu_bwd(S["h"], S["stats"], P(p + "csgu_ln_g"), P(p + "csgu_ln_b"), P(p + "csgu_w"), P(p + "csgu_b"), dsg, dh[:, :I // 2], dgn,
+                       G(p + "csgu_w"), G(p + "csgu_b"), B, T2, pad_left=self.cs_pad, dilation=self.cs_dil, defer=self._lnred)
+        T.layernorm_bwd(S["h"][:, I // 2:], P(p + "csgu_ln_g"), dgn, dh[:, I // 2:], accumulate=False, **self._lng(p + "csgu_ln_g", p + "csgu_ln_b"))
+        dhp = T.act_bwd(dh, S["hp"])       # (folding this pass into the two kernels above was built and measured: each slows by what its share of this one costs — DESIGN §7)
+        da2 = T.linear_bwd(dhp, S["a2"], WT(p + "mlp_w1"), dw=GL(p + "mlp_w1"), db=GL(p + "mlp_b1"), defer=self._tnb)
+        # the two branch norms read the same x1: one pass for both when their affine pairs train (the gradient w.r.t. x1 is linear in dy * gamma)
+        lng_m, lng_a = self._lng(p + "mlp_ln_g", p + "mlp_ln_b"), self._lng(p + "att_ln_g", p + "att_ln_b")
+        dual = self.ptype != "rotary" and d <= 512 and lng_m["dgamma"] is not None and lng_a["dgamma"] is not None
+        if not dual:
+            T.layernorm_bwd(S["x1"], P(p + "mlp_ln_g"), da2, dx, accumulate=True, **lng_m)
+        # global branch
+        if pd["att"] > 0:
+            T.dropout_(dcat[:, :d], pd["att"], seed, self._sid(sl, 3))
+        dctx = T.linear_bwd(dcat[:, :d], S["ctx"], WT(p + "att_wo"), dw=GL(p + "att_wo"), db=GL(p + "att_bo"), defer=self._tnb)
+        dqkv = self._attention_bwd(dctx, S, p, pos, sp.inner, B, T2, self.H, (pd["att"], seed, self._sid(sl, 2)) if pd["att"] > 0 else None)
+        if self.ptype == "rotary":
+            wt = WT(p + "att_wqkv")
+            da1r = T.linear_bwd(dqkv[:, :2 * d], S["a1r"], wt[:, :2 * d], dw=GL(p + "att_wqkv", slice(0, 2 * d)), db=GL(p + "att_bqkv", slice(0, 2 * d)), defer=self._tnb)
+            da1 = T.linear_bwd(dqkv[:, 2 * d:], S["a1"], wt[:, 2 * d:3 * d], dw=GL(p + "att_wqkv", slice(2 * d, None)), db=GL(p + "att_bqkv", slice(2 * d, None)),
+                               dx_dtype=F32, defer=self._tnb)
+            rot = ops.rotary(da1r, pos[0].reshape(-1), pos[2].reshape(-1), T2, self.H)             # R^T = rotation by -theta
+            T.layernorm_bwd(S["x1"], P(p + "att_ln_g"), da1, dx, accumulate=True, **self._lng(p + "att_ln_g", p + "att_ln_b"))
+            last = dict(x=S["x1"], g=P(p + "att_ln_g"), dy=rot)
+        else:
+            da1 = T.linear_bwd(dqkv, S["a1"], WT(p + "att_wqkv")[:, :3 * d], dw=GL(p + "att_wqkv"), db=GL(p + "att_bqkv"), defer=self._tnb)
+            last = dict(x=S["x1"], g=P(p + "att_ln_g"), dy=da1)
+            if dual:
+                r = T.layernorm_bwd_dual(S["x1"], P(p + "att_ln_g"), da1, P(p + "mlp_ln_g"), da2, dx, accumulate=True, dgamma=lng_a["dgamma"], dbeta=lng_a["dbeta"],
+                                         dgamma2=lng_m["dgamma"], dbeta2=lng_m["dbeta"], defer=lng_a["defer"], cast=(0.5, hdrop(1)) if self.macaron else None)
+                if self.macaron:
+                    self._ffn_bwd(dx, S["x_in"], S["ff1"], p + "ff1", pd, sl, (0, 1), dyb=r[1])
+                return dx
+        if self.macaron:             # the layer's last accumulation into dx also leaves the first FFN's bf16 operand
+            _, dyb = T.layernorm_bwd(last["x"], last["g"], last["dy"], dx, accumulate=True, **self._lng(p + "att_ln_g", p + "att_ln_b"), cast=(0.5, hdrop(1)))
+            self._ffn_bwd(dx, S["x_in"], S["ff1"], p + "ff1", pd, sl, (0, 1), dyb=dyb)
+        else:
+            T.layernorm_bwd(last["x"], last["g"], last["dy"], dx, accumulate=True, **self._lng(p + "att_ln_g", p + "att_ln_b"))
+        return dx
+
+    def _front_bwd(self, dx, feats, S, sp, noise_mask):
+        """gradient at the encoder input (dx, consumed) back through the input masking, feature projection and Conv2d sub-sampling: the backward's last range"""
+        P, G, WT, GL, pd, seed, L = self.store.p, self.store.g, self.store.bfT, self._gl, sp.pd, self.seed, self.L
+        B, T1, T2, F1, F2, M = sp.B, sp.T1, sp.T2, sp.F1, sp.F2, sp.M
+        K, s_, pad, padl, C1, C2, cm = self.K, self.stride, self.pad, self.padl, self.C1, self.C2, self.ctx_mode
         if pd["hidden"] > 0:
             T.dropout_(dx, pd["hidden"], seed, self._sid(L, 1))
-        if inner is not None:
-            T.mask_rows_(dx, inner, T2)
+        if sp.inner is not None:
+            T.mask_rows_(dx, sp.inner, T2)
         if noise_mask is not None:
             T.spec_mask_bwd_(dx, noise_mask[0], None, None, T2)          # replaced frames pass no gradient upstream
-        elif tmask is not None or fmask is not None:
-            T.spec_mask_bwd_(dx, tmask, G("masked_spec_embed"), fmask, T2)
-        dyb = T.dropout_(dx, pd["fp"], seed, self._sid(L, 0), out=e16(M, d)) if pd["fp"] > 0 else T.add_cast(dx)
-        da = T.linear_bwd(dyb, a_fp, WT("fp_w"), dw=GL("fp_w"), db=GL("fp_b"))
-        dfeo = e32(M, d)
-        T.layernorm_bwd(feo, P("fp_ln_g"), da, dfeo, accumulate=False, **self._lng("fp_ln_g", "fp_ln_b"), eps=eps_e)
-        dact2 = T.linear_bwd(T.add_cast(dfeo), act2, WT("feout_w"), dw=GL("feout_w"), db=GL("feout_b"))      # (M, F2*C2)
+        elif S["tmask"] is not None or S["fmask"] is not None:
+            T.spec_mask_bwd_(dx, S["tmask"], G("masked_spec_embed"), S["fmask"], T2)
+        dyb = T.dropout_(dx, pd["fp"], seed, self._sid(L, 0), out=self._e16(M, self.d)) if pd["fp"] > 0 else T.add_cast(dx)
+        da = T.linear_bwd(dyb, S["a_fp"], WT("fp_w"), dw=GL("fp_w"), db=GL("fp_b"))
+        dfeo = self._e32(M, self.d)
+        T.layernorm_bwd(S["feo"], P("fp_ln_g"), da, dfeo, accumulate=False, **self._lng("fp_ln_g", "fp_ln_b"), eps=self.eps_e)
+        dact2 = T.linear_bwd(T.add_cast(dfeo), S["act2"], WT("feout_w"), dw=GL("feout_w"), db=GL("feout_b"))      # (M, F2*C2)
+        act1 = S["act1"]
         if cm == 0:
-            dpre2 = T.act_bwd(dact2.view(B * T2 * F2, C2), pre2)
+            dpre2 = T.act_bwd(dact2.view(B * T2 * F2, C2), S["pre2"])
             T.conv2d_wgrad_(G("conv2_w"), dpre2, act1, K, s_, padl, T2, F2, db=G("conv2_b"))      # the im2col operand is gathered inside the GEMM, never written
             if K == 3 and s_ == 2 and T.conv2d_s2k3_dgrad_supported(B, T1, F1, C1, T2, F2, padl):
                 # conv2's input gradient as four stride-1 convolutions (one per parity of the position) into phase buffers that conv1's backward reads directly
@@ -1020,17 +1034,19 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         else:
             # y = z * sigmoid(g), out = GELU(y): dz = dout GELU'(y) sigmoid(g), dg = sum over the rows sharing g of dout GELU'(y) z sigmoid(g)(1 - sigmoid(g));
             # then conv and gate are two plain convs (ONE for "gated": conv and gate rows stacked) — dW = dY^T col, dX = col2im(dY W)
+            share, (gK, gS, gP) = self.share, self.gate_geo
+            cK, cS, cP = (K, K), (s_, s_), (pad, pad)
             dact2 = dact2.view(B * T2 * F2, C2)
             col = T.im2col(act1, K, s_, pad, T2, F2)
             if cm == 1:
-                dzg = e16(B * T2 * F2, 2 * C2)
-                T.gated_act_bwd(dact2, z2, g2, B, T2, F2, C2, 1, dz=dzg[:, :C2], dg=dzg[:, C2:])
+                dzg = self._e16(B * T2 * F2, 2 * C2)
+                T.gated_act_bwd(dact2, S["z2"], S["g2"], B, T2, F2, C2, 1, dz=dzg[:, :C2], dg=dzg[:, C2:])
                 T.gemm_tn_(G("conv2_w"), dzg, col, db=G("conv2_b"))
                 dcol = ops.gemm(dzg, WT("conv2_w")[:, :2 * C2])
                 del col
                 dact1 = T.col2im(dcol, (B, T1, F1, C1), cK, cS, cP, T2, F2)
             else:
-                dz2, dg2 = T.gated_act_bwd(dact2, z2, g2, B, T2, F2, C2, share)
+                dz2, dg2 = T.gated_act_bwd(dact2, S["z2"], S["g2"], B, T2, F2, C2, share)
                 T.gemm_tn_(G("conv2_w"), dz2, col, db=G("conv2_b"))
                 dcol = ops.gemm(dz2, WT("conv2_w")[:, :C2])
                 del col
@@ -1041,11 +1057,10 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
                 del colg
                 T.col2im(dcol, (B, T1, F1, C1), gK, gS, gP, T2 // share, F2, out=dact1)
             del dcol
-            dz1, dg1 = T.gated_act_bwd(dact1.view(-1, C1), z1.view(-1, C1), g1.view(-1, C1), B, T1, F1, C1, share)
+            dz1, dg1 = T.gated_act_bwd(dact1.view(-1, C1), S["z1"].view(-1, C1), S["g1"].view(-1, C1), B, T1, F1, C1, share)
             T.conv2d_first_wgrad(feats, dz1.view(B, T1, F1, C1), G("conv1_w"), G("conv1_b"), cK, cS, cP)
             T.conv2d_first_wgrad(feats, dg1.view(B, T1 // share, F1, C1), G("gate1_w"), G("gate1_b"), gK, gS, gP)
-        self._range_done(*st.range_of(self._front_names), final=True)
-        return out
+        self._range_done(*self.store.range_of(self._front_names), final=True)
 
     # ------------------------------------------------------------------ pieces
     def _sid(self, layer: int, site: int) -> int:
@@ -1073,32 +1088,16 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         return tm, fm
 
     def _outer_len(self, n):
-        k, s = self.cfg["conv_kernel"][0], self.cfg["conv_stride"][0]
         for _ in range(2):
-            n = (n - k) // s + 1
+            n = (n - self.K) // self.stride + 1
         return n
 
-    def _lengths(self, feat_lengths, T2):
-        c = self.cfg
-        k, s, p = c["conv_kernel"][0], c["conv_stride"][0], c["conv_padding"][0]
-        if feat_lengths.is_cuda and feat_lengths.dtype == torch.int32:                 # one launch instead of fifteen one-block torch kernels
-            from . import _lib
-            inner, outer = torch.empty_like(feat_lengths), torch.empty_like(feat_lengths)
-            _lib.check(_lib.lib().mi_subsampled_lengths_i32(feat_lengths.data_ptr(), feat_lengths.numel(), int(k), int(s), int(p), 2, int(T2), inner.data_ptr(), outer.data_ptr(),
-                                                            torch.cuda.current_stream().cuda_stream), "mi_subsampled_lengths_i32")
-            return inner, outer
-        li, lo = feat_lengths.clone(), feat_lengths.clone()
-        for _ in range(2):
-            li = torch.div(li + 2 * p - k, s, rounding_mode="floor") + 1
-            lo = torch.div(lo - k, s, rounding_mode="floor") + 1
-        return torch.clamp(li, max=T2).to(torch.int32), lo.to(torch.int32)
-
-    def _ffn_fwd(self, x, pre, LN, e16, pd, l, sites):
+    def _ffn_fwd(self, x, pre, pd, l, sites):
         """x + 0.5 * dropout(W2 dropout(gelu(W1 LN(x))))  (e_branchformer.py:271-273, 307-309; tf:350-357)"""
         P, W = self.store.p, self.store.bf
         M, d = x.shape
-        a = e16(M, d)
-        LN(x, lna=(P(pre + "_ln_g"), P(pre + "_ln_b")), outa=a)
+        a = self._e16(M, d)
+        ops.layernorm_chain(x, lna=(P(pre + "_ln_g"), P(pre + "_ln_b")), outa=a)
         # intermediate_dense + GELU + activation dropout: one launch (the GEMM's training epilogue leaves the pre-activation for the backward and the activation)
         hp, h = T.gemm_act_fwd(a, W(pre + "_w1"), P(pre + "_b1"), drop=(pd["act"], self.seed, self._sid(l, sites[0])) if pd["act"] > 0 else None)
         if pd["hidden"] > 0:
@@ -1111,8 +1110,7 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         """dx (f32, in place): gradient w.r.t. the block output -> gradient w.r.t. its input (residual + LN path).
         dyb: bf16(0.5 * dropout(dx)) when the producer of dx already wrote it; cast_next = (alpha, drop): -> the same operand of the NEXT linear backward,
         written by this block's LayerNorm backward."""
-        P, G, WT = self.store.p, self.store.g, self.store.bfT
-        GL = lambda n: None if n in self.frozen else self.store.g(n)
+        P, WT, GL = self.store.p, self.store.bfT, self._gl
         if dyb is None:
             if pd["hidden"] > 0:
                 dyb = T.dropout_(dx, pd["hidden"], self.seed, self._sid(l, sites[1]), out=torch.empty(dx.shape, device=dx.device, dtype=BF16), alpha=0.5)
@@ -1187,11 +1185,9 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
             # accumulates dQ = dS K + dBD P on the way (its two terms' column sums are the position-bias gradients)
             # (with positions the walk also leaves q + u and q + v, its own A operands, for the dK and d(positions) products below)
             prob, ds, dbd, su, sv, qu, qv = T.attn_bwd_probs(qkv, B, Tt, H, S["ctx"], dctx, S["lse"], dqkv[:, :d], pos=posp, bias_u=P(p + "att_u") if rel else None,
-                                                             bias_v=P(p + "att_v") if rel else None, lengths=lengths, causal=self.causal, drop=drop, qb=self.walk_qb, sparse=self.sparse_attn_bwd)[:7] + ((None, None) if not self.walk_qb else ())
+                                                             bias_v=P(p + "att_v") if rel else None, lengths=lengths, causal=self.causal, drop=drop, qb=True, sparse=self.sparse_attn_bwd)
             fused = True
             if rel:
-                if qu is None:
-                    qu, qv = T.add_rowvec2(q, P(p + "att_u"), P(p + "att_v"))
                 off, Kp = T.band_geometry(Tt)                 # dbd's columns are relative positions + off
         else:
             fused = False
@@ -1221,7 +1217,7 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
             return dqkv
         Ps = dbd.shape[-1]
         if fused:
-            self._dwred().add_rows2(su, G(p + "att_u"), G(p + "att_v"))       # the per-wave rows' column sums leave with the deferred LayerNorm reductions' next launch
+            self._lnred.add_rows2(su, G(p + "att_u"), G(p + "att_v"))       # the per-wave rows' column sums leave with the deferred LayerNorm reductions' next launch
         else:
             dqu = torch.empty((M, d), device=dev, dtype=F32)
             dqv = torch.empty((M, d), device=dev, dtype=F32)

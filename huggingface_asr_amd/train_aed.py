@@ -275,7 +275,7 @@ class JointAEDTrainer(ZeroCopyTrainer):
         tnb = T.TnBatch()            # every weight gradient of the decoder's backward: one grouped launch at the end (46 problems, ~150 output tiles at 6 x 256)
         # first backward after zero_grad: the launch writes its targets instead of adding into the zeros (train.EncoderCTCTrainer._forward_backward); the embedding
         # gradient — the one other contribution to a matrix of this store (wte, tied to the lm head) — is therefore added AFTER the flush below
-        tnb.overwrite = bool(self.enc.dw_overwrite and getattr(st, "fresh", False))
+        tnb.overwrite = st.fresh
         st.fresh = False
         T.gemm_tn_(G(lm_name), dl, hid, n_store=V, defer=tnb)
         tap_grads, final_dys = {}, [dhid]
