@@ -2,6 +2,8 @@
 """Headline benchmark: audio-seconds/sec, encoder forward + CTC, E-Branchformer-base (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 outside torchrun: the bench starts its N ranks itself, one per GPU)
+    python bench.py ... --full                                   (also everything beyond the headline, after the timed region: one step at a time, roofline, CPU baseline,
+                                                                  configs 3 / 4 / 5 as `secondary` on one rank, `train_dp` on more than one)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --gpus N --train                             (BASELINE config 3: data-parallel training step, gradient all-reduce over RCCL)
     python bench.py ... --dump-outputs DIR                       (also write what the last timed step returned to DIR/*.npy: same arguments, same inputs)
@@ -105,7 +107,7 @@ def rocprof_child_dense_us(args, B, per_step):
     steps = max(3, min(10, args.event_steps))
     with tempfile.TemporaryDirectory(dir="/tmp") as td:
         cmd = [exe, "--kernel-trace", "--stats", "--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", "2",
-               "--batch", str(B), "--pos", args.pos, "--streams", "1", "--no-cpu-baseline", "--no-kernel-events", "--no-secondary"]
+               "--batch", str(B), "--pos", args.pos, "--streams", "1"]                  # a plain run: warm-up and timed steps only
         try:
             r = subprocess.run(cmd, env=dict(os.environ, TMPDIR="/tmp"), cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=240)      # ~20 s when all is well
         except Exception as e:  # noqa: BLE001
@@ -133,8 +135,8 @@ def rocprof_child_dense_us(args, B, per_step):
 
 
 def rocprof_child_in_flight(args, B):
-    """The headline's OWN mode (steps in flight, wide tiles) as a kernel trace: a rocprofv3 --kernel-trace child run of this script with the default lanes and no one-step
-    comparison, summarised by tools/lanes_trace.py — the share of the wall in which a dense kernel / only other kernels / nothing runs, and the non-GEMM share of the busy
+    """The headline's OWN mode (steps in flight, wide tiles) as a kernel trace: a rocprofv3 --kernel-trace child run of this script (a plain run) with the default lanes,
+    summarised by tools/lanes_trace.py — the share of the wall in which a dense kernel / only other kernels / nothing runs, and the non-GEMM share of the busy
     time.  Tracing serialises dispatch bookkeeping, so the traced wall is longer than the timed region's (both are reported); the shares are what the trace is for."""
     import glob
     import shutil
@@ -149,7 +151,7 @@ def rocprof_child_in_flight(args, B):
     import lanes_trace
     with tempfile.TemporaryDirectory(dir="/tmp") as td:
         cmd = [exe, "--kernel-trace", "--output-format", "csv", "-d", td, "--", sys.executable, os.path.abspath(__file__), "--steps", "24", "--warmup", "8", "--batch", str(B),
-               "--pos", args.pos, "--streams", str(args.streams), "--wide-tiles", str(int(args.wide_tiles)), "--no-cpu-baseline", "--no-kernel-events", "--no-secondary", "--no-one-step"]
+               "--pos", args.pos, "--streams", str(args.streams), "--wide-tiles", str(int(args.wide_tiles))]
         try:
             r = subprocess.run(cmd, env=dict(os.environ, TMPDIR="/tmp"), cwd="/tmp", stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=150)      # ~20 s when all is well
         except Exception as e:  # noqa: BLE001
@@ -199,9 +201,13 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default 32 forward / 96 --train)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure what the headline does not need (each leg below can be left out with its --no-* "
+                                                        "option): one step at a time, the roofline leg and the in-flight trace, the CPU baseline, the secondary records "
+                                                        "(configs 3, 4, 5) on one rank, `train_dp` on more than one.  Without it a run sets up, warms up, times its steps, "
+                                                        "writes --dump-outputs and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--head-lse", action="store_true", help="the CTC loss's row log-sum-exp out of the head GEMM's epilogue (mi_ebf_forward_lse) instead of a pass of its own over the logits: same-box A/B (tools/head_lse_ab.sh)")
-    ap.add_argument("--no-kernel-events", action="store_true", help="skip the separate HIP-event pass over the dense GEMM launches (roofline leg)")
+    ap.add_argument("--no-kernel-events", action="store_true", help="--full: skip the separate HIP-event pass over the dense GEMM launches (roofline leg)")
     ap.add_argument("--event-steps", type=int, default=5, help="steps of the separate roofline pass (every dense launch timed, stride 1; never inside the timed region)")
     ap.add_argument("--keep-profile", default=None, help="directory that receives the kernel_stats.csv of the roofline leg's rocprofv3 child run")
     ap.add_argument("--pos", default="relative", choices=["relative", "rotary"])
@@ -224,12 +230,11 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous check on a box without GPUs: gloo, no HIP work, value null")
     ap.add_argument("--secondary", default=None, choices=["whisper", "decode", "train"], help="run ONE bounded secondary measurement (config 4 / 5 / 3) on cuda:0 and print its "
                                                                                                 "JSON; the default run starts these as children after its timed region")
-    ap.add_argument("--no-one-step", action="store_true", help="skip the one-step-at-a-time comparison after the timed region (a kernel trace of this command then shows the "
-                                                                "headline's own mode only: tools/lanes_trace.py)")
-    ap.add_argument("--no-in-flight-trace", action="store_true", help="skip the kernel trace of the headline's own mode (`roofline.in_flight.trace`)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary records (configs 3, 4, 5) of the default single-GPU run")
+    ap.add_argument("--no-one-step", action="store_true", help="--full: skip the one-step-at-a-time comparison after the timed region")
+    ap.add_argument("--no-in-flight-trace", action="store_true", help="--full: skip the kernel trace of the headline's own mode (`roofline.in_flight.trace`)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary records (configs 3, 4, 5) of a single-GPU run")
     ap.add_argument("--secondary-timeout", type=float, default=150.0, help="seconds allowed per secondary child")
-    ap.add_argument("--no-train-dp", action="store_true", help="more than one rank: skip the config-3 training step under both gradient all-reduce schedules")
+    ap.add_argument("--no-train-dp", action="store_true", help="--full, more than one rank: skip the config-3 training step under both gradient all-reduce schedules")
     ap.add_argument("--train-dp-batch", type=int, default=96, help="per-GPU batch of the `train_dp` record (config 3: 96)")
     ap.add_argument("--train-dp-steps", type=int, default=5, help="timed steps per schedule of the `train_dp` record")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="forward bench: after the timed steps write what the last timed step returned (CTC loss, encoder "
@@ -239,6 +244,8 @@ def parse_args(argv=None):
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.train or args.secondary or args.dry_run):
         ap.error("--dump-outputs covers the forward headline only (not --train, --secondary or --dry-run)")
+    if args.keep_profile and not args.full:
+        ap.error("--keep-profile keeps a file of the roofline leg, which runs with --full only")
     if args.wide_tiles is None:
         args.wide_tiles = int(args.streams >= 3)         # wide tiles leave one step alone with a quarter of the blocks per launch: they come with the lanes that fill the rest
     return args
@@ -632,7 +639,7 @@ def main():
     nstr = max(1, args.streams)
     pipe = ForwardPipeline(cfg, dev, sd, lanes=nstr, wide_tiles=bool(args.wide_tiles))
     eng = pipe.engines[0]
-    if args.wide_tiles:                      # the one-step-at-a-time comparison and the per-kernel roofline leg run the product's own tiles (wide tiles are for steps in flight)
+    if args.full and args.wide_tiles:        # the one-step-at-a-time comparison and the per-kernel roofline leg run the product's own tiles (wide tiles are for steps in flight)
         eng = EBranchformerEngine(cfg, dev)
         eng.load_state_dict(sd)
     if args.head_lse:
@@ -659,7 +666,7 @@ def main():
         return pipe.submit(lambda e, lane: step(e, *batches[lane], keep=keep))
 
     L = _lib.lib()
-    use_events = not args.no_kernel_events and rank == 0
+    use_events = args.full and not args.no_kernel_events and rank == 0
     n_gemm_per_step = 4 + cfg["num_hidden_layers"] * 10 + 1
     for _ in range(max(args.warmup, nstr)):
         step_pipelined()
@@ -677,7 +684,7 @@ def main():
     if last is not None:
         dump_outputs(args.dump_outputs, last)
     single = None
-    if nstr > 1 and not args.no_one_step:    # the same K steps strictly one at a time (outside the timed region): what the pipelining buys
+    if args.full and nstr > 1 and not args.no_one_step:    # the same K steps strictly one at a time (outside the timed region): what the pipelining buys
         for _ in range(2):
             step()
         dt1 = PL.timed(lambda: step(), args.steps, sync=torch.cuda.synchronize, device=dev)
@@ -780,12 +787,16 @@ def main():
         # flat copies of what `config` nests (a reader of the parsed line sees the headline's mode and the single-step latency beside it: ADVICE r3)
         rec["mode"] = f"throughput: {nstr} independent steps in flight on {nstr} HIP streams" if nstr > 1 else "one step at a time"
         rec["steps_in_flight"] = nstr
-        rec["one_step_ms"] = single["ms_per_step"] if single else rec["ms_per_step"]
-        rec["one_step_value"] = single["value"] if single else rec["value"]
+        if single is not None:
+            rec["one_step_ms"], rec["one_step_value"] = single["ms_per_step"], single["value"]
+        elif nstr == 1:                      # the headline itself runs one step at a time
+            rec["one_step_ms"], rec["one_step_value"] = rec["ms_per_step"], rec["value"]
+        else:                                # steps in flight, and no one-step comparison ran (it comes with --full)
+            rec["one_step_ms"] = rec["one_step_value"] = None
         rec["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(cfg, sd)
-    if world > 1 and not args.no_train_dp:
+    if world > 1 and args.full and not args.no_train_dp:
         # The forward curve is what a multi-GPU run of this command is for: its line goes to stdout BEFORE any training collective starts, and the line with `train_dp`
         # merged in follows as the LAST line.  A rank that fails inside `train_dp` leaves at once with a non-zero code — it never waits in a collective, and the launcher
         # (torch.distributed.run) takes the other ranks down with it; stdout keeps the forward line.  Collectives time out after PL.COLLECTIVE_TIMEOUT_S.
@@ -810,7 +821,7 @@ def main():
     elif rank == 0:
         rec["train_dp"] = None
         rec["secondary"] = None
-        if world == 1 and not args.no_secondary:
+        if world == 1 and args.full and not args.no_secondary:
             del pipe
             torch.cuda.empty_cache()
             rec["secondary"] = run_secondaries(args)

@@ -29,6 +29,14 @@ def test_steps_is_the_number_of_timed_steps_and_at_least_one():
             B.parse_args(bad)
 
 
+def test_full_is_off_by_default_and_keep_profile_needs_it():
+    B = _bench()
+    assert B.parse_args([]).full is False and B.parse_args(["--full"]).full is True
+    assert B.parse_args(["--full", "--keep-profile", "d"]).keep_profile == "d"
+    with pytest.raises(SystemExit):
+        B.parse_args(["--keep-profile", "d"])          # the roofline leg it keeps a file of runs with --full only
+
+
 def _last_step(B_, T2, V1, seed):
     g = torch.Generator().manual_seed(seed)
     lbuf = torch.randn((B_, T2, (V1 + 7) // 8 * 8), generator=g)        # the engine's padded row stride; callers get the (B, T2, V+1) view

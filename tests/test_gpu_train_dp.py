@@ -162,16 +162,16 @@ def test_bench_train_entry_point_both_schedules_identical_weights():
     assert recs[0]["weights_checksum_by_rank"] == recs[1]["weights_checksum_by_rank"], (recs[0]["weights_checksum_by_rank"], recs[1]["weights_checksum_by_rank"])
 
 
-def test_default_bench_command_carries_train_dp_when_it_runs_on_more_than_one_rank():
-    """the command the driver runs for the scaling curve (`bench.py --gpus N`, the forward replica bench) also runs, at N > 1, the config-3 training step
-    under BOTH gradient all-reduce schedules and reports it as `train_dp` — so the first multi-GPU run exercises the gradient all-reduce without a second invocation.  Here:
+def test_full_bench_command_carries_train_dp_when_it_runs_on_more_than_one_rank():
+    """the forward replica bench with --full (`bench.py --gpus N --full`) also runs, at N > 1, the config-3 training step
+    under BOTH gradient all-reduce schedules and reports it as `train_dp` — so one multi-GPU run exercises the gradient all-reduce without a second invocation.  Here:
     two ranks sharing the box's one GPU over gloo, small batches.  The schedules must agree bit for bit (no float atomics in the backward), replicas must be identical."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--streams", "1", "--train-dp-batch", "4", "--train-dp-steps", "2", "--no-kernel-events"], capture_output=True, text=True, timeout=900,
+                        "--streams", "1", "--train-dp-batch", "4", "--train-dp-steps", "2", "--no-kernel-events", "--full"], capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, HFASR_DP_OVERLAP="0"))
     assert r.returncode == 0, r.stderr[-2000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -186,7 +186,7 @@ def test_default_bench_command_carries_train_dp_when_it_runs_on_more_than_one_ra
 
 
 def test_a_rank_failing_in_train_dp_cannot_take_the_forward_line_down():
-    """VERDICT r4 item 5 / ADVICE r4: at more than one rank the forward headline is printed before the training collectives start; a rank that fails inside `train_dp`
+    """VERDICT r4 item 5 / ADVICE r4: with --full at more than one rank the forward headline is printed before the training collectives start; a rank that fails inside `train_dp`
     (here: injected on rank 1 while rank 0 is already inside the first schedule's collectives) exits non-zero at once, the launcher ends the run, and stdout still carries a
     parseable forward line — the run neither hangs until the driver's limit nor loses its headline."""
     import json
@@ -196,7 +196,7 @@ def test_a_rank_failing_in_train_dp_cannot_take_the_forward_line_down():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "2", "--warmup", "1", "--batch", "4",
-                        "--streams", "1", "--train-dp-batch", "4", "--train-dp-steps", "2", "--no-kernel-events"], capture_output=True, text=True, timeout=600,
+                        "--streams", "1", "--train-dp-batch", "4", "--train-dp-steps", "2", "--no-kernel-events", "--full"], capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, HFASR_DP_OVERLAP="0", HFASR_BENCH_FAIL_RANK="1"))
     assert r.returncode != 0
     assert time.time() - t0 < 400

@@ -8,7 +8,7 @@ timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $O/tests.log 2>&1 || {
 tail -1 $O/tests.log
 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-python3 bench.py --keep-profile $O/roof > $O/bench.log 2>&1
+python3 bench.py --full --keep-profile $O/roof > $O/bench.log 2>&1
 tail -1 $O/bench.log > $O/bench_default.json
 python3 -c "import json;d=json.load(open('$O/bench_default.json'));print(d['value'],d['ms_per_step'],d['roofline'],{k:v for k,v in d.items() if k.startswith('one_step')})"
 bash tools/prof_config3.sh > $O/c3.log 2>&1 || true

@@ -8,7 +8,7 @@ if [ -z "$SKIP_TESTS" ]; then
 timeout -k 10 1000 python3 -m pytest tests -x -q -m gpu > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
 fi
-python3 bench.py --keep-profile $O/roof > $O/bench.log 2>&1
+python3 bench.py --full --keep-profile $O/roof > $O/bench.log 2>&1
 tail -1 $O/bench.log > $O/bench_default.json
 python3 -c "import json;d=json.load(open('$O/bench_default.json'));print(d['value'],d['ms_per_step'],d['roofline']['frac'],{k:v for k,v in d.items() if k.startswith('one_step')})"
 rocprofv3 --kernel-trace --output-format csv -d $O/lt -o lt -- python3 bench.py --steps 40 --warmup 8 --no-kernel-events --no-secondary --no-cpu-baseline --no-one-step > $O/lanes_bench.log 2>&1
