@@ -109,6 +109,7 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
     float mv = -INFINITY; int me = 0x7fffffff;
     float mv2 = -INFINITY; int me2 = 0x7fffffff;                       // cached form: the thread's second best (valid while have2), so that a taken best needs no rescan
     bool have2 = true;
+    unsigned alive = 0xffffffffu;                                      // cached form: bit i = candidate tid + 1024 i exists (< N) and is not yet taken
     if (!was_done) {
         if (cached) {
             // Round 5: every load of the pass is requested before the first is used.  Written as `e < N ? cand_value(...) : -inf` each candidate's four loads sat under
@@ -138,9 +139,12 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
                         sc = a + c;
                     }
                     sc = sc + row_bs[beam < W ? beam : 0];
-                    cv[i] = e < N ? sc : -INFINITY;
-                    if (cv[i] > mv) { mv2 = mv; me2 = me; mv = cv[i]; me = e; }           // ascending e: the first of equal values stays (= better())
-                    else if (cv[i] > mv2) { mv2 = cv[i]; me2 = e; }
+                    cv[i] = sc;
+                    // better(): a -inf candidate is still one (ranked by index, as the uncached pass and the pinned loop rank it); past N there is none
+                    if (e < N) {
+                        if (better(sc, e, mv, me)) { mv2 = mv; me2 = me; mv = sc; me = e; }
+                        else if (better(sc, e, mv2, me2)) { mv2 = sc; me2 = e; }
+                    } else alive &= ~(1u << i);
                     beam += qstep; tok += rstep;
                     if (tok >= p.V) { tok -= p.V; ++beam; }
                 }
@@ -152,7 +156,6 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
             }
     }
     if (BEAM_STOP == 1) { if (mv == 12345.f) p.new_tok[0] = me; return; }
-    unsigned alive = 0xffffffffu;                                      // cached form: bit i = candidate tid + 1024 i not yet taken
     for (int r = 0; r < R && !was_done; ++r) {
         const float wm = wave_max(mv);
         const float ecand = (mv == wm && me != 0x7fffffff) ? -(float)me : -INFINITY;      // indices < 2^24: exact in fp32
@@ -175,10 +178,8 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
                 else {
                     mv = -INFINITY; me = 0x7fffffff;
 #pragma unroll
-                    for (int i = 0; i < CPT; ++i) {
-                        const float v = ((alive >> i) & 1u) ? cv[i] : -INFINITY;
-                        if (v > mv) { mv = v; me = tid + i * BS_THREADS; }
-                    }
+                    for (int i = 0; i < CPT; ++i)
+                        if (((alive >> i) & 1u) && better(cv[i], tid + i * BS_THREADS, mv, me)) { mv = cv[i]; me = tid + i * BS_THREADS; }
                 }
             } else {
                 mv = -INFINITY; me = 0x7fffffff;

@@ -23,6 +23,13 @@ from .engine import EBranchformerEngine
 BF16 = torch.bfloat16
 
 
+def _sinusoid_table(n: int, d: int, device) -> torch.Tensor:
+    """rows [0, n) of the fixed sinusoidal positions (reference src/models/embeddings.py:65-90); row i does not depend on n"""
+    inv = 1 / (10000 ** (torch.arange(0.0, d, 2.0) / d))
+    s = torch.outer(torch.arange(n).float(), inv)
+    return torch.cat([s.sin(), s.cos()], -1).to(device).contiguous()
+
+
 class GPT2DecoderEngine:
     def __init__(self, cfg: dict, device="cuda:0"):
         self.cfg = dict(cfg)
@@ -44,10 +51,7 @@ class GPT2DecoderEngine:
         if c.get("pos_emb_fixed", False):
             w["wte"] = f32(sd[prefix + "transformer.wte.emb_layers.0.weight"])
             w["scale"] = float(d) ** 0.5
-            n = c.get("n_positions", 1024)
-            inv = 1 / (10000 ** (torch.arange(0.0, d, 2.0) / d))
-            s = torch.outer(torch.arange(n).float(), inv)
-            w["pos"] = torch.cat([s.sin(), s.cos()], -1).to(dev).contiguous()
+            w["pos"] = _sinusoid_table(c.get("n_positions", 1024), d, dev)
         else:
             w["wte"] = f32(sd[prefix + "transformer.wte.weight"])
             w["scale"] = 1.0
@@ -77,6 +81,20 @@ class GPT2DecoderEngine:
         self._wtable = (C.c_void_p * len(ptrs))(*[t.data_ptr() for t in ptrs])
         self._gcfg = _lib.Gpt2Config(d=d, H=c["n_head"], L=L, V=w["lm_head"].shape[0], eps=float(c.get("layer_norm_epsilon", 1e-5)))
         self._step_ws = None
+
+    def ensure_positions(self, n: int):
+        """Positions [0, n) must have rows in the table the kernels read (they take row `past + u` unchecked).  Fixed sinusoidal positions exist for every position in
+        the reference: the table grows, and the C step's pointer table follows it.  A learned wpe has n_positions rows (the reference fails with an index error past
+        them): refused here, on the host, before any launch."""
+        have = self.w["pos"].shape[0]
+        if n <= have:
+            return
+        if not self.cfg.get("pos_emb_fixed", False):
+            raise ValueError(f"decoding needs {n} positions but the learned position table (wpe) has n_positions = {have} rows")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)        # (rare: once per longer cache) no queued step still reads the old table when it is released
+        self.w["pos"] = _sinusoid_table(n, self.cfg["n_embd"], self.device)
+        self._wtable[1] = self.w["pos"].data_ptr()
 
     # ------------------------------------------------------------------ building blocks
     def cross_kv(self, enc_bf16: torch.Tensor):
@@ -123,6 +141,7 @@ class GPT2DecoderEngine:
         c, w = self.cfg, self.w
         B, U = ids.shape
         d, L, eps = c["n_embd"], c["n_layer"], c.get("layer_norm_epsilon", 1e-5)
+        self.ensure_positions(U)
         x = ops.embed_tokens(ids, w["wte"], w["pos"], scale=w["scale"])
         kvs = self.cross_kv(enc_bf16)
         locs = list(c.get("head_locations") or [])
@@ -150,6 +169,8 @@ class GPT2DecoderEngine:
     def init_cache(self, B: int, Lmax: int):
         """KV cache: two sets of (B, Lmax, d) tensors per layer (beam re-ordering copies set A -> set B in one kernel and swaps)."""
         d, L = self.cfg["n_embd"], self.cfg["n_layer"]
+        if self.cfg.get("pos_emb_fixed", False):
+            self.ensure_positions(Lmax)
         # one allocation and one fill for all 4 L tensors.  Zero, not empty: the MFMA attention kernel stages whole 32-key tiles, and a V row past the last key meets a
         # probability of exactly 0 — which only gives 0 if the row holds finite numbers
         buf = torch.zeros((4, L, B, Lmax, d), device=self.device, dtype=BF16)
@@ -180,6 +201,7 @@ class GPT2DecoderEngine:
         ids_new = ids_new.contiguous()
         B, U = ids_new.shape
         past, Lmax = cache["past"], cache["Lmax"]
+        self.ensure_positions(past + U)
         L_ = _lib.lib()
         nbytes = L_.mi_gpt2_step_workspace_bytes(C.byref(self._gcfg), B, U)
         if self._step_ws is None or self._step_ws.numel() < nbytes:
@@ -202,6 +224,7 @@ class GPT2DecoderEngine:
         B, U = ids_new.shape
         d, L, eps = c["n_embd"], c["n_layer"], c.get("layer_norm_epsilon", 1e-5)
         past, Lmax = cache["past"], cache["Lmax"]
+        self.ensure_positions(past + U)
         x = ops.embed_tokens(ids_new, w["wte"], w["pos"], scale=w["scale"], pos_offset=past)
         for l in range(L):
             x = self._block(l, x, B, U, kvs[l], T_enc, enc_len, cache["k"][l], cache["v"][l], past, Lmax)
@@ -282,11 +305,22 @@ def _step_denoms(cur_len, max_length, length_penalty, early_stopping):
     return float(np.float32(cur_len ** length_penalty)), float(np.float32(hyp ** length_penalty))
 
 
-def _check_generate_args(num_beams, max_length, early_stopping):
+def _stop_rule(num_beams, cur_len, max_length, length_penalty, early_stopping):
+    """(closing denominator, early-stop denominator, early-stop mode) of a step.  One beam is transformers' greedy loop, which the reference runs for num_beams = 1: it
+    stops at the first EOS whatever `early_stopping` and `length_penalty` say.  The beam rules give that with mode False and the early-stop denominator equal to the
+    closing one (the running beam, ranked behind the EOS candidate, cannot beat it); "never" with a positive penalty would keep the runner-up alive."""
+    denom, heur = _step_denoms(cur_len, max_length, length_penalty, early_stopping)
+    if num_beams == 1:
+        return denom, denom, 0
+    return denom, heur, _ES_MODE[early_stopping]
+
+
+def _check_generate_args(joint, num_beams, max_length, early_stopping):
     if early_stopping not in _ES_MODE:
         raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
     if num_beams < 1 or max_length < 2:
         raise ValueError(f"num_beams >= 1 and max_length >= 2 required, got {num_beams}, {max_length}")
+    joint.dec.ensure_positions(max_length - 1)           # the last step feeds position max_length - 2: a learned table too short is refused before decoding starts
 
 
 def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_length=64, ctc_weight=0.3, length_penalty=1.0, early_stopping=False,
@@ -300,7 +334,7 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
     (same arithmetic, operation for operation).  `stats` (a dict) receives the host time spent enqueuing the token loop and the number of steps enqueued; `trace` (a list)
     receives per step the (B, 2W) candidate values and indices the kernel walked and the (B) done flags before the step (device tensors)."""
     from .decoding import CTCRescorerLogitsProcessor
-    _check_generate_args(num_beams, max_length, early_stopping)
+    _check_generate_args(joint, num_beams, max_length, early_stopping)
     dev = joint.device
     c = joint.jcfg
     pad = c["pad_token_id"] if pad_token_id is None else pad_token_id
@@ -352,7 +386,6 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
     ev_ids.record(main)
     cur_len, steps = 1, 0
     w_att, w_ctc = float(1 - ctc_weight), float(ctc_weight)
-    es_mode = _ES_MODE[early_stopping]
     t_loop = time.perf_counter()
     while cur_len < max_length:
         if len(flags) >= run_ahead:            # bounded run-ahead: wait for the flags of step (now - run_ahead) and stop if everything is done
@@ -378,7 +411,7 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
         if trace is not None:
             top_s, top_i = torch.empty((B, 2 * W), device=dev), torch.empty((B, 2 * W), dtype=torch.int32, device=dev)
             trace.append((top_s, top_i, done.clone()))          # the done flags BEFORE the step
-        denom, heur = _step_denoms(cur_len, max_length, length_penalty, early_stopping)
+        denom, heur, es_mode = _stop_rule(W, cur_len, max_length, length_penalty, early_stopping)
         _lib.check(L_.mi_beam_step(logits.data_ptr(), logits.stride(0), lse.data_ptr(), ctc.data_ptr() if ctc is not None else None, w_att, w_ctc, int(proc is not None), pad,
                                    eos_token_id, B, W, V, cur_len, max_length, Lmax, denom, heur, es_mode, ids.data_ptr(), beam_scores.data_ptr(), new_tok.data_ptr(),
                                    beam_idx.data_ptr(), done.data_ptr(), nfin.data_ptr(), fin_score.data_ptr(), fin_len.data_ptr(), fin_tok.data_ptr(),
@@ -411,7 +444,7 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
     the route of the eos / space trick (the processor applies it, ctc_scorer.py:333-349)."""
     import numpy as np
     from .decoding import CTCRescorerLogitsProcessor
-    _check_generate_args(num_beams, max_length, early_stopping)
+    _check_generate_args(joint, num_beams, max_length, early_stopping)
     dev = joint.device
     c = joint.jcfg
     pad = c["pad_token_id"] if pad_token_id is None else pad_token_id
@@ -448,7 +481,8 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
         top_s, top_i = top_s.cpu().numpy(), top_i.cpu().numpy()
         cur_len = ids.shape[1]
         at_max = cur_len + 1 >= max_length
-        denom, heur = (np.float32(v) for v in _step_denoms(cur_len, max_length, length_penalty, early_stopping))
+        denom, heur, es_mode = _stop_rule(W, cur_len, max_length, length_penalty, early_stopping)
+        denom, heur = np.float32(denom), np.float32(heur)
         nb_scores = torch.zeros((B, W)); nb_tok = torch.zeros((B, W), dtype=torch.long); nb_idx = torch.zeros((B, W), dtype=torch.long)
         ids_cpu = ids.cpu()
         for b in range(B):
@@ -473,7 +507,7 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
                         del kept[b][W:]
             best = np.float32(nxt[0][0] / heur)
             unsat = best > (kept[b][W - 1][0] if len(kept[b]) == W else NEG)
-            if (not unsat) or (early_stopping is True and len(kept[b]) == W) or at_max:
+            if (not unsat) or (es_mode == 1 and len(kept[b]) == W) or at_max:
                 done[b] = True
         beam_idx = nb_idx.view(-1).to(dev)
         new_tok = nb_tok.view(-1, 1).to(dev)

@@ -77,3 +77,32 @@ def test_generate_refuses_what_it_does_not_implement():
         m.generate(input_values=x, num_beams=5)
     with pytest.raises(RuntimeError, match="GPU"):                # a valid request reaches the device check: no CPU fallback
         m.generate(input_values=x, attention_mask=torch.ones(1, 200, dtype=torch.long), labels=torch.zeros(1, 3, dtype=torch.long), output_hidden_states=True)
+
+
+def greedy_stop_case():
+    """gen_tiny with an end-of-sequence id taken from the greedy path (its 3rd generated token): greedy stops there, while the beam loop with one beam,
+    early_stopping "never" and length_penalty 1.6 keeps the runner-up alive and returns another sequence.  -> (case inputs, eos, max_length)"""
+    case = gen_case_inputs("gen_tiny")
+    g, sd, x, am, dec_cfg = case
+    fn, B = G.joint_score_fn(sd, ENC, dec_cfg, AED_JCFG, x, am, 1, 0.3)
+    free = G.greedy(fn, B, max_length=14, eos=GM.EOS, pad=GM.PAD, start=GM.START)
+    return case, int(free[0, 3]), 14
+
+
+def test_greedy_ignores_the_beam_stop_rules():
+    """transformers decodes num_beams = 1 with its greedy loop, which stops a row at its first EOS whatever `early_stopping` and `length_penalty` say.  The beam loop
+    with one beam, early_stopping "never" and a positive penalty does not: its early-stop rule divides the running beam's score by (max_length - 1) ** 1.6 and keeps it
+    alive after EOS has won.  This setting tells the two rules apart, which is what gives tests/test_gpu_generate.py's greedy check its teeth; and the oracle's greedy
+    loop is the reference's (the fixture's greedy rows)."""
+    torch.set_num_threads(8)
+    (g, sd, x, am, dec_cfg), eos, ml = greedy_stop_case()
+    fn, B = G.joint_score_fn(sd, ENC, dec_cfg, AED_JCFG, x, am, 1, 0.3)
+    assert (G.greedy(fn, B, max_length=ml, eos=GM.EOS, pad=GM.PAD, start=GM.START) == g[GM.setting_key(1, 1.0, False, ml) + "/sequences"]).all()
+    fn, B = G.joint_score_fn(sd, ENC, dec_cfg, AED_JCFG, x, am, 1, 0.3)           # (the CTC prefix scorer keeps state: a fresh score function per decode)
+    greedy = G.greedy(fn, B, max_length=ml, eos=eos, pad=GM.PAD, start=GM.START)
+    assert (greedy[:, -1] == eos).all() and greedy.shape[1] < ml              # every row stops at the chosen EOS
+    fn, B = G.joint_score_fn(sd, ENC, dec_cfg, AED_JCFG, x, am, 1, 0.3)
+    never, _ = G.beam_search(fn, B, 1, GM.V, max_length=ml, eos=eos, pad=GM.PAD, start=GM.START, length_penalty=1.6, early_stopping="never")
+    L = max(greedy.shape[1], never.shape[1])
+    pad_to = lambda a: np.pad(a, ((0, 0), (0, L - a.shape[1])), constant_values=GM.PAD)
+    assert (pad_to(greedy) != pad_to(never)).any(1).all(), (greedy, never)

@@ -162,3 +162,28 @@ def test_fused_token_step_against_the_launch_per_op_step(W):
             fa, fb = ca[t][l][:, :20].float(), cb[t][l][:, :20].float()
             assert float((fa - fb).abs().max()) <= 0.02 * float(fb.abs().max()) and float((fa - fb).abs().mean()) < 1e-3 * float(fb.abs().max())     # last-bit flips of bf16 values (deeper layers: more of them)
     print(f"fused vs launch-per-op token step, W = {W}: max |dlogit| over 20 steps {worst:.2e}")
+
+
+def test_beam10_at_the_recipes_evaluation_setting():
+    """The reference's evaluation recipes decode with `ctc_weight=0.3;num_beams=10` (e.g. recipes_v0.0.1/voxpopuli/train_small_base_lumi.sh:120).  W = 10 at config-5
+    size reaches two paths no W <= 8 decode does: the general token-step path (B * W > 8 rows: MFMA GEMMs, mi_attention_qkv_bf16 against the cache) and the uncached
+    candidate pass of csrc/beam_step.hip (W * V > 32 Ki).  max_length 60, an end-of-sequence id chosen among the structured decoder's second-best successors as in the
+    43-step test above, held by the same certification (exact bookkeeping, candidate values within tol, tokens equal up to a certified near tie); and the
+    device-resident loop must equal the host loop hypothesis for hypothesis."""
+    from test_gpu_generate import certified_decode
+    from huggingface_asr_amd.decoder import generate, generate_stepwise
+    torch.set_num_threads(8)
+    W, ml = 10, 60
+    assert 1 * W > 8 and W * M.V > 32 * 1024
+    sd = M.state_dict(8, structured=True)
+    x, am = _inputs()
+    eng = _engine(sd)
+    fl = am.sum(-1).to(DEV, torch.int32)
+    greedy = generate(eng, x.to(DEV), fl, num_beams=1, max_length=ml, ctc_weight=0.3, eos_token_id=10 ** 6)[0]["tokens"]
+    assert len(greedy) == ml
+    eos = M.successors(greedy[18])[1]
+    got, _, diverged, worst = certified_decode(eng, sd, M.ENC_CFG, M.DEC_CFG, M.JCFG, x, am, W, 1.0, False, ml, eos, ref_q=A.E.bf16_round, tol=0.06)
+    lens = [len(t) for _, t in got[0]["hypotheses"]]
+    print("config 5, W = 10, max_length 60: kept lengths", lens, "worst candidate-value gap", worst, "diverged at a near tie:", diverged)
+    want = generate_stepwise(eng, x.to(DEV), fl, num_beams=W, max_length=ml, ctc_weight=0.3, eos_token_id=eos)
+    assert got[0]["hypotheses"] == want[0]["hypotheses"]

@@ -223,3 +223,35 @@ def test_eos_space_trick_reaches_generate():
     seq, sc = G.beam_search(fn, B, 3, GM.V, max_length=10, eos=GM.EOS, pad=GM.PAD, start=GM.START)
     for u in range(B):
         assert abs(a[u]["score"] - float(sc[u * 3])) < 0.05
+
+
+def test_one_beam_is_greedy_whatever_the_stop_settings():
+    """num_beams = 1 is transformers' greedy loop in the reference: the first EOS stops, whatever `early_stopping` and `length_penalty` say.  Both HIP loops (the
+    device-resident one and the host loop) and the model's generate() must give the oracle greedy loop's tokens for every setting, on a case where the beam rules with
+    early_stopping "never" and length_penalty 1.6 return another sequence (tests/test_generate_cpu.py asserts that this case tells the rules apart)."""
+    from test_generate_cpu import greedy_stop_case
+    from test_surface_cpu import _joint_model
+    from huggingface_asr_amd.decoder import generate, generate_stepwise
+    from huggingface_asr_amd.decoding import GenerationConfigCustom
+    torch.set_num_threads(8)
+    (g, sd, x, am, dec_cfg), eos, ml = greedy_stop_case()
+    fn, B = G.joint_score_fn(sd, ENC, dec_cfg, AED_JCFG, x, am, 1, 0.3)
+    want = G.greedy(fn, B, max_length=ml, eos=eos, pad=GM.PAD, start=GM.START)
+    eng = _engine(sd, dec_cfg)
+    fl = am.sum(-1).to(DEV, torch.int32)
+    for es in (False, True, "never"):
+        for lp in (1.0, 1.6):
+            for fn_ in (generate, generate_stepwise):
+                got = fn_(eng, x.to(DEV), fl, num_beams=1, max_length=ml, ctc_weight=0.3, length_penalty=lp, early_stopping=es, eos_token_id=eos)
+                for b in range(B):
+                    toks = got[b]["tokens"]
+                    assert toks == want[b, : len(toks)].tolist() and (want[b, len(toks):] == GM.PAD).all(), (fn_.__name__, es, lp, b, toks, want[b])
+    model = _joint_model(False)
+    missing, unexpected = model.load_state_dict(sd, strict=False)
+    assert not missing and not unexpected
+    model = model.to(DEV).eval()
+    model.generation_config = GenerationConfigCustom(bos_token_id=GM.START, pad_token_id=GM.PAD, decoder_start_token_id=GM.START, eos_token_id=eos, max_length=ml,
+                                                     num_beams=1, ctc_weight=0.3, ctc_margin=0, lm_weight=0, lm_model=None, space_token_id=-1, apply_eos_space_trick=False,
+                                                     eos_space_trick_weight=1.0)
+    out = model.generate(input_values=x.to(DEV), attention_mask=am.to(DEV), num_beams=1, early_stopping="never", length_penalty=1.6)
+    assert out.cpu().numpy().tolist() == want.tolist(), (out, want)
