@@ -3,6 +3,7 @@ import os
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from huggingface_asr_amd import shapes, synth
 
@@ -32,6 +33,42 @@ def synth_labels(seed, B, U, vocab, tgt_lens):
     for b, n in enumerate(tgt_lens):
         lab[b, n:] = -100
     return torch.from_numpy(lab)
+
+
+def compare_grads(grads, ref, rel=0.03, cos_min=0.999):
+    """every gradient tensor of `ref` (reference names) against `grads`: relative L2 error <= rel and cosine >= cos_min; tensors whose reference is
+    (near) zero only against the largest gradient.  Returns the worst (relative error, cosine, name)."""
+    worst = []
+    gmax = max(float(torch.as_tensor(v).float().norm()) for v in ref.values())
+    for k, want in ref.items():
+        got = grads[k].float().cpu().reshape(-1)
+        want = torch.as_tensor(want).float().reshape(-1)
+        assert got.shape == want.shape, k
+        nw = float(want.norm())
+        err = float((got - want).norm())
+        cos = float(F.cosine_similarity(got, want, dim=0)) if nw > 0 else 1.0
+        if nw < 1e-5:          # mathematically zero gradients (key bias under softmax): only bf16 noise on our side, fp32 noise in the fixture
+            assert err < 1e-3 * gmax, (k, err, gmax)
+            continue
+        worst.append((err / nw, cos, k))
+    worst.sort(reverse=True)
+    bad = [(e, c, k) for e, c, k in worst if e > rel or c < cos_min]
+    assert not bad, f"{len(bad)} gradient tensors off; worst: {bad[:6]}"
+    return worst[0]
+
+
+def oracle_ctc_grads(cfg, sd, x, am, lab, skip_layers=()):
+    """loss and parameter gradients (reference names) of the encoder + CTC head by torch autograd of the CPU oracle"""
+    from oracle import ebranchformer_ref as R
+    sdr = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    hidden = R.encoder_forward(sdr, cfg, x, am, skip_layers=skip_layers)
+    logits = R.ctc_head(sdr, hidden)
+    in_len = R.conv_out_lengths_outer(am.sum(-1), cfg).long()
+    tl = (lab >= 0).sum(-1)
+    loss = F.ctc_loss(torch.log_softmax(logits, -1).transpose(0, 1), lab[lab >= 0], in_len, tl, blank=logits.shape[-1] - 1,
+                      reduction=cfg.get("ctc_loss_reduction", "mean"), zero_infinity=True)
+    loss.backward()
+    return float(loss.detach()), {k: v.grad for k, v in sdr.items() if v.grad is not None}
 
 
 def case_inputs(g, cfg):

@@ -13,6 +13,8 @@ import torch
 import torch.nn.functional as F
 
 from helpers import case_inputs, load_golden
+from helpers import compare_grads as _compare
+from helpers import oracle_ctc_grads as _oracle_grads
 from huggingface_asr_amd import shapes
 from oracle import ebranchformer_ref as R
 
@@ -27,26 +29,6 @@ def _trainer(cfg, sd, **kw):
     tr = EncoderCTCTrainer(dict(cfg, **NO_DROPOUT), DEV, **kw)
     tr.load_state_dict(sd)
     return tr
-
-
-def _compare(grads, ref, rel=0.03, cos_min=0.999):
-    worst = []
-    gmax = max(float(torch.as_tensor(v).float().norm()) for v in ref.values())
-    for k, want in ref.items():
-        got = grads[k].float().cpu().reshape(-1)
-        want = torch.as_tensor(want).float().reshape(-1)
-        assert got.shape == want.shape, k
-        nw = float(want.norm())
-        err = float((got - want).norm())
-        cos = float(F.cosine_similarity(got, want, dim=0)) if nw > 0 else 1.0
-        if nw < 1e-5:          # mathematically zero gradients (key bias under softmax): only bf16 noise on our side, fp32 noise in the fixture
-            assert err < 1e-3 * gmax, (k, err, gmax)
-            continue
-        worst.append((err / nw, cos, k))
-    worst.sort(reverse=True)
-    bad = [(e, c, k) for e, c, k in worst if e > rel or c < cos_min]
-    assert not bad, f"{len(bad)} gradient tensors off; worst: {bad[:6]}"
-    return worst[0]
 
 
 @pytest.mark.parametrize("name,extra", [("grads_tiny_rel", {}), ("grads_tiny_rotary", {"position_embeddings_type": "rotary"}),
@@ -327,18 +309,6 @@ def test_finetune_head_trains_and_layerdrop_keeps_the_mix_consistent():
     tr.set_frozen(())                                   # thawing restores decay and updates
     tr.train_step(x.to(DEV), am.sum(-1).to(DEV), lab.to(DEV))
     assert not torch.equal(tr.state_dict()["wav2vec2.encoder.layers.0.merge_proj.weight"].cpu(), sd["wav2vec2.encoder.layers.0.merge_proj.weight"])
-
-
-def _oracle_grads(cfg, sd, x, am, lab, skip_layers=()):
-    sdr = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
-    hidden = R.encoder_forward(sdr, cfg, x, am, skip_layers=skip_layers)
-    logits = R.ctc_head(sdr, hidden)
-    in_len = R.conv_out_lengths_outer(am.sum(-1), cfg).long()
-    tl = (lab >= 0).sum(-1)
-    loss = F.ctc_loss(torch.log_softmax(logits, -1).transpose(0, 1), lab[lab >= 0], in_len, tl, blank=logits.shape[-1] - 1,
-                      reduction=cfg.get("ctc_loss_reduction", "mean"), zero_infinity=True)
-    loss.backward()
-    return float(loss.detach()), {k: v.grad for k, v in sdr.items() if v.grad is not None}
 
 
 def test_gradients_match_oracle_autograd_head64():

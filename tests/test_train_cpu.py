@@ -137,3 +137,34 @@ def test_decoder_layout_roundtrips_reference_names():
         for k, v in sd.items():
             assert torch.equal(covered[k], v), k
         assert store.specs["h0.wqkv"].shape == (3 * d, d) and store.specs["h0.wpr"].shape == (d, 4 * d)
+
+
+def test_dbd_static_buffers_are_a_three_entry_lru_of_zero_filled_buffers():
+    """ops_train._dbd_static (the sparse-writes attention backward's dBD buffers) on the host: at most three shapes are held, a shape in use returns the same
+    storage, the least recently used goes first, and a buffer made again after its eviction is all zeros.  (Host memory of this size comes from fresh pages, which
+    read as zero anyway: a `torch.empty` in place of the zero fill passes here and is caught by tests/test_gpu_train_shapes.py, where freed memory holds NaN bits.)"""
+    from huggingface_asr_amd import ops_train as OT
+    saved = dict(OT._DBD_CACHE)
+    OT.release_static_buffers()
+    try:
+        cpu = torch.device("cpu")
+        a = OT._dbd_static(cpu, 4, 2, 25, 64)
+        assert a.shape == (4, 2, 25, 64) and a.dtype == torch.bfloat16 and not bool(a.any())
+        b = OT._dbd_static(cpu, 4, 3, 75, 160)
+        c = OT._dbd_static(cpu, 4, 2, 128, 288)
+        a.fill_(1.0); b.fill_(2.0)                                  # what a launch leaves behind
+        assert OT._dbd_static(cpu, 4, 2, 25, 64).data_ptr() == a.data_ptr()     # a is now the most recently used: b is the oldest
+        assert len(OT._DBD_CACHE) == 3
+        OT._dbd_static(cpu, 4, 2, 129, 288)                         # a fourth shape evicts b
+        assert len(OT._DBD_CACHE) == 3
+        assert [k[1:] for k in OT._DBD_CACHE] == [(4, 2, 128, 288), (4, 2, 25, 64), (4, 2, 129, 288)]
+        assert OT._dbd_static(cpu, 4, 2, 128, 288).data_ptr() == c.data_ptr()
+        assert OT._dbd_static(cpu, 4, 2, 25, 64).data_ptr() == a.data_ptr() and bool((a == 1.0).all())    # kept buffers are not cleared
+        b2 = OT._dbd_static(cpu, 4, 3, 75, 160)                     # b again: made anew, all zeros; the oldest (129) went
+        assert b2.shape == b.shape and not bool(b2.any()) and b2.data_ptr() != b.data_ptr()
+        assert [k[1:] for k in OT._DBD_CACHE] == [(4, 2, 128, 288), (4, 2, 25, 64), (4, 3, 75, 160)]
+        OT._dbd_static(torch.device("meta"), 4, 2, 25, 64)          # the device is part of the key
+        assert [k[1:] for k in OT._DBD_CACHE] == [(4, 2, 25, 64), (4, 3, 75, 160), (4, 2, 25, 64)] and len({k[0] for k in OT._DBD_CACHE}) == 2
+    finally:
+        OT.release_static_buffers()
+        OT._DBD_CACHE.update(saved)
