@@ -377,15 +377,16 @@ def embed_tokens(ids, wte, pos, *, scale=1.0, pos_offset=0, U=None):
     return out
 
 
-def ce_label_smoothing(logits, labels, *, shift=1, eps=0.0):
-    """mean over valid targets of the label-smoothed CE of logits[b,u] vs labels[b,u+shift] (ignore < 0). logits (B,U,V) fp32."""
+def ce_label_smoothing(logits, labels, *, shift=1, eps=0.0, return_acc=False):
+    """mean over valid targets of the label-smoothed CE of logits[b,u] vs labels[b,u+shift] (ignore < 0). logits (B,U,V) fp32.
+    return_acc: hand back the kernel's [sum, count] pair instead, undivided — what `ops_train.ce_label_smoothing_bwd` reads, and what a caller that wants the sum needs."""
     B, U, V = logits.shape
     labels = labels.contiguous()
     acc = torch.zeros((2,), device=logits.device, dtype=torch.float32)
     rows = torch.empty((B * (U - shift),), device=logits.device, dtype=torch.float32)       # per-row losses; summed by one block in a fixed order
     rc = _lib.lib().mi_ce_label_smoothing(logits.data_ptr(), logits.stride(1), labels.data_ptr(), B, U, shift, V, float(eps), acc.data_ptr(), rows.data_ptr(), _stream())
     _lib.check(rc, "mi_ce_label_smoothing")
-    return acc[0] / acc[1]
+    return acc if return_acc else acc[0] / acc[1]
 
 
 def cast_bf16(x):

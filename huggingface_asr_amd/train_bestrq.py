@@ -92,10 +92,7 @@ class BestRQTrainer(StoreTrainer):
                 ops.gemm(hb, W(f"cls{k}_w"), P(f"cls{k}_b"), out=buf.view(M, Cp))
                 lg = buf[..., :self.C]
                 lab = tg[:, k].contiguous()
-                acc = torch.zeros((2,), device=dev, dtype=F32)
-                rows = torch.empty((B * T2,), device=dev, dtype=F32)
-                _lib.check(_lib.lib().mi_ce_label_smoothing(lg.data_ptr(), lg.stride(1), lab.data_ptr(), B, T2, 0, self.C, 0.0, acc.data_ptr(), rows.data_ptr(),
-                                                            torch.cuda.current_stream().cuda_stream), "mi_ce_label_smoothing")
+                acc = ops.ce_label_smoothing(lg, lab, shift=0, eps=0.0, return_acc=True)
                 lk = acc[0] / self.nb                           # reduction="sum", then / num_books (bestrq.py:141-142)
                 loss = lk if loss is None else loss + lk
                 logits.append(lg)

@@ -1,10 +1,12 @@
 """Shared helpers for the parity tests: rebuild the seeded inputs the golden fixtures were made from."""
+import math
 import os
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
+from huggingface_asr_amd import ops_train as OT
 from huggingface_asr_amd import shapes, synth
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -162,3 +164,46 @@ def gen_case_inputs(name):
     B, T = [int(v) for v in g["shape"]]
     x, am = synth_feats(seed, B, T, lengths)
     return g, sd, x, am, dict(TINY_DEC, pos_emb_fixed=fixed)
+
+
+# ---- the decoder attention with materialised scores: what huggingface_asr_amd.train_aed.attention_bwd_fused and ops_train.attention_x_lse are compared against
+def _scores(q, k, B, Tq, Tk, H, hd):
+    Ts = OT.pad8(Tk)
+    ac = torch.empty((H, B, Tq, Ts), device=q.device, dtype=torch.float32)
+    OT.bgemm(q, (hd, Tq * q.stride(0), q.stride(0), 1), k, (hd, Tk * k.stride(0), k.stride(0), 1), ac, (B * Tq * Ts, Tq * Ts, Ts), H, B, Tq, Tk, hd)
+    return ac, Ts
+
+
+def attention_fwd_plain(q, k, v, B, Tq, Tk, H, *, lengths=None, causal=False, drop=None):
+    """Materialised attention forward (batched GEMM, generic soft-max, batched GEMM), the comparison for the fused kernels: -> (ctx (B*Tq, d) bf16, prob, prob_dropped)."""
+    d = q.shape[1]
+    hd = d // H
+    ac, Ts = _scores(q, k, B, Tq, Tk, H, hd)
+    r = OT.attn_softmax_fwd(ac, None, lengths, H, B, Tq, Tk, 1.0 / math.sqrt(hd), causal, drop=drop)
+    prob, pdrop = r if drop else (r, r)                    # (without dropout the op returns the probabilities alone)
+    ctx = torch.empty((B * Tq, d), device=q.device, dtype=torch.bfloat16)
+    OT.bgemm(pdrop, (B * Tq * Ts, Tq * Ts, Ts, 1), v, (hd, Tk * v.stride(0), 1, v.stride(0)), ctx, (hd, Tq * d, d), H, B, Tq, hd, Tk)
+    return ctx, prob, pdrop
+
+
+def attention_bwd_plain(q, k, v, dctx, dq, dk, dv, B, Tq, Tk, H, *, lengths=None, causal=False, drop=None, saved=None):
+    """Backward of ctx = dropout(softmax(q k^T / sqrt(hd) + mask)) v per (utterance, head); all operands are (rows, >= d) bf16 row
+    views with head h at columns [h*hd, (h+1)*hd).  Probabilities are recomputed (saved = None) or passed in as
+    saved = (prob, prob_dropped) from attention_fwd_plain."""
+    d = dctx.shape[1]
+    hd = d // H
+    scale = 1.0 / math.sqrt(hd)
+    sq, sk, sv = q.stride(0), k.stride(0), v.stride(0)
+    ac, Ts = _scores(q, k, B, Tq, Tk, H, hd)
+    sS = (B * Tq * Ts, Tq * Ts)
+    if saved is None:
+        prob = pdrop = OT.attn_softmax_fwd(ac, None, lengths, H, B, Tq, Tk, scale, causal)
+    else:
+        prob, pdrop = saved
+    dp = ac                                                # reuse the fp32 buffer
+    sd_ = dctx.stride(0)
+    OT.bgemm(dctx, (hd, Tq * sd_, sd_, 1), v, (hd, Tk * sv, sv, 1), dp, (*sS, Ts), H, B, Tq, Tk, hd)
+    ds, _ = OT.attn_softmax_bwd(prob, dp, H, B, Tq, Tk, scale, drop=drop)
+    OT.bgemm(pdrop, (*sS, 1, Ts), dctx, (hd, Tq * sd_, 1, sd_), dv, (hd, Tk * dv.stride(0), dv.stride(0)), H, B, Tk, hd, Tq)
+    OT.bgemm(ds, (*sS, 1, Ts), q, (hd, Tq * sq, 1, sq), dk, (hd, Tk * dk.stride(0), dk.stride(0)), H, B, Tk, hd, Tq)
+    OT.bgemm(ds, (*sS, Ts, 1), k, (hd, Tk * sk, 1, sk), dq, (hd, Tq * dq.stride(0), dq.stride(0)), H, B, Tq, hd, Tk)
