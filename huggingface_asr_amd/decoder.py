@@ -19,6 +19,7 @@ import torch
 
 from . import _lib, ops
 from .engine import EBranchformerEngine
+from .packing import _dec_map, decoder_specs, mapped_fp32, packed
 
 BF16 = torch.bfloat16
 
@@ -43,35 +44,18 @@ class GPT2DecoderEngine:
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd: dict, prefix: str = "decoder."):
+        """every packed parameter of packing.decoder_specs (Conv1D weights transposed to (out, in) there), matrices in bf16, the rest in fp32"""
         c, dev = self.cfg, self.device
         d, L = c["n_embd"], c["n_layer"]
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        lin = lambda t: t.detach().to(dev, torch.float32).t().to(BF16).contiguous()      # Conv1D (in,out) -> (out,in) bf16
-        w = {"layers": []}
-        if c.get("pos_emb_fixed", False):
-            w["wte"] = f32(sd[prefix + "transformer.wte.emb_layers.0.weight"])
-            w["scale"] = float(d) ** 0.5
-            w["pos"] = _sinusoid_table(c.get("n_positions", 1024), d, dev)
-        else:
-            w["wte"] = f32(sd[prefix + "transformer.wte.weight"])
-            w["scale"] = 1.0
-            w["pos"] = f32(sd[prefix + "transformer.wpe.weight"])
-        for l in range(L):
-            p = f"{prefix}transformer.h.{l}."
-            g = lambda n: f32(sd[p + n])
-            w["layers"].append(dict(
-                ln1=(g("ln_1.weight"), g("ln_1.bias")), wqkv=lin(sd[p + "attn.c_attn.weight"]), bqkv=g("attn.c_attn.bias"),
-                wo=lin(sd[p + "attn.c_proj.weight"]), bo=g("attn.c_proj.bias"),
-                lnc=(g("ln_cross_attn.weight"), g("ln_cross_attn.bias")),
-                wq=lin(sd[p + "crossattention.q_attn.weight"]), bq=g("crossattention.q_attn.bias"),
-                wkv=lin(sd[p + "crossattention.c_attn.weight"]), bkv=g("crossattention.c_attn.bias"),
-                wco=lin(sd[p + "crossattention.c_proj.weight"]), bco=g("crossattention.c_proj.bias"),
-                ln2=(g("ln_2.weight"), g("ln_2.bias")), wfc=lin(sd[p + "mlp.c_fc.weight"]), bfc=g("mlp.c_fc.bias"),
-                wpr=lin(sd[p + "mlp.c_proj.weight"]), bpr=g("mlp.c_proj.bias")))
-        w["lnf"] = (f32(sd[prefix + "transformer.ln_f.weight"]), f32(sd[prefix + "transformer.ln_f.bias"]))
-        w["heads"] = [sd[f"{prefix}additional_lm_heads.{k}.weight"].detach().to(dev, torch.float32).to(BF16).contiguous()
-                      for k in range(len(c.get("head_locations") or []))]
-        w["lm_head"] = sd[prefix + "lm_head.weight"].detach().to(dev, torch.float32).to(BF16).contiguous()
+        m = _dec_map(c, False, prefix)
+        P = {s.name: (t.to(BF16) if s.mat and s.name != "wte" else t).contiguous()          # wte stays fp32: the embedding gather reads it
+             for s, t in packed(decoder_specs(c, d, False), m, mapped_fp32(m, sd, dev))}
+        fixed = c.get("pos_emb_fixed", False)
+        w = dict(wte=P["wte"], scale=float(d) ** 0.5 if fixed else 1.0, pos=_sinusoid_table(c.get("n_positions", 1024), d, dev) if fixed else P["wpe"],
+                 lnf=(P["lnf_g"], P["lnf_b"]), heads=[P[f"head{k}"] for k in range(len(c.get("head_locations") or []))],
+                 lm_head=P["lm_head"] if "lm_head" in P else P["wte"].to(BF16))               # tied: the token embedding is the head
+        w["layers"] = [dict({n: P[f"h{l}.{n}"] for n in ("wqkv", "bqkv", "wo", "bo", "wq", "bq", "wkv", "bkv", "wco", "bco", "wfc", "bfc", "wpr", "bpr")},
+                            **{n: (P[f"h{l}.{n}_g"], P[f"h{l}.{n}_b"]) for n in ("ln1", "lnc", "ln2")}) for l in range(L)]
         self.w = w
         # pointer table of mi_gpt2_step (csrc/decoder_step.hip): 5 globals, then 18 per layer
         ptrs = [w["wte"], w["pos"], w["lnf"][0], w["lnf"][1], w["lm_head"]]

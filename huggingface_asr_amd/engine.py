@@ -1,23 +1,20 @@
 """Host driver of the HIP encoder: packs weights into the slot table of `mi_ebf_forward`, owns the
 workspace / position tables, and launches the whole-encoder C call on the current stream.
 
-Weight packing mirrors the reference state dict (huggingface_asr_amd/shapes.py) into the layouts the
-kernels want: bf16 (N,K) row-major matrices (nn.Linear layout IS K-contiguous, which is what the MFMA
-tiles read), Q/K concatenated, lm_head ⊕ blank_projection concatenated with blank LAST
-(e_branchformer.py:456-457), conv2 weight re-ordered to (Cout, kh, kw, Cin), and the columns of the
-conv-out Linear permuted from the reference's (c, f) flattening (extractors.py:112) to our channels-last
-(f, c) activation layout.
+The packed layouts themselves (and the reference state-dict names they come from) are defined once, in
+packing.py, for this engine and the trainers alike; `load_state_dict` casts them into the slot table and
+adds what only the forward kernels want: the V row views, the gated conv2's block interleave, ln_fold.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
 import os
 
 import torch
 
 from . import _lib
-from .shapes import GATE_SHARE, context_mode, conv_freq_out
+from .packing import _enc_map, encoder_specs, mapped_fp32, packed, relative_position_table, rotary_tables
+from .shapes import GATE_SHARE, context_mode
 
 G = dict(CONV1_W=0, CONV1_B=1, CONV2_W=2, CONV2_B=3, FEOUT_W=4, FEOUT_B=5, FP_LN_G=6, FP_LN_B=7, FP_W=8, FP_B=9,
          ENC_LN_G=10, ENC_LN_B=11, HEAD_W=12, HEAD_B=13, MIX_W=14, GATE1_W=15, GATE1_B=16, GATE2_W=17, GATE2_B=18)
@@ -29,6 +26,10 @@ LS = {n: i for i, n in enumerate(
      "FF2_LN_G", "FF2_LN_B", "FF2_W1", "FF2_B1", "FF2_W2", "FF2_B2", "CSGU_LIN_W", "CSGU_LIN_B",
      # ln_fold (csrc/gemm_args.hpp): W' = bf16(W diag(gamma)), colsum(W') fp32, W beta + b fp32 of the four LayerNorm -> Linear pairs
      "FF1_WF", "FF1_SF", "FF1_CF", "QKV_WF", "QKV_SF", "QKV_CF", "MLP_WF", "MLP_SF", "MLP_CF", "FF2_WF", "FF2_SF", "FF2_CF"])}
+SLOT_RENAME = {"att_wqkv": "ATT_WQK", "att_bqkv": "ATT_BQK"}      # every other slot is named like its packed parameter (packing.encoder_specs), upper-cased
+# the bias that completes a LayerNorm -> Linear pair of ln_fold -> (slot prefix, weight, LayerNorm gamma, beta); the pair's other three precede it in the walk
+FOLDS = {"ff1_b1": ("FF1", "ff1_w1", "ff1_ln_g", "ff1_ln_b"), "att_bqkv": ("QKV", "att_wqkv", "att_ln_g", "att_ln_b"),
+         "mlp_b1": ("MLP", "mlp_w1", "mlp_ln_g", "mlp_ln_b"), "ff2_b1": ("FF2", "ff2_w1", "ff2_ln_g", "ff2_ln_b")}
 ACT = {"identity": 0, "gelu": 1, "relu": 2, "silu": 3, "swish": 3}
 POS = {None: 0, "none": 0, "relative": 1, "rotary": 2}
 
@@ -99,96 +100,35 @@ class EBranchformerEngine:
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd: dict):
-        """sd: reference-named tensors (any device/dtype); packs them on `self.device`."""
+        """sd: reference-named tensors (any device/dtype); packs them on `self.device`: every packed parameter of packing.encoder_specs into the slot of its
+        name (`l3.ff1_ln_g` -> layer 3, FF1_LN_G), matrices in bf16, the rest in fp32, plus the three things only the forward kernels want (below)."""
         c, dev = self.cfg, self.device
-        d, L = c["hidden_size"], c["num_hidden_layers"]
-        bf = lambda t: t.detach().to(dev, torch.float32).to(torch.bfloat16).contiguous()
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()
-        K = c["conv_kernel"][0]
-        C1, C2 = c["conv_dim"]
-        F2 = conv_freq_out(c.get("num_fbanks", 80), c["conv_kernel"], c["conv_stride"], c["conv_padding"])
-        fe = "wav2vec2.feature_extractor."
-        cw = "" if c.get("is_causal", False) else ".conv"
-        slots = [None] * (_lib.GLOBAL_SLOTS + (L + self.extra) * _lib.LAYER_SLOTS)
-        keep = []
-
-        def put(idx, t):
-            keep.append(t)
-            slots[idx] = t
-
-        if self.ctx_mode:       # ContextAwareConv2d.conv = Gated* module with .conv and .gate (extractors.py:23-54)
-            cl = lambda t: t.detach().to(dev, torch.float32).permute(0, 2, 3, 1).reshape(t.shape[0], -1)      # (Cout, Cin, KH, KW) -> (Cout, (kh, kw, cin))
-            put(G["CONV1_W"], f32(sd[f"{fe}conv.0.0.conv.conv.weight"]).reshape(C1, -1)); put(G["CONV1_B"], f32(sd[f"{fe}conv.0.0.conv.conv.bias"]))
-            put(G["GATE1_W"], f32(sd[f"{fe}conv.0.0.conv.gate.weight"]).reshape(C1, -1)); put(G["GATE1_B"], f32(sd[f"{fe}conv.0.0.conv.gate.bias"]))
-            wc, wg = cl(sd[f"{fe}conv.1.0.conv.conv.weight"]), cl(sd[f"{fe}conv.1.0.conv.gate.weight"])
-            bc, bg = f32(sd[f"{fe}conv.1.0.conv.conv.bias"]), f32(sd[f"{fe}conv.1.0.conv.gate.bias"])
-            if self.ctx_mode == 1:          # one implicit GEMM: [conv blk ; gate blk] per 2*blk rows (gemm_8p.hip GATED epilogue / mi_gated_act_bf16)
-                nb = C2 // self.gate_blk
-                put(G["CONV2_W"], bf(torch.stack([wc.view(nb, self.gate_blk, -1), wg.view(nb, self.gate_blk, -1)], 1).reshape(2 * C2, -1)))
-                put(G["CONV2_B"], f32(torch.stack([bc.view(nb, -1), bg.view(nb, -1)], 1).reshape(2 * C2)))
-            else:
-                put(G["CONV2_W"], bf(wc)); put(G["CONV2_B"], bc)
-                put(G["GATE2_W"], bf(wg)); put(G["GATE2_B"], bg)
-        else:
-            put(G["CONV1_W"], f32(sd[f"{fe}conv.0.0{cw}.weight"]).reshape(C1, K * K))
-            put(G["CONV1_B"], f32(sd[f"{fe}conv.0.0{cw}.bias"]))
-            put(G["CONV2_W"], bf(sd[f"{fe}conv.1.0{cw}.weight"].permute(0, 2, 3, 1).reshape(C2, K * K * C1)))
-            put(G["CONV2_B"], f32(sd[f"{fe}conv.1.0{cw}.bias"]))
-        put(G["FEOUT_W"], bf(sd[fe + "out.weight"].reshape(d, C2, F2).permute(0, 2, 1).reshape(d, F2 * C2)))
-        put(G["FEOUT_B"], f32(sd[fe + "out.bias"]))
-        fp = "wav2vec2.feature_projection."
-        put(G["FP_LN_G"], f32(sd[fp + "layer_norm.weight"])); put(G["FP_LN_B"], f32(sd[fp + "layer_norm.bias"]))
-        put(G["FP_W"], bf(sd[fp + "projection.weight"])); put(G["FP_B"], f32(sd[fp + "projection.bias"]))
-        put(G["ENC_LN_G"], f32(sd["wav2vec2.encoder.layer_norm.weight"])); put(G["ENC_LN_B"], f32(sd["wav2vec2.encoder.layer_norm.bias"]))
-        put(G["HEAD_W"], bf(torch.cat([sd["lm_head.weight"].detach().to(dev), sd["blank_projection.weight"].detach().to(dev)], 0)))
-        put(G["HEAD_B"], f32(torch.cat([sd["lm_head.bias"].detach().to(dev), sd["blank_projection.bias"].detach().to(dev)], 0)))
-        if self.mix:
-            put(G["MIX_W"], f32(sd["per_layer_weights"]))
-        rel = c.get("position_embeddings_type", "relative") == "relative"
-        for l in range(L + self.extra):
-            p = f"wav2vec2.encoder.layers.{l}." if l < L else "additional_layer."
-            base = _lib.GLOBAL_SLOTS + l * _lib.LAYER_SLOTS
-            lp = lambda name, t: put(base + LS[name], t)
-            if c.get("use_macaron_ff", True):
-                for ff, pre in (("ff1", "FF1"), ("ff2", "FF2")):
-                    lp(pre + "_LN_G", f32(sd[p + ff + ".0.weight"])); lp(pre + "_LN_B", f32(sd[p + ff + ".0.bias"]))
-                    lp(pre + "_W1", bf(sd[p + ff + ".1.intermediate_dense.weight"])); lp(pre + "_B1", f32(sd[p + ff + ".1.intermediate_dense.bias"]))
-                    lp(pre + "_W2", bf(sd[p + ff + ".1.output_dense.weight"])); lp(pre + "_B2", f32(sd[p + ff + ".1.output_dense.bias"]))
-            lp("ATT_LN_G", f32(sd[p + "self_attn_layer_norm.weight"])); lp("ATT_LN_B", f32(sd[p + "self_attn_layer_norm.bias"]))
-            a = p + "self_attn."
-            # [Wq; Wk; Wv] packed as one (3d, d) matrix: the fused QKV GEMM uses all rows, the Q/K-only and V-only GEMMs views
-            wqkv = bf(torch.cat([sd[a + f"linear_{n}.weight"].detach().to(dev) for n in "qkv"], 0))
-            bqkv = f32(torch.cat([sd[a + f"linear_{n}.bias"].detach().to(dev) for n in "qkv"], 0))
-            lp("ATT_WQK", wqkv); lp("ATT_BQK", bqkv)
-            lp("ATT_WV", wqkv[2 * d:]); lp("ATT_BV", bqkv[2 * d:])
-            lp("ATT_WO", bf(sd[a + "linear_out.weight"])); lp("ATT_BO", f32(sd[a + "linear_out.bias"]))
-            if rel:
-                lp("ATT_WPOS", bf(sd[a + "linear_pos.weight"]))
-                lp("ATT_U", f32(sd[a + "pos_bias_u"])); lp("ATT_V", f32(sd[a + "pos_bias_v"]))
-            lp("MLP_LN_G", f32(sd[p + "cgMLP_layer_norm.weight"])); lp("MLP_LN_B", f32(sd[p + "cgMLP_layer_norm.bias"]))
-            m = p + "cgMLP."
-            lp("MLP_W1", bf(sd[m + "channel_proj1.0.weight"])); lp("MLP_B1", f32(sd[m + "channel_proj1.0.bias"]))
-            lp("CSGU_LN_G", f32(sd[m + "csgu.norm.weight"])); lp("CSGU_LN_B", f32(sd[m + "csgu.norm.bias"]))
-            lp("CSGU_W", f32(sd[m + "csgu.conv.weight"]).reshape(-1, c.get("csgu_kernel_size", 31)))
-            lp("CSGU_B", f32(sd[m + "csgu.conv.bias"]))
-            if c.get("csgu_use_linear_after_conv", False):
-                lp("CSGU_LIN_W", bf(sd[m + "csgu.linear.weight"])); lp("CSGU_LIN_B", f32(sd[m + "csgu.linear.bias"]))
-            lp("MLP_W2", bf(sd[m + "channel_proj2.weight"])); lp("MLP_B2", f32(sd[m + "channel_proj2.bias"]))
-            lp("MRG_DW_W", f32(sd[p + "depthwise_conv_fusion.weight"]).reshape(-1, c.get("merge_conv_kernel", 31)))
-            lp("MRG_DW_B", f32(sd[p + "depthwise_conv_fusion.bias"]))
-            lp("MRG_W", bf(sd[p + "merge_proj.weight"])); lp("MRG_B", f32(sd[p + "merge_proj.bias"]))
-            lp("FIN_LN_G", f32(sd[p + "final_layer_norm.weight"])); lp("FIN_LN_B", f32(sd[p + "final_layer_norm.bias"]))
-            if self._fold_shapes_ok():
-                def fold(tag, w, b, g, be):          # LN(x) W^T + b = rstd (x W'^T) - rstd mu colsum(W') + (W beta + b)
-                    w32, g32, be32 = w.detach().to(dev, torch.float32), g.detach().to(dev, torch.float32), be.detach().to(dev, torch.float32)
-                    wf = (w32 * g32[None, :]).to(torch.bfloat16).contiguous()
-                    lp(tag + "_WF", wf); lp(tag + "_SF", wf.float().sum(-1).contiguous()); lp(tag + "_CF", ((w32 * be32[None, :]).sum(-1) + b.detach().to(dev, torch.float32)).contiguous())      # (element-wise + row sum: no vendor BLAS call even at load time)
-                for ff, tag in (("ff1", "FF1"), ("ff2", "FF2")):
-                    fold(tag, sd[p + ff + ".1.intermediate_dense.weight"], sd[p + ff + ".1.intermediate_dense.bias"], sd[p + ff + ".0.weight"], sd[p + ff + ".0.bias"])
-                fold("QKV", torch.cat([sd[a + f"linear_{n}.weight"].detach().to(dev) for n in "qkv"], 0), torch.cat([sd[a + f"linear_{n}.bias"].detach().to(dev) for n in "qkv"], 0),
-                     sd[p + "self_attn_layer_norm.weight"], sd[p + "self_attn_layer_norm.bias"])
-                fold("MLP", sd[m + "channel_proj1.0.weight"], sd[m + "channel_proj1.0.bias"], sd[p + "cgMLP_layer_norm.weight"], sd[p + "cgMLP_layer_norm.bias"])
-        self._keep = keep
+        d, C2 = c["hidden_size"], c["conv_dim"][1]
+        m = _enc_map(c)
+        slots = [None] * (_lib.GLOBAL_SLOTS + (c["num_hidden_layers"] + self.extra) * _lib.LAYER_SLOTS)
+        fold = self._fold_shapes_ok()
+        layer = {}                                   # fp32 packed tensors of the layer being walked, by short name (ln_fold reads them)
+        for s, t in packed(encoder_specs(c), m, mapped_fp32(m, sd, dev)):
+            if s.name == "masked_spec_embed":        # SpecAugment's fill vector: training only
+                continue
+            l, _, n = s.name.rpartition(".")         # ("l3", ".", "ff1_ln_g") or ("", "", "feout_w")
+            base, names = (_lib.GLOBAL_SLOTS + int(l[1:]) * _lib.LAYER_SLOTS, LS) if l else (0, G)
+            if self.ctx_mode == 1 and n in ("conv2_w", "conv2_b"):
+                # packed: conv rows then gate rows; the one implicit GEMM's epilogue wants [conv blk ; gate blk] per 2*blk rows (gemm_8p.hip GATED / mi_gated_act_bf16)
+                t = t.reshape(2, C2 // self.gate_blk, self.gate_blk, -1).transpose(0, 1).reshape(s.shape)
+            w = t.to(torch.bfloat16).contiguous() if s.mat else t.contiguous()
+            slots[base + names[SLOT_RENAME.get(n, n.upper())]] = w
+            if n in ("att_wqkv", "att_bqkv"):        # the V-only GEMM reads row views of the packed [Wq; Wk; Wv]
+                slots[base + LS["ATT_WV" if s.mat else "ATT_BV"]] = w[2 * d:]
+            if fold:
+                layer[n] = t
+                if n in FOLDS:                       # LN(x) W^T + b = rstd (x W'^T) - rstd mu colsum(W') + (W beta + b)
+                    tag, wn, gn, bn = FOLDS[n]
+                    wf = (layer[wn] * layer[gn][None, :]).to(torch.bfloat16).contiguous()
+                    slots[base + LS[tag + "_WF"]] = wf
+                    slots[base + LS[tag + "_SF"]] = wf.float().sum(-1).contiguous()
+                    slots[base + LS[tag + "_CF"]] = ((layer[wn] * layer[bn][None, :]).sum(-1) + t).contiguous()      # (element-wise + row sum: no vendor BLAS call even at load time)
+        self._keep = [t for t in slots if t is not None]
         self._slots = slots
         self._table = (C.c_void_p * len(slots))(*[(t.data_ptr() if t is not None else None) for t in slots])
         self._posp_valid = {}
@@ -245,19 +185,11 @@ class EBranchformerEngine:
         if key in self._pos:
             return self._pos[key]
         d, H = c["hidden_size"], c["num_attention_heads"]
-        if ptype == "relative":   # tf wav2vec2_conformer :159-205, rows = relative position T2-1 ... -(T2-1)
-            pos = torch.arange(T2 - 1, -T2, -1, dtype=torch.float32)[:, None]
-            div = torch.exp(torch.arange(0, d, 2, dtype=torch.int64).float() * -(math.log(10000.0) / d))
-            pe = torch.zeros(2 * T2 - 1, d)
-            pe[:, 0::2] = torch.sin(pos * div)
-            pe[:, 1::2] = torch.cos(pos * div)
-            t = pe.to(self.device).to(torch.bfloat16).contiguous()
-        elif ptype == "rotary":   # tf :125-156
-            hd = d // H
-            inv = 1.0 / (c.get("rotary_embedding_base", 10000) ** (torch.arange(0, hd, 2, dtype=torch.int64).float() / hd))
-            fr = torch.einsum("i,j->ij", torch.arange(T2).float(), inv)
-            emb = torch.cat((fr, fr), dim=-1)
-            t = torch.cat([emb.cos().reshape(-1), emb.sin().reshape(-1)]).to(self.device).contiguous()
+        if ptype == "relative":
+            t = relative_position_table(T2, d).to(self.device).to(torch.bfloat16).contiguous()
+        elif ptype == "rotary":   # one buffer: [cos.flat ; sin.flat]
+            cos, sin = rotary_tables(T2, d // H, c.get("rotary_embedding_base", 10000))
+            t = torch.cat([cos.reshape(-1), sin.reshape(-1)]).to(self.device).contiguous()
         else:
             t = None
         self._pos[key] = t

@@ -7,11 +7,11 @@ reference (`src/models/encoders/e_branchformer.py:225-261,408-416`, `src/models/
 from __future__ import annotations
 
 
-def conv_freq_out(num_fbanks: int, kernels, strides, paddings, causal: bool = False) -> int:
+def conv_freq_out(num_fbanks: int, kernels, strides, paddings) -> int:
     """reference src/models/utils.py:4-38 for the frequency axis."""
     f = num_fbanks
     for k, s, p in zip(kernels, strides, paddings):
-        f = (f + ((2 * p) if causal else 2 * p) - (k - 1) - 1) // s + 1
+        f = (f + 2 * p - (k - 1) - 1) // s + 1
     return f
 
 
@@ -58,7 +58,7 @@ def param_shapes(cfg: dict) -> dict:
             out[f"wav2vec2.feature_extractor.conv.{i}.0{cw}.weight"] = (c, cin, k, k)
             out[f"wav2vec2.feature_extractor.conv.{i}.0{cw}.bias"] = (c,)
         cin = c
-    fo = conv_freq_out(cfg.get("num_fbanks", 80), ks, cfg["conv_stride"], pads, cfg.get("is_causal", False))
+    fo = conv_freq_out(cfg.get("num_fbanks", 80), ks, cfg["conv_stride"], pads)
     out["wav2vec2.feature_extractor.out.weight"] = (d, conv_dim[-1] * fo)
     out["wav2vec2.feature_extractor.out.bias"] = (d,)
     out["wav2vec2.feature_projection.layer_norm.weight"] = (d,)

@@ -27,42 +27,19 @@ from __future__ import annotations
 import math
 import os
 from collections import namedtuple
-from dataclasses import dataclass
 from functools import partial
-from typing import Callable, NamedTuple
 
 import torch
 
 from . import ops
 from . import ops_train as T
-from .shapes import GATE_SHARE, context_mode, conv_freq_out, gate_geometry
+from .packing import Ref, Spec, _enc_map, _one, encoder_specs, mapped_fp32, packed, relative_position_table, rotary_tables  # noqa: F401
+from .shapes import GATE_SHARE, context_mode, gate_geometry
 
 BF16, F32 = torch.bfloat16, torch.float32
 
 
 # ====================================================================================================== parameter store
-@dataclass
-class Spec:
-    name: str
-    shape: tuple
-    mat: bool          # bf16 (N,K) GEMM operand -> also keeps the transposed bf16 copy
-    decay: bool
-
-
-class Ref(NamedTuple):
-    """how one packed parameter relates to the reference's state dict: pack(sd) -> the packed tensor, pieces = [(reference key,
-    unpack(packed) -> the reference tensor, a view where the layouts allow), ...]; optional: the keys may be missing from a reference
-    state dict (pack then supplies the default) and are not exported when the last load lacked them"""
-    pack: Callable
-    pieces: list
-    optional: bool = False
-
-
-def _one(m, name, key, fwd=lambda t: t, bwd=lambda t: t):
-    """map entry of a packed parameter that is ONE reference tensor: packed = fwd(sd[key]), reference = bwd(packed)"""
-    m[name] = Ref(lambda sd: fwd(sd[key]), [(key, bwd)])
-
-
 def _al(n, a=64):
     return (n + a - 1) // a * a
 
@@ -92,7 +69,7 @@ class ParamStore:
         self.frozen_spans = []
         self.set_frozen(())
         self.step_count = 0
-        self.map = {n: Ref(*r) for n, r in (ref_map or {}).items()}
+        self.map = dict(ref_map or {})
         self._piece = {key: (name, unpack) for name, r in self.map.items() for key, unpack in r.pieces}
         self.absent = set()             # optional reference keys the last load lacked
         self.fresh = False              # see zero_grad
@@ -174,10 +151,10 @@ class ParamStore:
 
     def pack(self, sd: dict):
         """the fp32 masters from a reference state dict (keys this store does not map are ignored; the bf16 mirrors are left to `load`)"""
-        sd = {k: v.detach().to(self.device, F32) for k, v in sd.items() if k in self._piece and torch.is_tensor(v) and v.is_floating_point()}
+        sd = mapped_fp32(self.map, sd, self.device)
         self.absent = {key for r in self.map.values() if r.optional for key, _ in r.pieces if key not in sd}
-        for name in self.order:
-            self.p(name).copy_(self.map[name].pack(sd).reshape(self.specs[name].shape))
+        for s, t in packed(self.specs.values(), self.map, sd):
+            self.p(s.name).copy_(t)
 
     def load(self, sd: dict):
         self.pack(sd)
@@ -227,144 +204,6 @@ def ops_cast_flat(src_f32, dst_bf16):
     if rem:
         ops._lib.check(ops._lib.lib().mi_cast_f32_bf16(src_f32[rows * w:].data_ptr(), rem, dst_bf16[rows * w:].data_ptr(), rem, 1, rem,
                                                        torch.cuda.current_stream().cuda_stream), "mi_cast_f32_bf16")
-
-
-# ====================================================================================================== encoder parameters
-def encoder_specs(c: dict, head: bool = True) -> list[Spec]:
-    d, I, L, V1 = c["hidden_size"], c["intermediate_size"], c["num_hidden_layers"], c["vocab_size"] + 1
-    C1, C2 = c["conv_dim"]
-    K = c["conv_kernel"][0]
-    F2 = conv_freq_out(c.get("num_fbanks", 80), c["conv_kernel"], c["conv_stride"], c["conv_padding"])
-    kc, km = c.get("csgu_kernel_size", 31), c.get("merge_conv_kernel", 31)
-    rel = c.get("position_embeddings_type", "relative") == "relative"
-    S = []
-    mat = lambda n, *sh: S.append(Spec(n, tuple(sh), True, True))
-    vec = lambda n, *sh, decay=False: S.append(Spec(n, tuple(sh), False, decay))
-    vec("masked_spec_embed", d)     # SpecAugment fill vector: carried for state-dict parity, never receives a gradient on this path (torch skips it too)
-    mode = context_mode(c)                                   # context-aware front end (extractors.py:23-65): 0 plain, 1 gated, 2 gated_shared
-    gkh = K * (GATE_SHARE if mode == 2 else 1)               # the shared gate's kernel is (4K, K)
-    vec("conv1_w", C1, K * K, decay=True); vec("conv1_b", C1)
-    if mode:
-        vec("gate1_w", C1, gkh * K, decay=True); vec("gate1_b", C1)
-    if mode == 1:                                            # conv rows, then gate rows: ONE implicit GEMM forward, one dW / dX GEMM pair backward
-        mat("conv2_w", 2 * C2, K * K * C1); vec("conv2_b", 2 * C2)
-    else:
-        mat("conv2_w", C2, K * K * C1); vec("conv2_b", C2)
-    if mode == 2:
-        mat("gate2_w", C2, gkh * K * C1); vec("gate2_b", C2)
-    mat("feout_w", d, F2 * C2); vec("feout_b", d)
-    vec("fp_ln_g", d); vec("fp_ln_b", d); mat("fp_w", d, d); vec("fp_b", d)
-    for l in range(L + int(bool(c.get("finetune_with_additional_layer", False)))):     # layer L = the fine-tuning head's `additional_layer` (bestrq.py:199-200)
-        p = f"l{l}."
-        ffs = ("ff1", "ff2") if c.get("use_macaron_ff", True) else ()
-        for ff in ffs[:1]:
-            vec(p + ff + "_ln_g", d); vec(p + ff + "_ln_b", d); mat(p + ff + "_w1", I, d); vec(p + ff + "_b1", I); mat(p + ff + "_w2", d, I); vec(p + ff + "_b2", d)
-        vec(p + "att_ln_g", d); vec(p + "att_ln_b", d)
-        mat(p + "att_wqkv", 3 * d, d); vec(p + "att_bqkv", 3 * d); mat(p + "att_wo", d, d); vec(p + "att_bo", d)
-        if rel:
-            mat(p + "att_wpos", d, d); vec(p + "att_u", d); vec(p + "att_v", d)          # pos_bias_* : "bias" in the name -> no decay
-        vec(p + "mlp_ln_g", d); vec(p + "mlp_ln_b", d); mat(p + "mlp_w1", I, d); vec(p + "mlp_b1", I)
-        vec(p + "csgu_ln_g", I // 2); vec(p + "csgu_ln_b", I // 2); vec(p + "csgu_w", I // 2, kc, decay=True); vec(p + "csgu_b", I // 2)
-        if c.get("csgu_use_linear_after_conv", False):
-            mat(p + "csgu_lin_w", I // 2, I // 2); vec(p + "csgu_lin_b", I // 2)
-        mat(p + "mlp_w2", d, I // 2); vec(p + "mlp_b2", d)
-        vec(p + "mrg_dw_w", 2 * d, km, decay=True); vec(p + "mrg_dw_b", 2 * d); mat(p + "mrg_w", d, 2 * d); vec(p + "mrg_b", d)
-        for ff in ffs[1:]:
-            vec(p + ff + "_ln_g", d); vec(p + ff + "_ln_b", d); mat(p + ff + "_w1", I, d); vec(p + ff + "_b1", I); mat(p + ff + "_w2", d, I); vec(p + ff + "_b2", d)
-        vec(p + "fin_ln_g", d); vec(p + "fin_ln_b", d)
-    vec("enc_ln_g", d); vec("enc_ln_b", d)
-    if c.get("finetune_with_layer_mixing", False):
-        vec("mix_w", L + 1, decay=True)          # `per_layer_weights` (bestrq.py:202-205): a plain nn.Parameter, so weight decay applies
-    if head:
-        mat("head_w", V1, d); vec("head_b", V1)
-    return S
-
-
-def _enc_map(c: dict, head: bool = True):
-    """packed name -> Ref (the encoder's packed layouts <-> the reference's state-dict names)"""
-    d, L = c["hidden_size"], c["num_hidden_layers"]
-    C1, C2 = c["conv_dim"]
-    K = c["conv_kernel"][0]
-    V = c["vocab_size"]
-    F2 = conv_freq_out(c.get("num_fbanks", 80), c["conv_kernel"], c["conv_stride"], c["conv_padding"])
-    kc, km = c.get("csgu_kernel_size", 31), c.get("merge_conv_kernel", 31)
-    fe, fp = "wav2vec2.feature_extractor.", "wav2vec2.feature_projection."
-    cw = "" if c.get("is_causal", False) else ".conv"
-    m = {}
-    one = partial(_one, m)
-    # optional in the reference (present iff mask_time_prob > 0 or mask_feature_prob > 0): absent -> zeros, not exported
-    m["masked_spec_embed"] = Ref(lambda sd: sd["wav2vec2.masked_spec_embed"] if "wav2vec2.masked_spec_embed" in sd else torch.zeros(d),
-                                 [("wav2vec2.masked_spec_embed", lambda t: t)], optional=True)
-    mode = context_mode(c)
-    if mode:        # ContextAwareConv2d.conv is a Gated* module: keys ...conv.N.0.conv.{conv,gate}.{weight,bias} (extractors.py:23-54)
-        gkh = K * (GATE_SHARE if mode == 2 else 1)
-        c1, c2 = f"{fe}conv.0.0.conv.", f"{fe}conv.1.0.conv."
-        cl = lambda t: t.permute(0, 2, 3, 1).reshape(t.shape[0], -1)                                  # (Cout, Cin, KH, KW) -> (Cout, (kh, kw, cin))
-        uncl = lambda kh: (lambda t: t.reshape(C2, kh, K, C1).permute(0, 3, 1, 2))
-        one("conv1_w", c1 + "conv.weight", lambda t: t.reshape(C1, K * K), lambda t: t.reshape(C1, 1, K, K))
-        one("conv1_b", c1 + "conv.bias")
-        one("gate1_w", c1 + "gate.weight", lambda t: t.reshape(C1, gkh * K), lambda t: t.reshape(C1, 1, gkh, K))
-        one("gate1_b", c1 + "gate.bias")
-        if mode == 1:
-            m["conv2_w"] = (lambda sd: torch.cat([cl(sd[c2 + "conv.weight"]), cl(sd[c2 + "gate.weight"])], 0),
-                            [(c2 + "conv.weight", lambda t: uncl(K)(t[:C2])), (c2 + "gate.weight", lambda t: uncl(K)(t[C2:]))])
-            m["conv2_b"] = (lambda sd: torch.cat([sd[c2 + "conv.bias"], sd[c2 + "gate.bias"]], 0),
-                            [(c2 + "conv.bias", lambda t: t[:C2]), (c2 + "gate.bias", lambda t: t[C2:])])
-        else:
-            one("conv2_w", c2 + "conv.weight", cl, uncl(K)); one("conv2_b", c2 + "conv.bias")
-            one("gate2_w", c2 + "gate.weight", cl, uncl(gkh)); one("gate2_b", c2 + "gate.bias")
-    else:
-        one("conv1_w", f"{fe}conv.0.0{cw}.weight", lambda t: t.reshape(C1, K * K), lambda t: t.reshape(C1, 1, K, K))
-        one("conv1_b", f"{fe}conv.0.0{cw}.bias")
-        one("conv2_w", f"{fe}conv.1.0{cw}.weight", lambda t: t.permute(0, 2, 3, 1).reshape(C2, K * K * C1),
-            lambda t: t.reshape(C2, K, K, C1).permute(0, 3, 1, 2))
-        one("conv2_b", f"{fe}conv.1.0{cw}.bias")
-    one("feout_w", fe + "out.weight", lambda t: t.reshape(d, C2, F2).permute(0, 2, 1).reshape(d, F2 * C2),
-        lambda t: t.reshape(d, F2, C2).permute(0, 2, 1).reshape(d, C2 * F2))
-    one("feout_b", fe + "out.bias")
-    one("fp_ln_g", fp + "layer_norm.weight"); one("fp_ln_b", fp + "layer_norm.bias")
-    one("fp_w", fp + "projection.weight"); one("fp_b", fp + "projection.bias")
-    one("enc_ln_g", "wav2vec2.encoder.layer_norm.weight"); one("enc_ln_b", "wav2vec2.encoder.layer_norm.bias")
-    if head:
-        m["head_w"] = (lambda sd: torch.cat([sd["lm_head.weight"], sd["blank_projection.weight"]], 0),
-                       [("lm_head.weight", lambda t: t[:V]), ("blank_projection.weight", lambda t: t[V:])])
-        m["head_b"] = (lambda sd: torch.cat([sd["lm_head.bias"], sd["blank_projection.bias"]], 0),
-                       [("lm_head.bias", lambda t: t[:V]), ("blank_projection.bias", lambda t: t[V:])])
-    if c.get("finetune_with_layer_mixing", False):
-        one("mix_w", "per_layer_weights")
-    for l in range(L + int(bool(c.get("finetune_with_additional_layer", False)))):
-        p, r = f"l{l}.", (f"wav2vec2.encoder.layers.{l}." if l < L else "additional_layer.")
-        if c.get("use_macaron_ff", True):
-            for ff in ("ff1", "ff2"):
-                one(p + ff + "_ln_g", r + ff + ".0.weight"); one(p + ff + "_ln_b", r + ff + ".0.bias")
-                one(p + ff + "_w1", r + ff + ".1.intermediate_dense.weight"); one(p + ff + "_b1", r + ff + ".1.intermediate_dense.bias")
-                one(p + ff + "_w2", r + ff + ".1.output_dense.weight"); one(p + ff + "_b2", r + ff + ".1.output_dense.bias")
-        one(p + "att_ln_g", r + "self_attn_layer_norm.weight"); one(p + "att_ln_b", r + "self_attn_layer_norm.bias")
-        a = r + "self_attn."
-        m[p + "att_wqkv"] = (lambda sd, a=a: torch.cat([sd[a + f"linear_{n}.weight"] for n in "qkv"], 0),
-                             [(a + f"linear_{n}.weight", (lambda t, i=i: t[i * d:(i + 1) * d])) for i, n in enumerate("qkv")])
-        m[p + "att_bqkv"] = (lambda sd, a=a: torch.cat([sd[a + f"linear_{n}.bias"] for n in "qkv"], 0),
-                             [(a + f"linear_{n}.bias", (lambda t, i=i: t[i * d:(i + 1) * d])) for i, n in enumerate("qkv")])
-        one(p + "att_wo", a + "linear_out.weight"); one(p + "att_bo", a + "linear_out.bias")
-        if c.get("position_embeddings_type", "relative") == "relative":
-            H = c["num_attention_heads"]
-            one(p + "att_wpos", a + "linear_pos.weight")
-            one(p + "att_u", a + "pos_bias_u", lambda t: t.reshape(d), lambda t: t.reshape(H, d // H))
-            one(p + "att_v", a + "pos_bias_v", lambda t: t.reshape(d), lambda t: t.reshape(H, d // H))
-        one(p + "mlp_ln_g", r + "cgMLP_layer_norm.weight"); one(p + "mlp_ln_b", r + "cgMLP_layer_norm.bias")
-        g = r + "cgMLP."
-        one(p + "mlp_w1", g + "channel_proj1.0.weight"); one(p + "mlp_b1", g + "channel_proj1.0.bias")
-        one(p + "csgu_ln_g", g + "csgu.norm.weight"); one(p + "csgu_ln_b", g + "csgu.norm.bias")
-        one(p + "csgu_w", g + "csgu.conv.weight", lambda t: t.reshape(-1, kc), lambda t: t.reshape(-1, 1, kc))
-        one(p + "csgu_b", g + "csgu.conv.bias")
-        if c.get("csgu_use_linear_after_conv", False):
-            one(p + "csgu_lin_w", g + "csgu.linear.weight"); one(p + "csgu_lin_b", g + "csgu.linear.bias")
-        one(p + "mlp_w2", g + "channel_proj2.weight"); one(p + "mlp_b2", g + "channel_proj2.bias")
-        one(p + "mrg_dw_w", r + "depthwise_conv_fusion.weight", lambda t: t.reshape(-1, km), lambda t: t.reshape(-1, 1, km))
-        one(p + "mrg_dw_b", r + "depthwise_conv_fusion.bias")
-        one(p + "mrg_w", r + "merge_proj.weight"); one(p + "mrg_b", r + "merge_proj.bias")
-        one(p + "fin_ln_g", r + "final_layer_norm.weight"); one(p + "fin_ln_b", r + "final_layer_norm.bias")
-    return m
 
 
 # ====================================================================================================== gradient sync (DP)
@@ -640,18 +479,10 @@ class EncoderCTCTrainer(ZeroCopyTrainer):
         key = (ptype, T2)
         if key not in self._pos:
             if ptype == "relative":
-                pos = torch.arange(T2 - 1, -T2, -1, dtype=F32)[:, None]
-                div = torch.exp(torch.arange(0, d, 2, dtype=torch.int64).float() * -(math.log(10000.0) / d))
-                pe = torch.zeros(2 * T2 - 1, d)
-                pe[:, 0::2] = torch.sin(pos * div); pe[:, 1::2] = torch.cos(pos * div)
-                t = pe.to(self.device).to(BF16).contiguous()
-                self._pos[key] = (t,)
+                self._pos[key] = (relative_position_table(T2, d).to(self.device).to(BF16).contiguous(),)
             elif ptype == "rotary":
-                hd = d // H
-                inv = 1.0 / (self.cfg.get("rotary_embedding_base", 10000) ** (torch.arange(0, hd, 2, dtype=torch.int64).float() / hd))
-                fr = torch.einsum("i,j->ij", torch.arange(T2).float(), inv)
-                emb = torch.cat((fr, fr), dim=-1)
-                self._pos[key] = (emb.cos().contiguous().to(self.device), emb.sin().contiguous().to(self.device), (-emb.sin()).contiguous().to(self.device))
+                cos, sin = rotary_tables(T2, d // H, self.cfg.get("rotary_embedding_base", 10000))
+                self._pos[key] = (cos.contiguous().to(self.device), sin.contiguous().to(self.device), (-sin).contiguous().to(self.device))
             else:
                 self._pos[key] = None
         return self._pos[key]

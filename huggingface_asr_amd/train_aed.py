@@ -13,71 +13,14 @@ restrictions as train.py; GPT-2's embd / attn / resid dropouts use the same coun
 from __future__ import annotations
 
 from collections import namedtuple
-from functools import partial
 
 import torch
 
 from . import ops
 from . import ops_train as T
 from .decoder import _sinusoid_table, shift_tokens_right
-from .train import BF16, F32, EncoderCTCTrainer, GradSync, ParamStore, Spec, ZeroCopyTrainer, _one
-
-
-def decoder_specs(c: dict, enc_dim: int, with_proj: bool) -> list[Spec]:
-    d, L, V = c["n_embd"], c["n_layer"], c["vocab_size"]
-    S = []
-    mat = lambda n, *sh: S.append(Spec(n, tuple(sh), True, True))
-    vec = lambda n, *sh, decay=False: S.append(Spec(n, tuple(sh), False, decay))
-    if with_proj:
-        mat("proj_w", d, enc_dim); vec("proj_b", d)
-    mat("wte", V, d)                                       # fp32 master feeds the embedding gather, bf16 mirror a tied lm_head
-    if not c.get("pos_emb_fixed", False):
-        vec("wpe", c.get("n_positions", 1024), d, decay=True)
-    for l in range(L):
-        p = f"h{l}."
-        vec(p + "ln1_g", d); vec(p + "ln1_b", d); mat(p + "wqkv", 3 * d, d); vec(p + "bqkv", 3 * d); mat(p + "wo", d, d); vec(p + "bo", d)
-        vec(p + "lnc_g", d); vec(p + "lnc_b", d); mat(p + "wq", d, d); vec(p + "bq", d); mat(p + "wkv", 2 * d, d); vec(p + "bkv", 2 * d)
-        mat(p + "wco", d, d); vec(p + "bco", d)
-        vec(p + "ln2_g", d); vec(p + "ln2_b", d); mat(p + "wfc", 4 * d, d); vec(p + "bfc", 4 * d); mat(p + "wpr", d, 4 * d); vec(p + "bpr", d)
-    vec("lnf_g", d); vec("lnf_b", d)
-    if not c.get("tie_word_embeddings", False):
-        mat("lm_head", V, d)
-    for k in range(len(c.get("head_locations") or [])):
-        mat(f"head{k}", V, d)
-    return S
-
-
-def _dec_map(c: dict, with_proj: bool, prefix="decoder."):
-    L = c["n_layer"]
-    m = {}
-    one = partial(_one, m)
-    tr_in = lambda t: t.t().contiguous()                   # transformers Conv1D stores (in, out); the store keeps (out, in)
-    tr = lambda t: t.t()                                   # export: a transposed VIEW (alias_views hands it to the nn.Parameter; state_dict() clones it contiguous)
-    if with_proj:
-        one("proj_w", "enc_to_dec_proj.weight"); one("proj_b", "enc_to_dec_proj.bias")
-    t = prefix + "transformer."
-    if c.get("pos_emb_fixed", False):
-        one("wte", t + "wte.emb_layers.0.weight")
-    else:
-        one("wte", t + "wte.weight"); one("wpe", t + "wpe.weight")
-    for l in range(L):
-        p, r = f"h{l}.", f"{t}h.{l}."
-        one(p + "ln1_g", r + "ln_1.weight"); one(p + "ln1_b", r + "ln_1.bias")
-        one(p + "wqkv", r + "attn.c_attn.weight", tr_in, tr); one(p + "bqkv", r + "attn.c_attn.bias")
-        one(p + "wo", r + "attn.c_proj.weight", tr_in, tr); one(p + "bo", r + "attn.c_proj.bias")
-        one(p + "lnc_g", r + "ln_cross_attn.weight"); one(p + "lnc_b", r + "ln_cross_attn.bias")
-        one(p + "wq", r + "crossattention.q_attn.weight", tr_in, tr); one(p + "bq", r + "crossattention.q_attn.bias")
-        one(p + "wkv", r + "crossattention.c_attn.weight", tr_in, tr); one(p + "bkv", r + "crossattention.c_attn.bias")
-        one(p + "wco", r + "crossattention.c_proj.weight", tr_in, tr); one(p + "bco", r + "crossattention.c_proj.bias")
-        one(p + "ln2_g", r + "ln_2.weight"); one(p + "ln2_b", r + "ln_2.bias")
-        one(p + "wfc", r + "mlp.c_fc.weight", tr_in, tr); one(p + "bfc", r + "mlp.c_fc.bias")
-        one(p + "wpr", r + "mlp.c_proj.weight", tr_in, tr); one(p + "bpr", r + "mlp.c_proj.bias")
-    one("lnf_g", t + "ln_f.weight"); one("lnf_b", t + "ln_f.bias")
-    if not c.get("tie_word_embeddings", False):
-        one("lm_head", prefix + "lm_head.weight")
-    for k in range(len(c.get("head_locations") or [])):
-        one(f"head{k}", f"{prefix}additional_lm_heads.{k}.weight")
-    return m
+from .packing import _dec_map, decoder_specs
+from .train import BF16, F32, EncoderCTCTrainer, GradSync, ParamStore, ZeroCopyTrainer
 
 
 def attention_bwd_fused(q, k, v, ctx, dctx, lse, dq, dk, dv, B, Tq, Tk, H, *, lengths=None, causal=False, drop=None):
