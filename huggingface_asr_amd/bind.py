@@ -20,6 +20,7 @@ import sys
 from transformers import AutoConfig, AutoFeatureExtractor, AutoModelForCTC, AutoModelForPreTraining, AutoModelForSpeechSeq2Seq
 
 from .configuration_ebranchformer import Wav2Vec2EBranchformerConfig
+from .decoding import ctc_greedy_decode
 from .feature_extraction import CustomFeatureExtractor, CustomFeatureExtractorConfig
 from .modeling_bestrq import BestRQEBranchformerForCTC, BestRQEBranchformerForPreTraining, BestRQEBranchformerForPreTrainingConfig
 from .modeling_ebranchformer import Wav2Vec2EBranchformerForCTC
@@ -36,6 +37,11 @@ REBIND = {
     "models.bestrq": {"BestRQEBranchformerForCTC": BestRQEBranchformerForCTC, "BestRQEBranchformerForPreTraining": BestRQEBranchformerForPreTraining,
                       "BestRQEBranchformerForPreTrainingConfig": BestRQEBranchformerForPreTrainingConfig},
     "utilities.feature_extractors": {"CustomFeatureExtractor": CustomFeatureExtractor, "CustomFeatureExtractorConfig": CustomFeatureExtractorConfig},
+}
+# reference module -> {function it exports: ours}; apart from REBIND, which holds classes.  ctc_greedy_decode (eval_utils.py:37-43) is the CTC trainer's
+# preprocess_logits_for_metrics (train_ctc_asr.py:77-85): a Python groupby over a device tensor there, two kernel launches here.
+REBIND_FUNCTIONS = {
+    "utilities.eval_utils": {"ctc_greedy_decode": ctc_greedy_decode},
 }
 _REF_PACKAGES = ("models", "utilities", "decoding", "trainers", "augmentations")
 
@@ -73,6 +79,25 @@ def _rebind_everywhere(replaced: dict):
                 setattr(mod, attr, replaced[id(val)])
 
 
+def _install_functions():
+    """REBIND's job for the function table: the defining module gets ours (for importers that come later), and every already-imported reference module or
+    `__main__` that holds the reference's function under its own name (`from utilities.eval_utils import ctc_greedy_decode`) gets it too."""
+    import importlib
+    for modname, names in REBIND_FUNCTIONS.items():
+        try:
+            mod = importlib.import_module(modname)
+        except (ImportError, OSError):      # jiwer / torchaudio / wandb absent, or a shared library of theirs that does not load: the module cannot be in use either
+            continue
+        for attr, ours in names.items():
+            ref = getattr(mod, attr, None)
+            setattr(mod, attr, ours)
+            if ref is None or ref is ours:
+                continue
+            for name, other in list(sys.modules.items()):
+                if other is not None and (name == "__main__" or name.split(".")[0] in _REF_PACKAGES) and vars(other).get(attr) is ref:
+                    setattr(other, attr, ours)
+
+
 def install():
     """Swap the reference's classes for the HIP ones (needs the reference's `src/` on sys.path; call before the trainer's main(), e.g.
     through `python -m huggingface_asr_amd.launch`).  Idempotent."""
@@ -89,6 +114,7 @@ def install():
                 replaced[id(ref)] = ours
             setattr(mod, attr, ours)
     _rebind_everywhere(replaced)
+    _install_functions()
     importlib.import_module("models.auto_wrappers")
     ref_bind = importlib.import_module("utilities.bind")
     ref_bind.bind_all = bind_all

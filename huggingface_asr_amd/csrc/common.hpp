@@ -111,6 +111,45 @@ __device__ __forceinline__ float wave_max(float v) {
     v = fmaxf(v, dpp_f32<0x143, 0xC>(v, v));
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// Argmax with torch.argmax's rules as ONE order: a candidate (value, index) becomes a 64-bit key whose unsigned order IS that order — used by every kernel that
+// picks a best class (ctc_decode.hip, the argmax epilogue of gemm8p_kernel and its merge), so the fused and the stand-alone forms cannot disagree.
+//   high word: the float's bits made monotone (negatives inverted, positives with the sign bit set; -0 counts as +0), every NaN at the top (0xFFFFFFFF): a NaN beats
+//              every number, the larger value beats the smaller;
+//   low word:  ~index: among equal values (NaNs among themselves included) the lower index wins.
+// A total order, so folding candidates in any grouping gives the same winner, and a fold is one 64-bit compare and two selects.  The empty key 0 is below every real
+// candidate (-inf is 0x007FFFFF in the high word): an all -inf row ends at its index 0.
+typedef unsigned long long amax_t;
+constexpr amax_t ARGMAX_EMPTY = 0ull;
+__device__ __forceinline__ amax_t argmax_key(float v, int i) {
+    unsigned b = __builtin_bit_cast(unsigned, v);
+    b = b == 0x80000000u ? 0u : b;
+    unsigned k = b ^ ((unsigned)((int)b >> 31) | 0x80000000u);
+    k = v != v ? 0xFFFFFFFFu : k;
+    return ((amax_t)k << 32) | (amax_t)(unsigned)~i;
+}
+__device__ __forceinline__ amax_t argmax_max(amax_t a, amax_t b) { return a > b ? a : b; }
+__device__ __forceinline__ int argmax_index(amax_t k) { return (int)~(unsigned)k; }
+__device__ __forceinline__ float argmax_value(amax_t k) {            // the winning value back as a float (a NaN winner as a NaN; the empty key as a NaN too)
+    const unsigned u = (unsigned)(k >> 32);
+    return __builtin_bit_cast(float, (u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ amax_t argmax_dpp(amax_t k) {              // fold with the key of the lane the DPP control names (lanes outside ROW_MASK: with their own)
+    const int lo = (int)(unsigned)k, hi = (int)(unsigned)(k >> 32);
+    const unsigned plo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xF, false);
+    const unsigned phi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xF, false);
+    return argmax_max(k, ((amax_t)phi << 32) | (amax_t)plo);
+}
+__device__ __forceinline__ amax_t argmax_row16(amax_t k) {            // every lane of a row of 16 ends with the row's winner
+    k = argmax_dpp<0xB1, 0xF>(k); k = argmax_dpp<0x4E, 0xF>(k); k = argmax_dpp<0x141, 0xF>(k); k = argmax_dpp<0x140, 0xF>(k);
+    return k;
+}
+__device__ __forceinline__ int wave_argmax(amax_t k) {                // the wave's winning index, in every lane
+    k = argmax_row16(k);
+    k = argmax_dpp<0x142, 0xA>(k);                                    // row_bcast:15 into rows 1 and 3
+    k = argmax_dpp<0x143, 0xC>(k);                                    // row_bcast:31 into rows 2 and 3: lane 63 holds the wave's
+    return argmax_index(((amax_t)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), 63) << 32) | (amax_t)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, 63));
+}
 // max / sum of a value with its partner in the other half of the wave (lane ^ 32): one v_permlane32_swap instead of a ds_bpermute round trip
 __device__ __forceinline__ float half_swap_max(float v) {
     const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v), __builtin_bit_cast(unsigned, v), false, false);

@@ -244,14 +244,19 @@ extern "C" size_t mi_ebf_workspace_bytes(const mi_ebf_config* cfg) { return carv
 extern "C" int mi_gemm_lse_f32(const void* A, long lda, const void* W, long ldw, const float* bias, float* C, long ldc, float* lse, float* workspace,
                                int M, int N, int K, hipStream_t stream);
 extern "C" int mi_row_lse(const void* x, long ld, int dtype, int V, float* lse, int M, hipStream_t stream);
-extern "C" int mi_ebf_forward_lse(const mi_ebf_config* cfg, const void* const* weights, const float* feats,
-                                  const int* feat_lengths, const void* pos_table, void* posp, int compute_posp,
-                                  void* workspace, size_t workspace_bytes, float* last_hidden, void* logits,
-                                  int* inner_len, int* outer_len, float* hidden_states, float* lse, float* lse_workspace, hipStream_t st) {
+// best (nullable; mi_ebf_forward_greedy): (B*T2) int32 = the per-frame argmax over the V+1 classes.  With amax_workspace the head is mi_gemm_argmax_bf16 and no logits
+// exist; otherwise, or outside that kernel's shapes, the head GEMM runs into `logits` (here a scratch the caller lends) and mi_row_argmax reads it.
+static int ebf_forward_body(const mi_ebf_config* cfg, const void* const* weights, const float* feats,
+                            const int* feat_lengths, const void* pos_table, void* posp, int compute_posp,
+                            void* workspace, size_t workspace_bytes, float* last_hidden, void* logits,
+                            int* inner_len, int* outer_len, float* hidden_states, float* lse, float* lse_workspace,
+                            int* best, float* amax_workspace, hipStream_t st) {
     MI_ENTER();
     if ((lse != nullptr) != (lse_workspace != nullptr) || (lse && (!logits || !cfg->logits_f32))) return MI_ERR_ARG;
     const mi_ebf_config& c = *cfg;
     if (hidden_states && !last_hidden) return MI_ERR_ARG;
+    if (best && !amax_workspace && !logits) return MI_ERR_ARG;
+    if (best && !logits && ((c.d % 64) != 0 || c.d < 128)) return MI_ERR_UNSUPPORTED;      // the fused head's K: known before the encoder runs
     if (c.B <= 0 || c.T <= 0 || c.L <= 0 || c.d % c.H || c.I % 2) return MI_ERR_ARG;
     if (c.extra_layers < 0 || c.extra_layers > 1 || (c.layer_mixing && c.L + 1 > 1024)) return MI_ERR_ARG;
     const int Lt = c.L + c.extra_layers;      // the fine-tuning head's additional layer (bestrq.py:247-274) is layer L of the weight table
@@ -478,7 +483,19 @@ extern "C" int mi_ebf_forward_lse(const mi_ebf_config* cfg, const void* const* w
                                    Lf(l + 1, MLP_LN_G), Lf(l + 1, MLP_LN_B), w.a2, d, M, d, st));
     }
     // CTC head: lm_head ⊕ blank_projection, blank LAST (e_branchformer.py:456-457)
-    if (logits) {
+    if (best) {
+        const long ldl = c.logits_ld > 0 ? c.logits_ld : c.V + 1;
+        int rc_a = MI_ERR_UNSUPPORTED;
+        if (amax_workspace) {
+            rc_a = mi_gemm_argmax_bf16(w.hid, d, Gw(G_HEAD_W), d, Gf(G_HEAD_B), best, amax_workspace, M, c.V + 1, d, st);
+            if (rc_a != MI_OK && rc_a != MI_ERR_UNSUPPORTED) return rc_a;
+        }
+        if (rc_a == MI_ERR_UNSUPPORTED) {
+            if (!logits) return MI_ERR_UNSUPPORTED;
+            RUN(mi_gemm_bf16(w.hid, d, Gw(G_HEAD_W), d, Gf(G_HEAD_B), 1, logits, ldl, c.logits_f32, nullptr, 0, 1.f, 0, M, c.V + 1, d, 0, 0, st));
+            RUN(mi_row_argmax(logits, ldl, c.logits_f32 ? 0 : 1, c.V + 1, best, M, st));
+        }
+    } else if (logits) {
         const long ldl = c.logits_ld > 0 ? c.logits_ld : c.V + 1;
         int rc_l = MI_ERR_UNSUPPORTED;
         if (lse) {
@@ -494,6 +511,22 @@ extern "C" int mi_ebf_forward_lse(const mi_ebf_config* cfg, const void* const* w
         return MI_ERR_LAUNCH;
     MI_CHECK_LAUNCH();
     return MI_OK;
+}
+
+extern "C" int mi_ebf_forward_lse(const mi_ebf_config* cfg, const void* const* weights, const float* feats,
+                                  const int* feat_lengths, const void* pos_table, void* posp, int compute_posp,
+                                  void* workspace, size_t workspace_bytes, float* last_hidden, void* logits,
+                                  int* inner_len, int* outer_len, float* hidden_states, float* lse, float* lse_workspace, hipStream_t st) {
+    return ebf_forward_body(cfg, weights, feats, feat_lengths, pos_table, posp, compute_posp, workspace, workspace_bytes, last_hidden, logits, inner_len, outer_len,
+                            hidden_states, lse, lse_workspace, nullptr, nullptr, st);
+}
+
+extern "C" int mi_ebf_forward_greedy(const mi_ebf_config* cfg, const void* const* weights, const float* feats, const int* feat_lengths,
+                                     const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
+                                     float* last_hidden, int* best, float* argmax_workspace, void* head_scratch, int* inner_len, int* outer_len, hipStream_t st) {
+    if (!best) return MI_ERR_ARG;
+    return ebf_forward_body(cfg, weights, feats, feat_lengths, pos_table, posp, compute_posp, workspace, workspace_bytes, last_hidden, head_scratch, inner_len, outer_len,
+                            nullptr, nullptr, nullptr, best, argmax_workspace, st);
 }
 
 extern "C" int mi_ebf_forward_hs(const mi_ebf_config* cfg, const void* const* weights, const float* feats,

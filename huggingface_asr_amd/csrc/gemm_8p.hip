@@ -80,7 +80,8 @@ struct Ctx {
 // LNF (LayerNorm folded into the GEMM, gemm_args.hpp): the prologue reduces the per-row partial (sum, sumsq) pairs of the tile's 256 rows to (rstd, rstd * mean) in a 2-KiB LDS
 // table behind the ring — issued before the first K tile is consumed, so its memory round trip hides under the ring's fill — and the epilogue computes
 // rstd * acc - rstd * mean * s_n + bias_n instead of acc + bias_n.
-template <bool CONV, int ACT, bool OUT32 = false, bool GATED = false, bool LNF = false, bool LSE = false>     // ACT: 0 none, 1 erf-GELU, 2 tanh-GELU — compile-time, so the epilogue is straight-line code with many independent chains in flight
+// AMAX (with OUT32): the epilogue keeps only each row's (max, index) per wave block and stores no C (gemm_args.hpp amax_part).
+template <bool CONV, int ACT, bool OUT32 = false, bool GATED = false, bool LNF = false, bool LSE = false, bool AMAX = false>     // ACT: 0 none, 1 erf-GELU, 2 tanh-GELU — compile-time, so the epilogue is straight-line code with many independent chains in flight
 __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -321,7 +322,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
             // chip): out = resid + alpha * (acc + bias), and the LayerNorm-fold producer's extras (bf16 copy, per-row partial statistics over the wave's 64 columns).
             // The half's 16 residual vectors are requested once its accumulators have gone to LDS (their registers are free) and land under the LDS round trip.
             f32x4 rr[16];
-            if (p.resid) {
+            if (!AMAX && p.resid) {
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
                     const int m = min(m0 + wr * 128 + half * 64 + u * 4 + r16, p.M - 1);
@@ -334,6 +335,17 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
                 const int row = u * 4 + r16;
                 f32x4 v = *reinterpret_cast<const f32x4*>(reg + row * 256 + ((c16 ^ (row & 15)) << 4));
                 const int m = m0 + wr * 128 + half * 64 + row, n = nb + c16 * 4;
+                if constexpr (AMAX) {                       // the row's 64 columns of this wave block -> their (max, index); columns >= N do not count; nothing else leaves
+                    amax_t k = ARGMAX_EMPTY;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (n + e < p.N) k = argmax_max(k, argmax_key(v[e], n + e));
+                    k = argmax_row16(k);
+                    if (c16 == 0 && m < p.M)
+                        *reinterpret_cast<f32x2*>(p.amax_part + (long)m * p.amax_ld + ((n0 >> 6) + wc) * 2) = f32x2{argmax_value(k), __builtin_bit_cast(float, argmax_index(k))};
+                    if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+                    continue;
+                }
                 if (p.resid) v = rr[u] + p.alpha * v;
                 if (m < p.M && n < n4) *reinterpret_cast<f32x4*>(C + (long)m * p.ldc + n) = v;
                 if (p.C2 && m < p.M) *reinterpret_cast<bf16x4*>(p.C2 + (long)m * p.ldc2 + n) = bf16x4{f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w)};
@@ -1166,6 +1178,7 @@ bool gemm_8p_supported(const GemmArgs& a, bool conv) {
         if (!a.out_f32 || !a.resid || a.N > 1024 || (a.C2 && (((uintptr_t)a.C2 & 7) || (a.ldc2 % 4))) || ((uintptr_t)a.stats_out & 7)) return false;
     }
     if (a.lse_part && (conv || !a.out_f32 || a.resid || a.C2 || a.stats_out || a.act != 0 || ((uintptr_t)a.lse_part & 7) || (a.lse_ld % 2) || a.lse_ld < 8 * cdiv(a.N, TB))) return false;
+    if (a.amax_part && (conv || !a.out_f32 || a.resid || a.C2 || a.stats_out || a.lse_part || a.act != 0 || ((uintptr_t)a.amax_part & 7) || (a.amax_ld % 2) || a.amax_ld < 8 * cdiv(a.N, TB))) return false;
     if ((long)a.N * a.ldw * 2 >= (1l << 32)) return false;                                             // 32-bit source offsets
     if (conv) {
         if ((a.Cin % BK) != 0 || a.Fout <= 0 || a.Tout <= 0) return false;
@@ -1191,6 +1204,12 @@ int gemm_8p_launch(const GemmArgs& a, bool conv, hipStream_t stream) {
         (void)attr_t;
         if (a.act == 3) launch_dense(PF_8P, gemm8p_kernel<false, 3>, dim3(grid), dim3(512), (size_t)2 * BUF, stream, a);
         else launch_dense(PF_8P_GELU, gemm8p_kernel<false, 4>, dim3(grid), dim3(512), (size_t)2 * BUF, stream, a);
+        return MI_OK;
+    }
+    if (a.out_f32 && a.amax_part) {
+        const bool attr_m = set_lds_attr(gemm8p_kernel<false, 0, true, false, false, false, true>, 2 * BUF);
+        (void)attr_m;
+        launch_dense(PF_8P_AMAX, gemm8p_kernel<false, 0, true, false, false, false, true>, dim3(grid), dim3(512), (size_t)2 * BUF, stream, a);
         return MI_OK;
     }
     if (a.out_f32 && a.lse_part) {

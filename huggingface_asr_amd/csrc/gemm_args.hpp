@@ -39,6 +39,10 @@ struct GemmArgs {
     // at lse_part[m * lse_ld + 2 * (n0 / 64 + wave column)] — the row log-sum-exp without a second pass over the (M, N) logits.  lse_ld >= 8 * ceil(N / 256); every pair
     // of a row is written ((-inf, 0) for blocks entirely beyond N).
     float* lse_part; int lse_ld;
+    // Greedy-CTC form of the same epilogue (mi_gemm_argmax_bf16): per row and 64-column wave block the (max, index) pair of the columns < N under common.hpp's argmax
+    // order, the index bit-cast beside the float, at amax_part[m * amax_ld + 2 * (n0 / 64 + wave column)] — same layout and size as the LSE partials; blocks entirely
+    // beyond N leave (NaN, -1), which the merge skips.  C is NOT stored (and may be null).
+    float* amax_part; int amax_ld;
 };
 constexpr int LN_STATS_STRIDE = 32;       // floats per row of a partial-statistics buffer (16 (sum, sumsq) pairs)
 
@@ -58,9 +62,9 @@ int gemm_8p128_launch(const GemmArgs& a, int ring, hipStream_t stream);
 // hipExtLaunchKernelGGL and the slot's (start, stop) events, so the pair carries the DISPATCH's own begin / end timestamps — the quantity rocprofv3 --kernel-trace
 // reports — instead of bracketing the launch with two hipEventRecord markers, which also times the gap between the markers and the kernel.
 // `family`: 0 gemm8p 256x256 (bf16 out, no activation), 1 gemm8p + GELU epilogue, 2 gemm8p implicit-GEMM conv, 3 gemm8p fp32 out (CTC head), 4 gemm8p128 (N = 512 class),
-//           5 gemm_glds, 6 gemm_bf16 (generic)
+//           5 gemm_glds, 6 gemm_bf16 (generic), 7 gemm8p argmax epilogue (CTC head without logits)
 extern "C" int mi_profile_take_events(hipEvent_t* start, hipEvent_t* stop, int family);
-enum { PF_8P = 0, PF_8P_GELU = 1, PF_8P_CONV = 2, PF_8P_OUT32 = 3, PF_8P128 = 4, PF_GLDS = 5, PF_GENERIC = 6, PF_COUNT = 7 };
+enum { PF_8P = 0, PF_8P_GELU = 1, PF_8P_CONV = 2, PF_8P_OUT32 = 3, PF_8P128 = 4, PF_GLDS = 5, PF_GENERIC = 6, PF_8P_AMAX = 7, PF_COUNT = 8 };
 
 template <typename F, typename... Args>
 inline void launch_dense(int family, F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {

@@ -422,3 +422,45 @@ extern "C" int mi_gemm_lse_f32(const void* A, long lda, const void* W, long ldw,
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
+
+// ---- CTC head for greedy transcription: the per-frame class out of the GEMM's epilogue, no logits.  The 256x256 kernel's AMAX epilogue leaves one (max, index) pair per
+// row and 64-column block in `workspace` (the LSE partials' layout, the index bit-cast beside the float) and stores no C — at 8000 x 5001 that is 2.6 MB written instead
+// of 160 MB; the second launch folds a row's pairs (ascending columns per lane, then across the 16 lanes) with the order every argmax of the library shares
+// (common.hpp argmax_*), so best[m] is what mi_row_argmax finds in the fp32 output of mi_gemm_bf16 on the same operands.
+namespace {
+__global__ __launch_bounds__(256) void argmax_merge_kernel(const float* __restrict__ part, int ld, int npair, int* __restrict__ best, int M) {
+    const int g = threadIdx.x & 15;                                   // 16 lanes per row (one DPP row), 16 rows per block
+    const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const float* pr = part + (long)min(row, M - 1) * ld;
+    amax_t k = ARGMAX_EMPTY;
+    for (int t = g; t < npair; t += 16) {
+        const f32x2 q = *reinterpret_cast<const f32x2*>(pr + 2 * t);
+        const float qi = q.y;                                         // (a copy: __builtin_bit_cast of the vector ELEMENT expression reads element 0)
+        const int i = __builtin_bit_cast(int, qi);
+        if (i >= 0) k = argmax_max(k, argmax_key(q.x, i));            // (blocks entirely beyond N left index -1)
+    }
+    k = argmax_row16(k);
+    if (g == 0 && row < M) best[row] = argmax_index(k);
+}
+}  // namespace
+
+extern "C" size_t mi_gemm_argmax_workspace_floats(int M, int N) { return mi_gemm_lse_workspace_floats(M, N); }
+
+// MI_ERR_UNSUPPORTED: the shape is outside the 256x256 kernel (the caller runs mi_gemm_bf16 into a scratch + mi_row_argmax).
+extern "C" int mi_gemm_argmax_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, int* best, float* workspace, int M, int N, int K, hipStream_t stream) {
+    MI_ENTER();
+    if (!A || !W || !best || !workspace) return MI_ERR_ARG;
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.lda = lda; a.W = (const bf16_t*)W; a.ldw = ldw; a.bias = bias; a.bias_mode = bias ? 1 : 0;
+    a.C = nullptr; a.ldc = (N + 3) & ~3; a.out_f32 = 1; a.alpha = 1.f; a.act = 0; a.M = M; a.N = N; a.K = K;
+    a.amax_part = workspace; a.amax_ld = 8 * ((N + 255) / 256);
+    if (!gemm_8p_supported(a, false)) return MI_ERR_UNSUPPORTED;
+    const int slot = mi_profile_hook_begin(stream, 2.0 * M * N * K);
+    const int rc = gemm_8p_launch(a, false, stream);
+    if (slot >= 0) mi_profile_hook_end(slot, stream);
+    if (rc != MI_OK) return rc;
+    MI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(argmax_merge_kernel, dim3((M + 15) / 16), dim3(256), 0, stream, workspace, a.amax_ld, a.amax_ld / 2, best, M);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}

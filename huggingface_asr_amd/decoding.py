@@ -30,6 +30,19 @@ class GenerationConfigCustom(GenerationConfig):
         self.apply_eos_space_trick = apply_eos_space_trick
 
 
+def ctc_greedy_decode(logits: torch.Tensor, blank, pad_token_id) -> torch.Tensor:
+    """Drop-in for the reference's ctc_greedy_decode (src/utilities/eval_utils.py:37-43; the CTC trainer's preprocess_logits_for_metrics): logits (B, T, V+1) ->
+    (B, T) int64 on the logits' device — per utterance the argmax path with repeats merged and `blank` removed, then pad_token_id.  Every frame counts, padded ones
+    included, as there.  Two kernel launches (ops.ctc_greedy_decode) instead of a host loop over device elements; `ops.ctc_greedy_decode` also returns the token
+    counts and takes frame lengths."""
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_greedy_decode (HIP) needs a device tensor; there is no CPU fallback")
+    from . import ops
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    return ops.ctc_greedy_decode(logits, int(blank), int(pad_token_id))["tokens"]
+
+
 class CTCRescorerLogitsProcessor(LogitsProcessor):
     FULL_STATE_BYTES = 1 << 30      # keep every (hypothesis, token) chain between calls while that tensor stays below this (else: re-run the selected chains)
 

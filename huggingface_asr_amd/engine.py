@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .packing import _enc_map, encoder_specs, mapped_fp32, packed, relative_position_table, rotary_tables
 from .shapes import GATE_SHARE, context_mode
 
@@ -91,6 +91,9 @@ class EBranchformerEngine:
         self.wide_tiles = False
         self.head_lse = False                     # True: fp32 logits come with their row log-sum-exp out of the head GEMM's epilogue (`out["lse"]`, mi_ebf_forward_lse). Built for VERDICT r3
                                                   # item 7 and measured to buy nothing (the epilogue costs what the separate pass does): off by default, bench.py --head-lse
+        self.head_argmax = True                   # transcribe(): True = the per-frame argmax comes out of the head GEMM's epilogue and no logits are written (mi_gemm_argmax_bf16);
+                                                  # False = head GEMM into an fp32 scratch + one argmax pass over it.  Same ids either way.  On: measured 4.577 against 4.602 ms per step,
+                                                  # base encoder at 32 x 10 s, leg spread 0.003 ms (profiles/r06_a; DESIGN §4 'Greedy transcription')
         self.weights = {}
         self._table = None
         self._ws = {}
@@ -218,12 +221,14 @@ class EBranchformerEngine:
             self._ws[slot] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws[slot]
 
+    def _head_fusable(self) -> bool:
+        """the head shapes mi_gemm_argmax_bf16 takes (the 256 x 256 kernel: K = hidden size a multiple of 64, at least two K tiles); others run GEMM + argmax pass"""
+        d = self.cfg["hidden_size"]
+        return d % 64 == 0 and d >= 128
+
     # ------------------------------------------------------------------ forward
-    def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
-        """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
-        Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also
-        hidden_states = the L+1 tensors HF returns for output_hidden_states (every layer's input, then the last hidden state).
-        `slot` selects a private workspace: calls issued on different streams must use different slots."""
+    def _prepare(self, feats, slot):
+        """what every whole-encoder call needs: the config struct, the slot's workspace and the position tables for this batch shape"""
         if self._table is None:
             raise RuntimeError("EBranchformerEngine: load_state_dict() first")
         if not feats.is_cuda:
@@ -237,7 +242,7 @@ class EBranchformerEngine:
             raise ValueError("input too short for the conv sub-sampling")
         if self.ctx_mode == 2:
             self._check_shared_gate(T)
-        d, V1 = c["hidden_size"], c["vocab_size"] + 1
+        d = c["hidden_size"]
         ws = self._workspace(cs, slot)
         pos = self._pos_table(T2)
         posp, compute = None, 0
@@ -250,6 +255,50 @@ class EBranchformerEngine:
             if compute and slot != 0:
                 raise RuntimeError("multi-stream use: run one forward on slot 0 first (it fills the shared position-projection cache)")
             self._posp_valid[T2] = self.weights_version
+        return feats, cs, T2, ws, pos, posp, compute
+
+    def transcribe(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, span="valid", pad_id=0, slot=0, want_hidden=False, return_frames=False,
+                   dtype=torch.int64):
+        """CTC greedy transcription on the device: feats (B,T,F) -> dict(tokens (B,T2) `dtype` = the token ids then pad_id, n_tokens (B) int32, best (B,T2) int32 = the
+        per-frame classes, inner_len, outer_len[, frames (B,T2) int32 = the frame each token starts at, then -1][, last_hidden]).  Blank = the last class.
+        span "valid": frames beyond outer_len (the lengths the CTC loss is trained with) are cut; "all": every frame counts, as in the reference's ctc_greedy_decode.
+        With `head_argmax` on (the default; and a head that fits the fused kernel) no logits tensor is allocated; `slot` as in forward()."""
+        if span not in ("valid", "all"):
+            raise ValueError(f"transcribe: span must be 'valid' or 'all', got {span!r}")
+        feats, cs, T2, ws, pos, posp, compute = self._prepare(feats, slot)
+        B, c = feats.shape[0], self.cfg
+        d, V1, L = c["hidden_size"], c["vocab_size"] + 1, _lib.lib()
+        hidden = torch.empty((B, T2, d), dtype=torch.float32, device=self.device) if want_hidden else None
+        lens = torch.empty((2, B), dtype=torch.int32, device=self.device)
+        best = torch.empty((B, T2), dtype=torch.int32, device=self.device)
+        if feat_lengths is not None:
+            feat_lengths = feat_lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        p = lambda t: None if t is None else t.data_ptr()
+        cs.logits_f32 = 1                               # the head's scratch, when one is needed, is fp32 whatever `logits_dtype` says: both head forms then take the argmax of the same fp32 values
+        fused = bool(self.head_argmax) and self._head_fusable()
+        aws = torch.empty((int(L.mi_gemm_argmax_workspace_floats(B * T2, V1)),), dtype=torch.float32, device=self.device) if fused else None
+        scratch = None if fused else torch.empty((B * T2, cs.logits_ld), dtype=torch.float32, device=self.device)
+        call = lambda: L.mi_ebf_forward_greedy(C.byref(cs), self._table, feats.data_ptr(), p(feat_lengths), p(pos), p(posp), compute, ws.data_ptr(), ws.numel(), p(hidden),
+                                               best.data_ptr(), p(aws), p(scratch), lens[0].data_ptr(), lens[1].data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rc = call()
+        if rc == _lib.ERR_UNSUPPORTED and scratch is None:      # the fused entry refused for a reason _head_fusable does not restate: lend the scratch and run again, never raise
+            scratch = torch.empty((B * T2, cs.logits_ld), dtype=torch.float32, device=self.device)
+            rc = call()
+        _lib.check(rc, "mi_ebf_forward_greedy")
+        out = ops.ctc_collapse(best, V1 - 1, pad_id, lens[1] if span == "valid" else None, return_frames=return_frames, dtype=dtype)
+        out.update(best=best, inner_len=lens[0], outer_len=lens[1])
+        if want_hidden:
+            out["last_hidden"] = hidden
+        return out
+
+    def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
+        """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
+        Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also
+        hidden_states = the L+1 tensors HF returns for output_hidden_states (every layer's input, then the last hidden state).
+        `slot` selects a private workspace: calls issued on different streams must use different slots."""
+        feats, cs, T2, ws, pos, posp, compute = self._prepare(feats, slot)
+        B, c = feats.shape[0], self.cfg
+        d, V1 = c["hidden_size"], c["vocab_size"] + 1
         # rows padded to a multiple of 8 elements (16-B stores in the GEMM epilogue); callers get the (B,T2,V+1) view
         lbuf = torch.empty((B, T2, cs.logits_ld), dtype=self.logits_dtype, device=self.device) if want_logits else None
         logits = lbuf[..., :V1] if want_logits else None

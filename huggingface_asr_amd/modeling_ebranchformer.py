@@ -260,6 +260,25 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
             return (loss, out["logits"]) + ((hidden_states,) if hidden_states is not None else ())
         return CausalLMOutput(loss=loss, logits=out["logits"], hidden_states=hidden_states, attentions=None)
 
+    def transcribe(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, span: str = "valid"):
+        """CTC greedy transcription on the device (eval mode only): -> (tokens (B, T') int64 = each utterance's token ids then config.pad_token_id, n_tokens (B) int32).
+        span "valid" cuts every utterance at its un-padded output length (the lengths the CTC loss is trained with); "all" counts every frame, which is what the
+        reference's ctc_greedy_decode does with this model's logits.  Runs engine.transcribe: with `model._get_engine(device).head_argmax` on (the default), the head's argmax comes out of its GEMM and no logits tensor is produced; otherwise the head
+        GEMM fills an fp32 scratch and one argmax pass reads it (the same ids)."""
+        if span not in ("valid", "all"):
+            raise ValueError(f"transcribe: span must be 'valid' or 'all', got {span!r}")
+        if self.training:
+            raise RuntimeError("transcribe() is an inference call: put the model in eval mode first (model.eval())")
+        if not input_values.is_cuda:
+            raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): inputs must be on the GPU; there is no CPU fallback")
+        pad = self.config.pad_token_id
+        if pad is None:
+            raise ValueError("transcribe: config.pad_token_id is not set")
+        eng = self._get_engine(input_values.device)
+        feat_len = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        out = eng.transcribe(input_values, feat_len, span=span, pad_id=int(pad))
+        return out["tokens"], out["n_tokens"]
+
     def forward(
         self,
         input_values: Optional[torch.Tensor],

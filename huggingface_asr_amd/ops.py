@@ -343,6 +343,90 @@ def row_lse(x):
     return out
 
 
+def row_argmax(x):
+    """x (M, V) f32|bf16 (last dim contiguous, any row stride) -> (M) int32 = torch.argmax(x, -1): lowest index among equal maxima, the first NaN beats every number,
+    an all -inf row gives 0 (mi_row_argmax: one pass over x)."""
+    _req(x)
+    if x.dtype not in (torch.float32, BF16) or x.dim() != 2 or x.stride(1) != 1:
+        raise TypeError("row_argmax: a 2-D fp32 / bf16 tensor with contiguous rows")
+    M, V = x.shape
+    out = torch.empty((M,), device=x.device, dtype=torch.int32)
+    rc = _lib.lib().mi_row_argmax(x.data_ptr(), x.stride(0), 0 if x.dtype == torch.float32 else 1, V, out.data_ptr(), M, _stream())
+    _lib.check(rc, "mi_row_argmax")
+    return out
+
+
+def gemm_argmax(a, w, bias):
+    """the CTC head without its logits: -> (M) int32 = argmax_n (a W^T + b)[m, n] out of the GEMM's epilogue (mi_gemm_argmax_bf16: no (M, N) tensor is written);
+    shapes outside that kernel: the fp32 GEMM into a scratch followed by row_argmax."""
+    _req(a, BF16); _req(w, BF16)
+    M, K = a.shape
+    N = w.shape[0]
+    L = _lib.lib()
+    best = torch.empty((M,), device=a.device, dtype=torch.int32)
+    ws = torch.empty((int(L.mi_gemm_argmax_workspace_floats(M, N)),), device=a.device, dtype=torch.float32)
+    rc = L.mi_gemm_argmax_bf16(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias), best.data_ptr(), ws.data_ptr(), M, N, K, _stream())
+    if rc == _lib.ERR_UNSUPPORTED:
+        return row_argmax(gemm(a, w, bias, out_dtype=torch.float32))
+    _lib.check(rc, "mi_gemm_argmax_bf16")
+    return best
+
+
+def _lengths_i32(lengths, B, device):
+    if lengths is None:
+        return None
+    lengths = lengths.to(device=device, dtype=torch.int32).contiguous()
+    if lengths.shape != (B,):
+        raise ValueError(f"lengths: expected shape ({B},), got {tuple(lengths.shape)}")
+    return lengths
+
+
+def ctc_collapse(best, blank, pad_id, lengths=None, *, return_frames=False, dtype=torch.int64):
+    """best (B, T) int32 per-frame classes -> dict(tokens (B, T) `dtype`, n_tokens (B) int32[, frames (B, T) int32]): frame t is kept iff t < n_b, best != blank and
+    (t == 0 or best[t] != best[t-1]), n_b = lengths[b] or T; the kept ids in order, then pad_id (frames: where each kept token starts, then -1).  mi_ctc_collapse."""
+    _req(best, torch.int32)
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError("ctc_collapse: token dtype int32 or int64")
+    best = best.contiguous()
+    B, T = best.shape
+    lengths = _lengths_i32(lengths, B, best.device)
+    tokens = torch.empty((B, T), device=best.device, dtype=dtype)
+    n = torch.empty((B,), device=best.device, dtype=torch.int32)
+    frames = torch.empty((B, T), device=best.device, dtype=torch.int32) if return_frames else None
+    rc = _lib.lib().mi_ctc_collapse(best.data_ptr(), B, T, _p(lengths), int(blank), int(pad_id), tokens.data_ptr(), int(dtype == torch.int64), n.data_ptr(), _p(frames), _stream())
+    _lib.check(rc, "mi_ctc_collapse")
+    out = dict(tokens=tokens, n_tokens=n)
+    if return_frames:
+        out["frames"] = frames
+    return out
+
+
+def ctc_greedy_decode(logits, blank, pad_id, lengths=None, *, return_frames=False, dtype=torch.int64):
+    """CTC greedy transcription of logits (B, T, V+1) f32|bf16 (last dim contiguous, any row / batch strides): per-frame argmax, repeats merged, blanks dropped.
+    -> dict(tokens, n_tokens, best (B, T) int32[, frames]) as ctc_collapse; with lengths=None every frame counts (the reference's ctc_greedy_decode,
+    src/utilities/eval_utils.py:37-43).  One pass over the logits + one block per utterance (mi_ctc_greedy)."""
+    _req(logits)
+    if logits.dtype not in (torch.float32, BF16) or logits.dim() != 3:
+        raise TypeError("ctc_greedy_decode: (B, T, V+1) fp32 / bf16 logits")
+    if logits.stride(2) != 1:
+        logits = logits.contiguous()
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError("ctc_greedy_decode: token dtype int32 or int64")
+    B, T, V1 = logits.shape
+    lengths = _lengths_i32(lengths, B, logits.device)
+    best = torch.empty((B, T), device=logits.device, dtype=torch.int32)
+    tokens = torch.empty((B, T), device=logits.device, dtype=dtype)
+    n = torch.empty((B,), device=logits.device, dtype=torch.int32)
+    frames = torch.empty((B, T), device=logits.device, dtype=torch.int32) if return_frames else None
+    rc = _lib.lib().mi_ctc_greedy(logits.data_ptr(), logits.stride(1), logits.stride(0), 0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(lengths), int(blank), int(pad_id),
+                                  best.data_ptr(), tokens.data_ptr(), int(dtype == torch.int64), n.data_ptr(), _p(frames), _stream())
+    _lib.check(rc, "mi_ctc_greedy")
+    out = dict(tokens=tokens, n_tokens=n, best=best)
+    if return_frames:
+        out["frames"] = frames
+    return out
+
+
 def ctc_loss(logits, labels, in_len, *, reduction="mean", zero_infinity=False, lse=None):
     """logits (B,T,V+1) f32|bf16 (blank = last class), labels (B,U) int64 (<0 = padding), in_len (B) int32.
     Returns (loss scalar tensor | per-utterance nll for reduction='none', nll (B), tgt_len (B))."""

@@ -34,7 +34,7 @@ void mi_profile_reset(void);
 int mi_profile_count(void);
 int mi_profile_summary(double* total_ms, double* total_flops);
 int mi_profile_calibrate(mi_stream_t stream, int n, double* median_ms);   /* event pair around an EMPTY kernel, median of n: what the bracket adds + the empty kernel's ~1.3 us */
-int mi_profile_summary_family(int family, double* total_ms, double* total_flops, int* launches);   /* family < 0: all; 0 gemm8p, 1 gemm8p+GELU, 2 gemm8p conv, 3 gemm8p fp32 out, 4 gemm8p128, 5 gemm_glds, 6 generic */
+int mi_profile_summary_family(int family, double* total_ms, double* total_flops, int* launches);   /* family < 0: all; 0 gemm8p, 1 gemm8p+GELU, 2 gemm8p conv, 3 gemm8p fp32 out, 4 gemm8p128, 5 gemm_glds, 6 generic, 7 gemm8p argmax epilogue */
 
 /* ---- nn.Linear / lm_head / projections: C[M,N] = epi(A[M,K] * W[N,K]^T), bf16 in, fp32 accumulate (MFMA).
  * replaces: every nn.Linear on the path — reference src/models/encoders/e_branchformer.py:96-98,139,212-216,247,456-457;
@@ -254,6 +254,25 @@ int mi_row_lse(const void* x, long ld, int dtype, int V, float* lse, int M, mi_s
 size_t mi_gemm_lse_workspace_floats(int M, int N);
 int mi_gemm_lse_f32(const void* A, long lda, const void* W, long ldw, const float* bias, float* C, long ldc, float* lse, float* workspace,
                     int M, int N, int K, mi_stream_t stream);
+/* ---- CTC greedy transcription. replaces: ctc_greedy_decode (src/utilities/eval_utils.py:37-43: torch.argmax, then a Python groupby over a device tensor), the step
+ * between the CTC head and a transcript in src/trainers/train_ctc_asr.py:77-85.
+ * best[m] = argmax over the V1 columns of row m with torch.argmax's rules: the lowest index among equal maxima, a NaN beats every number (the first NaN wins), an
+ * all -inf row gives 0.  dtype 0 fp32 / 1 bf16; one pass over the rows. */
+int mi_row_argmax(const void* x, long ld, int dtype, int V1, int* best, int M, mi_stream_t stream);
+/* best (B, T) int32 -> frame t of utterance b is kept iff t < n_b, best != blank and (t == 0 or best[t] != best[t-1]); n_b = lengths[b] (int32, clamped to [0, T]) or T
+ * when lengths is null.  tokens (B, T) int32 (tokens_dtype 0) / int64 (1): the kept ids in order, then pad_id; n_tokens (B) int32; frames (B, T) int32 (nullable): the
+ * frame each kept token starts at, then -1.  tokens must not alias best.  One block per utterance, any T, no atomics. */
+int mi_ctc_collapse(const int* best, int B, int T, const int* lengths, int blank, long pad_id, void* tokens, int tokens_dtype, int* n_tokens, int* frames,
+                    mi_stream_t stream);
+/* the two above over logits (B, T, V1) with element strides (ld_batch, ld_row); best (B, T) int32: scratch of the caller, left holding the per-frame classes */
+int mi_ctc_greedy(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, long pad_id,
+                  int* best, void* tokens, int tokens_dtype, int* n_tokens, int* frames, mi_stream_t stream);
+/* the CTC head without its logits: best[m] = argmax_n (A W^T + b)[m][n] out of the 256 x 256 GEMM's epilogue, which leaves one (max, index) pair per row and 64 columns
+ * in `workspace` (mi_gemm_argmax_workspace_floats(M, N) floats) and stores no C; a small second launch folds a row's pairs.  Equals mi_row_argmax over the fp32 output of
+ * mi_gemm_bf16 on the same operands.  MI_ERR_UNSUPPORTED outside that kernel's shapes (K % 64, K >= 128, 16-B aligned operands): the caller runs mi_gemm_bf16 into a
+ * scratch + mi_row_argmax. */
+size_t mi_gemm_argmax_workspace_floats(int M, int N);
+int mi_gemm_argmax_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, int* best, float* workspace, int M, int N, int K, mi_stream_t stream);
 int mi_ctc_loss_fwd(const void* logits, long ld_b, long ld_t, int dtype, const float* lse, int T,
                     const long* labels, int U, const int* in_len, int blank, int B,
                     int reduction, int zero_infinity, float* nll, int* tgt_len, float* loss, mi_stream_t stream);
@@ -598,6 +617,14 @@ int mi_ebf_forward_lse(const mi_ebf_config* cfg, const void* const* weights, con
                        const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
                        float* last_hidden, void* logits, int* inner_len, int* outer_len, float* hidden_states,
                        float* lse, float* lse_workspace, mi_stream_t stream);
+/* the encoder + CTC head ending in the per-frame classes instead of logits: best (B*T2) int32 = argmax over the V+1 classes (mi_row_argmax's rules) — what
+ * mi_ctc_collapse turns into token ids.  argmax_workspace (mi_gemm_argmax_workspace_floats(B*T2, V+1) floats, nullable): the head runs as mi_gemm_argmax_bf16 and writes
+ * no logits.  head_scratch ((B*T2, logits_ld) in the config's logits dtype — engine.transcribe always sets logits_f32 for this call, so both head forms rank the same fp32 values —, nullable): where the head runs as mi_gemm_bf16 + mi_row_argmax — when argmax_workspace is
+ * null or the shape is outside the fused kernel's (hidden size d: d % 64 != 0 or d < 128).  Checked before anything runs: both null is MI_ERR_ARG, a head outside
+ * the fused kernel's shapes without head_scratch is MI_ERR_UNSUPPORTED. */
+int mi_ebf_forward_greedy(const mi_ebf_config* cfg, const void* const* weights, const float* feats, const int* feat_lengths,
+                          const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
+                          float* last_hidden, int* best, float* argmax_workspace, void* head_scratch, int* inner_len, int* outer_len, mi_stream_t stream);
 
 #ifdef __cplusplus
 }
