@@ -30,7 +30,7 @@ class LnRedDesc(C.Structure):
 
 class Gpt2Config(C.Structure):
     """mirror of mi_gpt2_config (include/hfasr_hip.h)"""
-    _fields_ = [("d", i32), ("H", i32), ("L", i32), ("V", i32), ("eps", f32), ("step_form", i32)]
+    _fields_ = [("d", i32), ("H", i32), ("L", i32), ("V", i32), ("eps", f32), ("step_form", i32), ("act", i32)]
 
 
 GLOBAL_SLOTS, LAYER_SLOTS = 24, 64
@@ -170,6 +170,10 @@ SIGNATURES = {
     "mi_mask_noise_f32": [vp, i64, vp, i32, i32, f32, C.c_uint, C.c_uint, vp],
     "mi_gpt2_step_workspace_bytes": [C.POINTER(Gpt2Config), i32, i32],
     "mi_gpt2_step": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, sz, vp, i64, vp],
+    "mi_decoder_step": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
+    "mi_linear_rows_workspace_bytes": [i32, i32, i32],
+    "mi_linear_rows": [vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp],
+    "mi_greedy_advance": [vp, vp, i64, i32, i64, i64, vp, vp, vp, i32, vp],
     "mi_kv_cache_reorder": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi_ctc_prefix_advance": [vp, i32, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp],
     "mi_ctc_prefix_score_full": [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, i64, i32, vp, vp, vp, vp],
@@ -206,7 +210,7 @@ def lib():
             fn.argtypes = args
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
-                                          "mi_gpt2_step_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats") else i32
+                                          "mi_gpt2_step_workspace_bytes", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None
         h.mi_profile_reset.argtypes = []; h.mi_profile_reset.restype = None

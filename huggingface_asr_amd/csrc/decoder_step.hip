@@ -150,7 +150,7 @@ int skinny(const SkArgs& a, hipStream_t st) {
     return MI_OK;
 }
 
-// ---- attention of at most 8 new rows over cached keys (token step): one block per (row, head).  The MFMA attention kernel pads these rows to a 128-query tile and walks the
+// ---- attention of the new rows over cached keys (token step; any number of rows): one block per (row, head).  The MFMA attention kernel pads these rows to a 128-query tile and walks the
 // keys in dependent steps (9-12 us over 250 encoder frames); here LPK = HD / 8 lanes share a key (16-B pieces of its K and V rows), the block's four waves split the keys, a wave
 // requests all 2 NB pieces of a batch before it uses the first, soft-max in fp32 with a running max across batches, key slots and waves merged through LDS.
 constexpr int DA_WAVES = 4;
@@ -281,8 +281,14 @@ bool gpt2_step_fused_ok(const mi_gpt2_config& c, int B, int U);
 size_t gpt2_step_fused_floats(const mi_gpt2_config& c, int M);
 int gpt2_step_fused(const mi_gpt2_config& c, const void* const* weights, const long* ids, float emb_scale, int M, int past, int Lmax, void* const* kcache, void* const* vcache,
                     const void* const* cross_kv, int T_enc, const int* enc_len, float* fws, bf16_t* hid, hipStream_t st);
+// linear_rows.hip: the rows-streaming linear of the streaming form of the token step
+size_t linear_rows_workspace_floats(int M, int N, int K);
+int linear_rows(const bf16_t* x, long ldx, const bf16_t* W, long ldw, const float* bias, int act, float* out32, long ldo32, int accumulate, bf16_t* out16, long ldo16,
+                bf16_t* kc, bf16_t* vc, int U, int past, int Lmax, int dkv, int M, int N, int K, float* workspace, size_t workspace_floats, hipStream_t st);
 namespace {
-struct StepWs { float* x; bf16_t *a, *qkv, *ctx, *qq, *m, *hid; float* fws; size_t bytes; };
+constexpr int ROWS_MAXM = 64;
+bool step_streams(const mi_gpt2_config& c, int M, int U) { return c.step_form == 2 && U == 1 && M <= ROWS_MAXM; }
+struct StepWs { float* x; bf16_t *a, *qkv, *ctx, *qq, *m, *hid; float* fws; float* part; size_t part_floats; size_t bytes; };
 StepWs carve(const mi_gpt2_config& c, int M, int B, int U, void* base) {
     Carver k{(char*)base, 0};
     StepWs w;
@@ -294,6 +300,12 @@ StepWs carve(const mi_gpt2_config& c, int M, int B, int U, void* base) {
     w.m = (bf16_t*)k.take((size_t)M * 4 * c.d * 2);
     w.hid = (bf16_t*)k.take((size_t)B * c.d * 2);
     w.fws = gpt2_step_fused_ok(c, B, U) ? (float*)k.take(gpt2_step_fused_floats(c, M) * sizeof(float)) : nullptr;
+    w.part = nullptr; w.part_floats = 0;
+    if (step_streams(c, M, U)) {                                       // the K-split partials of the largest linear of the step
+        const int shapes[5][2] = {{3 * c.d, c.d}, {c.d, c.d}, {4 * c.d, c.d}, {c.d, 4 * c.d}, {c.V, c.d}};
+        for (auto& s : shapes) { const size_t f = linear_rows_workspace_floats(M, s[0], s[1]); w.part_floats = f > w.part_floats ? f : w.part_floats; }
+        w.part = (float*)k.take(w.part_floats * sizeof(float));
+    }
     w.bytes = k.off;
     return w;
 }
@@ -307,12 +319,15 @@ extern "C" size_t mi_gpt2_step_workspace_bytes(const mi_gpt2_config* cfg, int B,
 // weights: [wte f32 (V,d), pos f32 (n_pos,d), lnf_g, lnf_b, lm_head bf16 (V,d)] then per layer 18 pointers in the order
 //   ln1_g, ln1_b, wqkv, bqkv, wo, bo, lnc_g, lnc_b, wq, bq, wco, bco, ln2_g, ln2_b, wfc, bfc, wpr, bpr     (matrices bf16 (out,in), vectors f32)
 // ids_new (B,U) int64; kcache / vcache: L pointers to (B, Lmax, d) bf16; cross_kv: L pointers to (B*T_enc, 2d) bf16 [K | V];
-// logits (B, ld_logits) f32 of the LAST new position.  Appends the new tokens' K/V at rows [past, past + U).
-extern "C" int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
-                            void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
-                            float emb_scale, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
+// logits (B, ld_logits) f32 of the LAST new position (+ head_bias (V) f32 when not null: 0 / -inf token suppression).  Appends the new tokens' K/V at rows [past, past + U).
+// cfg->act selects the MLP activation (0 gelu_new, 1 erf-GELU: the Whisper decoder block, which is this block with separate q / k / v matrices packed into wqkv).
+extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
+                               void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                               float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
     MI_ENTER();
     const mi_gpt2_config& c = *cfg;
+    if (c.act < 0 || c.act > 1 || c.step_form < 0 || c.step_form > 2) return MI_ERR_ARG;
+    const int mlp_act = c.act == 1 ? 1 : 2;                           // mi_gemm_bf16 / linear_rows activation codes
     if (B <= 0 || U <= 0 || past < 0 || past + U > Lmax || c.L <= 0 || c.L > MAX_LAYERS || c.d % c.H || (c.d % 8)) return MI_ERR_ARG;
     const int hd = c.d / c.H;
     if (hd != 64 && hd != 128) return MI_ERR_UNSUPPORTED;
@@ -326,16 +341,43 @@ extern "C" int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weight
     auto ln = [&](const float* x, long ldx, const float* g, const float* b, bf16_t* out, int rows) {
         return mi_layernorm_chain(x, ldx, nullptr, 1, nullptr, nullptr, 0.f, nullptr, 0, g, b, c.eps, out, d, nullptr, 0, nullptr, nullptr, nullptr, 0, rows, d, st);
     };
-    if (c.step_form != 1 && w.fws) {
+    if (c.step_form == 0 && c.act == 0 && w.fws) {
         // ---- fused token step (decoder_fused.hip): three launches per layer, every cross-workgroup reduction folded into the next launch's prologue (the embedding too)
         RUN(gpt2_step_fused(c, weights, ids_new, emb_scale, M, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, w.fws, w.hid, st));
         SkArgs a{}; a.x16 = w.hid; a.ldx16 = d; a.W = (const bf16_t*)weights[4]; a.ldw = d; a.out32 = logits; a.ldo32 = ld_logits; a.M = B; a.N = c.V; a.K = d; a.act = 0;
+        a.bias = head_bias;
         RUN(skinny(a, st));
         MI_CHECK_LAUNCH();
         return MI_OK;
     }
     RUN(mi_embed_tokens(ids_new, Gf(0), emb_scale, Gf(1), past, U, d, M, c.V, w.x, st));
-    if (M <= SK_MAXM && (d % 8) == 0 && 4 * d <= 2048) {
+    if (step_streams(c, M, U)) {
+        // ---- streaming token step (linear_rows.hip): up to 64 rows, one new token each; every linear reads its weights once, spread over the chip by N and K
+        auto lin = [&](const bf16_t* in, int K, const void* W, const float* bias, int N, int act, float* o32, long ldo32, int accumulate, bf16_t* o16, bf16_t* kc, bf16_t* vc) {
+            return linear_rows(in, K, (const bf16_t*)W, K, bias, act, o32, ldo32, accumulate, o16, N, kc, vc, 1, past, Lmax, d, M, N, K, w.part, w.part_floats, st);
+        };
+        for (int l = 0; l < c.L; ++l) {
+            bf16_t* kc = (bf16_t*)kcache[l];
+            bf16_t* vc = (bf16_t*)vcache[l];
+            const bf16_t* ckv = (const bf16_t*)cross_kv[l];
+            RUN(ln(w.x, d, Lf(l, 0), Lf(l, 1), w.a, M));
+            RUN(lin(w.a, d, Lw(l, 2), Lf(l, 3), 3 * d, 0, nullptr, 0, 0, w.qkv, kc, vc));
+            RUN(decode_attn(DecAttnArgs{w.qkv, 3 * d, kc, vc, d, (long)Lmax * d, nullptr, w.ctx, d, M, U, c.H, past, 1, 0, scale}, hd, st));
+            RUN(lin(w.ctx, d, Lw(l, 4), Lf(l, 5), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
+            RUN(ln(w.x, d, Lf(l, 6), Lf(l, 7), w.a, M));
+            RUN(lin(w.a, d, Lw(l, 8), Lf(l, 9), d, 0, nullptr, 0, 0, w.qq, nullptr, nullptr));
+            RUN(decode_attn(DecAttnArgs{w.qq, d, ckv, ckv + d, 2 * d, (long)T_enc * 2 * d, enc_len, w.ctx, d, M, U, c.H, 0, 0, T_enc, scale}, hd, st));
+            RUN(lin(w.ctx, d, Lw(l, 10), Lf(l, 11), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
+            RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
+            RUN(lin(w.a, d, Lw(l, 14), Lf(l, 15), 4 * d, mlp_act, nullptr, 0, 0, w.m, nullptr, nullptr));
+            RUN(lin(w.m, 4 * d, Lw(l, 16), Lf(l, 17), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
+        }
+        RUN(ln(w.x, d, Gf(2), Gf(3), w.hid, B));
+        RUN(lin(w.hid, d, weights[4], head_bias, c.V, 0, logits, ld_logits, 0, nullptr, nullptr, nullptr));
+        MI_CHECK_LAUNCH();
+        return MI_OK;
+    }
+    if (c.act == 0 && M <= SK_MAXM && (d % 8) == 0 && 4 * d <= 2048) {
         // ---- skinny token step: LayerNorms, biases, activations and residual adds fused into GEMV-style linears (8 launches per layer)
         auto lin_ln = [&](const float* g, const float* b, const void* W, const float* bias, int N, bf16_t* out, int act) {
             SkArgs a{}; a.x32 = w.x; a.ldx = d; a.ln_g = g; a.ln_b = b; a.eps = c.eps; a.W = (const bf16_t*)W; a.ldw = d; a.bias = bias;
@@ -367,7 +409,7 @@ extern "C" int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weight
         }
         // ln_f on the last new position of every sequence + lm head -> fp32 logits
         SkArgs a{}; a.x32 = w.x + (size_t)(U - 1) * d; a.ldx = (long)U * d; a.ln_g = Gf(2); a.ln_b = Gf(3); a.eps = c.eps; a.W = (const bf16_t*)weights[4];
-        a.ldw = d; a.out32 = logits; a.ldo32 = ld_logits; a.M = B; a.N = c.V; a.K = d; a.act = 0;
+        a.ldw = d; a.bias = head_bias; a.out32 = logits; a.ldo32 = ld_logits; a.M = B; a.N = c.V; a.K = d; a.act = 0;
         RUN(skinny(a, st));
         MI_CHECK_LAUNCH();
         return MI_OK;
@@ -390,12 +432,45 @@ extern "C" int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weight
         RUN(mi_attention_qkv_bf16(w.qq, d, ckv, 2 * d, ckv + d, 2 * d, nullptr, 0, nullptr, nullptr, enc_len, w.ctx, d, B, U, T_enc, 0, c.H, hd, scale, 0, st));
         RUN(mi_gemm_bf16(w.ctx, d, Lw(l, 10), d, Lf(l, 11), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, d, 0, 0, st));
         RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
-        RUN(mi_gemm_bf16(w.a, d, Lw(l, 14), d, Lf(l, 15), 1, w.m, 4 * d, 0, nullptr, 0, 1.f, 2, M, 4 * d, d, 0, 0, st));
+        RUN(mi_gemm_bf16(w.a, d, Lw(l, 14), d, Lf(l, 15), 1, w.m, 4 * d, 0, nullptr, 0, 1.f, mlp_act, M, 4 * d, d, 0, 0, st));
         RUN(mi_gemm_bf16(w.m, 4 * d, Lw(l, 16), 4 * d, Lf(l, 17), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, 4 * d, 0, 0, st));
     }
     // ln_f on the last new position of every sequence (rows b*U + U-1: a strided view), then the lm head
     RUN(ln(w.x + (size_t)(U - 1) * d, (long)U * d, Gf(2), Gf(3), w.hid, B));
-    RUN(mi_gemm_bf16(w.hid, d, weights[4], d, nullptr, 0, logits, ld_logits, 1, nullptr, 0, 1.f, 0, B, c.V, d, 0, 0, st));
+    RUN(mi_gemm_bf16(w.hid, d, weights[4], d, head_bias, head_bias ? 1 : 0, logits, ld_logits, 1, nullptr, 0, 1.f, 0, B, c.V, d, 0, 0, st));
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
+
+// the GPT-2 entry: the same step without a head bias
+extern "C" int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
+                            void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                            float emb_scale, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
+    return mi_decoder_step(cfg, weights, ids_new, B, U, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, emb_scale, nullptr, workspace, workspace_bytes, logits,
+                           ld_logits, st);
+}
+
+// ---- greedy decoding on the device: what the host does between two token steps of GenerationMixin's greedy loop (next = argmax; a finished row takes pad; the token joins
+// the ids and feeds the next step; a row is finished once it emitted EOS).  done_host (nullable): the flags after the step, for the host (pinned, device-mapped memory).
+namespace {
+__global__ __launch_bounds__(256) void greedy_advance_kernel(const int* __restrict__ best, long* __restrict__ ids, long ld_ids, int col, long eos, long pad,
+                                                              int* __restrict__ done, long* __restrict__ new_tok, int* __restrict__ done_host, int B) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int dn = done[b];
+    const long tok = dn ? pad : (long)best[b];
+    ids[(long)b * ld_ids + col] = tok;
+    new_tok[b] = tok;
+    dn |= tok == eos;
+    done[b] = dn;
+    if (done_host) done_host[b] = dn;
+}
+}  // namespace
+
+extern "C" int mi_greedy_advance(const int* best, long* ids, long ld_ids, int col, long eos, long pad, int* done, long* new_tok, int* done_host, int B, hipStream_t st) {
+    MI_ENTER();
+    if (B <= 0 || col < 0 || col >= ld_ids) return MI_ERR_ARG;
+    hipLaunchKernelGGL(greedy_advance_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, best, ids, ld_ids, col, eos, pad, done, new_tok, done_host, B);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }

@@ -335,6 +335,28 @@ def gemm_lse(a, w, bias, out):
     return lse
 
 
+def linear_rows(x, w, bias=None, *, act="none", out=None, out_dtype=BF16, accumulate=False, kv_cache=None, U=1, past=0):
+    """y = act(x @ w^T + bias) for 1 <= M <= 64 rows (mi_linear_rows, csrc/linear_rows.hip: the weights are streamed once, spread over the chip by N and K; no float
+    atomics, bit-reproducible, rows independent).  x (M, K), w (N, K) bf16, K % 8 == 0.  out fp32: y, or out += y with `accumulate` (the residual stream); out bf16: y, and
+    with kv_cache = (k, v), each (B, Lmax, d) bf16 and N == 3 d, columns [d, 2d) / [2d, 3d) of row b U + u are also written to k / v at position past + u."""
+    _req(x, BF16); _req(w, BF16)
+    M, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty((M, N), device=x.device, dtype=out_dtype)
+    L = _lib.lib()
+    nbytes = L.mi_linear_rows_workspace_bytes(M, N, K)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    f32 = out.dtype == torch.float32
+    kc, vc = kv_cache if kv_cache is not None else (None, None)
+    rc = L.mi_linear_rows(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), _p(bias), {"none": 0, "gelu": 1, "gelu_new": 2}[act],
+                          out.data_ptr() if f32 else None, out.stride(0) if f32 else 0, int(bool(accumulate)), None if f32 else out.data_ptr(), 0 if f32 else out.stride(0),
+                          _p(kc), _p(vc), int(U), int(past), kc.shape[1] if kc is not None else 0, kc.shape[2] if kc is not None else 0, M, N, K,
+                          ws.data_ptr(), nbytes, _stream())
+    _lib.check(rc, "mi_linear_rows")
+    return out
+
+
 def row_lse(x):
     M, V = x.shape
     out = torch.empty((M,), device=x.device, dtype=torch.float32)

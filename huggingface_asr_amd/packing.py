@@ -252,6 +252,65 @@ def _dec_map(c: dict, with_proj: bool, prefix="decoder."):
     return m
 
 
+# ====================================================================================================== Whisper decoder parameters
+def _whisper_as_gpt2(c: dict) -> dict:
+    """a transformers `WhisperConfig`'s decoder fields in the keys `decoder_specs` reads: learned positions, the token embedding tied as the head"""
+    return dict(n_embd=c["d_model"], n_layer=c["decoder_layers"], n_head=c["decoder_attention_heads"], vocab_size=c["vocab_size"],
+                n_positions=c["max_target_positions"], tie_word_embeddings=True)
+
+
+def whisper_decoder_specs(c: dict) -> list[Spec]:
+    """The Whisper decoder in the slots of the GPT-2 step (`decoder_specs`; the step's table is 5 globals + 18 per layer): the block is the same pre-LN block, with
+    [Wq; Wk; Wv] as wqkv (K bias zero: k_proj has none), the cross [Wk; Wv] as wkv (K bias zero), fc1 / fc2 as wfc / wpr, embed_positions as wpe, no separate head."""
+    return decoder_specs(_whisper_as_gpt2(c), c["d_model"], False)
+
+
+def _whisper_dec_map(c: dict, prefix: str = ""):
+    """packed name -> Ref for transformers' `WhisperDecoder` state-dict names"""
+    d, L = c["d_model"], c["decoder_layers"]
+    m = {}
+    one = partial(_one, m)
+    one("wte", prefix + "embed_tokens.weight"); one("wpe", prefix + "embed_positions.weight")
+    for l in range(L):
+        p, r = f"h{l}.", f"{prefix}layers.{l}."
+        sa, ca = r + "self_attn.", r + "encoder_attn."
+        one(p + "ln1_g", r + "self_attn_layer_norm.weight"); one(p + "ln1_b", r + "self_attn_layer_norm.bias")
+        m[p + "wqkv"] = Ref(lambda sd, a=sa: torch.cat([sd[a + f"{n}_proj.weight"] for n in "qkv"], 0),
+                            [(sa + f"{n}_proj.weight", (lambda t, i=i: t[i * d:(i + 1) * d])) for i, n in enumerate("qkv")])
+        m[p + "bqkv"] = Ref(lambda sd, a=sa: torch.cat([sd[a + "q_proj.bias"], torch.zeros_like(sd[a + "q_proj.bias"]), sd[a + "v_proj.bias"]], 0),
+                            [(sa + "q_proj.bias", lambda t: t[:d]), (sa + "v_proj.bias", lambda t: t[2 * d:])])
+        one(p + "wo", sa + "out_proj.weight"); one(p + "bo", sa + "out_proj.bias")
+        one(p + "lnc_g", r + "encoder_attn_layer_norm.weight"); one(p + "lnc_b", r + "encoder_attn_layer_norm.bias")
+        one(p + "wq", ca + "q_proj.weight"); one(p + "bq", ca + "q_proj.bias")
+        m[p + "wkv"] = Ref(lambda sd, a=ca: torch.cat([sd[a + "k_proj.weight"], sd[a + "v_proj.weight"]], 0),
+                           [(ca + "k_proj.weight", lambda t: t[:d]), (ca + "v_proj.weight", lambda t: t[d:])])
+        m[p + "bkv"] = Ref(lambda sd, a=ca: torch.cat([torch.zeros_like(sd[a + "v_proj.bias"]), sd[a + "v_proj.bias"]], 0), [(ca + "v_proj.bias", lambda t: t[d:])])
+        one(p + "wco", ca + "out_proj.weight"); one(p + "bco", ca + "out_proj.bias")
+        one(p + "ln2_g", r + "final_layer_norm.weight"); one(p + "ln2_b", r + "final_layer_norm.bias")
+        one(p + "wfc", r + "fc1.weight"); one(p + "bfc", r + "fc1.bias")
+        one(p + "wpr", r + "fc2.weight"); one(p + "bpr", r + "fc2.bias")
+    one("lnf_g", prefix + "layer_norm.weight"); one("lnf_b", prefix + "layer_norm.bias")
+    return m
+
+
+def suppression_vectors(V: int, suppress_tokens=None, begin_suppress_tokens=None, device="cpu"):
+    """(every step's, the first generated token's) fp32 (V) vectors added to the logits: -inf at a suppressed id, 0 elsewhere — transformers'
+    SuppressTokensLogitsProcessor and, for the first generated token only, SuppressTokensAtBeginLogitsProcessor on top of it.  None where nothing is suppressed."""
+    def vec(ids):
+        ids = [int(i) for i in ids]
+        bad = [i for i in ids if not 0 <= i < V]
+        if bad:
+            raise ValueError(f"suppressed token ids {bad} outside the vocabulary [0, {V})")
+        v = torch.zeros(V, dtype=torch.float32)
+        if ids:
+            v[torch.tensor(ids, dtype=torch.long)] = float("-inf")
+        return v.to(device)
+    always, begin = list(suppress_tokens or []), list(begin_suppress_tokens or [])
+    every = vec(always) if always else None
+    first = vec(always + begin) if (always or begin) else None
+    return every, first
+
+
 # ====================================================================================================== encoder position tables
 def relative_position_table(T2: int, d: int) -> torch.Tensor:
     """(2*T2-1, d) fp32 sinusoids of the relative positions T2-1 ... -(T2-1), one per row (tf wav2vec2_conformer :159-205)"""

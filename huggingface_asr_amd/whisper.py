@@ -1,4 +1,4 @@
-"""Whisper-style encoder on the HIP kernels (BASELINE.json config 4).
+"""Whisper-style encoder and greedy decoding on the HIP kernels (BASELINE.json config 4).
 
 The reference uses HuggingFace's Whisper classes as they are (`src/utilities/model_utils.py:183`,
 `src/trainers/train_enc_dec_asr.py:82-83`, `configs/default_data_preprocessing_whisper.json`), so the drop-in unit here is an
@@ -8,10 +8,14 @@ pre-LN layers (fused QKV GEMM with a zero bias block for k_proj, LDS-staged atte
 residual fused), final LayerNorm."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import _lib, ops
+from .decoder import GPT2DecoderEngine
+from .packing import _whisper_as_gpt2, _whisper_dec_map, mapped_fp32, packed, suppression_vectors, whisper_decoder_specs
 
 BF16 = torch.bfloat16
 
@@ -279,11 +283,228 @@ class WhisperEncoderEngine:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
+# Decoding.  A Whisper decoder block is the GPT-2 cross-attention block of decoder.py (pre-LN: self-attention over the KV cache, cross-attention over cached encoder
+# K/V, MLP) with separate q / k / v matrices (k_proj without a bias), erf-GELU, learned positions and the token embedding as the head — so it runs on the same C step
+# (`mi_decoder_step`, csrc/decoder_step.hip) from a table packed by `packing.whisper_decoder_specs`.
+class WhisperDecoderEngine(GPT2DecoderEngine):
+    """transformers' `WhisperDecoder.forward` with a KV cache + the tied `proj_out`, one C call per step.  cfg: the decoder fields of a `WhisperConfig`
+    (d_model, decoder_layers, decoder_attention_heads, decoder_ffn_dim, vocab_size, max_target_positions, activation_function, scale_embedding)."""
+
+    # (rows, d_model) at which the streaming form of the step (`mi_gpt2_config.step_form = 2`, csrc/linear_rows.hip) measured faster than the launch-per-op form by more
+    # than the run-to-run spread of the same call (tools/whisper_decode_bench.py, DESIGN "Whisper decoding"); every other shape runs form 1
+    STREAMING_AT = ((1, 768), (16, 768), (16, 1024))          # measured and lost: (64, 768); every other shape: not measured
+
+    def __init__(self, cfg: dict, device="cuda:0"):
+        d, H = cfg["d_model"], cfg["decoder_attention_heads"]
+        if d % H or d // H != 64:
+            raise NotImplementedError("the HIP Whisper decoder supports head size 64 (every released checkpoint)")
+        if cfg.get("decoder_ffn_dim", 4 * d) != 4 * d:
+            raise NotImplementedError("the HIP Whisper decoder needs decoder_ffn_dim == 4 * d_model")
+        if cfg.get("activation_function", "gelu") != "gelu":
+            raise NotImplementedError("Whisper decoder activation other than gelu")
+        self.cfg = dict(cfg, **_whisper_as_gpt2(cfg))        # + the GPT-2 names of the same numbers, which the inherited cache / position code reads
+        self.device = torch.device(device)
+        self.step_form = None           # None: by STREAMING_AT; 1 / 2 force a form (tests, the bench tool)
+        self.w = None
+
+    def load_state_dict(self, sd: dict, prefix: str = ""):
+        """transformers' `WhisperDecoder` names (embed_tokens, embed_positions, layers.N.{self_attn,encoder_attn}.*, layers.N.fc1 / fc2, layer_norm) -> the step's table"""
+        c, dev = self.cfg, self.device
+        d, L = c["d_model"], c["decoder_layers"]
+        m = _whisper_dec_map(c, prefix)
+        P = {s.name: (t.to(BF16) if s.mat and s.name != "wte" else t).contiguous()          # wte stays fp32: the embedding gather reads it
+             for s, t in packed(whisper_decoder_specs(c), m, mapped_fp32(m, sd, dev))}
+        w = dict(wte=P["wte"], scale=float(d) ** 0.5 if c.get("scale_embedding", False) else 1.0, pos=P["wpe"], lnf=(P["lnf_g"], P["lnf_b"]), heads=[],
+                 lm_head=P["wte"].to(BF16))                                                   # tied: the token embedding's bf16 image is the head
+        w["layers"] = [dict({n: P[f"h{l}.{n}"] for n in ("wqkv", "bqkv", "wo", "bo", "wq", "bq", "wkv", "bkv", "wco", "bco", "wfc", "bfc", "wpr", "bpr")},
+                            **{n: (P[f"h{l}.{n}_g"], P[f"h{l}.{n}_b"]) for n in ("ln1", "lnc", "ln2")}) for l in range(L)]
+        self.w = w
+        ptrs = [w["wte"], w["pos"], w["lnf"][0], w["lnf"][1], w["lm_head"]]
+        for lw in w["layers"]:
+            ptrs += [lw["ln1"][0], lw["ln1"][1], lw["wqkv"], lw["bqkv"], lw["wo"], lw["bo"], lw["lnc"][0], lw["lnc"][1], lw["wq"], lw["bq"],
+                     lw["wco"], lw["bco"], lw["ln2"][0], lw["ln2"][1], lw["wfc"], lw["bfc"], lw["wpr"], lw["bpr"]]
+        self._wtable = (C.c_void_p * len(ptrs))(*[t.data_ptr() for t in ptrs])
+        self._gcfg = _lib.Gpt2Config(d=d, H=c["decoder_attention_heads"], L=L, V=c["vocab_size"], eps=1e-5, step_form=1, act=1)
+        self._step_ws = None
+
+    def ensure_positions(self, n: int):
+        have = self.cfg["max_target_positions"]
+        if n > have:
+            raise ValueError(f"decoding needs {n} positions but the learned position table (embed_positions) has max_target_positions = {have} rows")
+
+    def form_for(self, rows: int) -> int:
+        if self.step_form is not None:
+            return self.step_form
+        return 2 if (rows, self.cfg["d_model"]) in self.STREAMING_AT else 1
+
+    def step(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, head_bias=None):
+        """ids_new (B, U) -> fp32 logits (B, V) of the last new position (+ head_bias (V) fp32, 0 / -inf); appends to the KV cache.  One C call (mi_decoder_step)."""
+        ids_new = ids_new.contiguous()
+        B, U = ids_new.shape
+        past, Lmax = cache["past"], cache["Lmax"]
+        self.ensure_positions(past + U)
+        if past + U > Lmax:
+            raise ValueError(f"the KV cache holds {Lmax} positions, the step needs {past + U}")
+        L_ = _lib.lib()
+        self._gcfg.step_form = self.form_for(B)
+        nbytes = L_.mi_gpt2_step_workspace_bytes(C.byref(self._gcfg), B, U)
+        if self._step_ws is None or self._step_ws.numel() < nbytes:
+            self._step_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        if cache.get("kv_id") != id(kvs):
+            cache["tkv"] = (C.c_void_p * len(kvs))(*[t.data_ptr() for t in kvs])
+            cache["kv_id"] = id(kvs)
+        V = self._gcfg.V
+        Vp = (V + 7) // 8 * 8
+        buf = torch.empty((B, Vp), device=self.device, dtype=torch.float32)
+        _lib.check(L_.mi_decoder_step(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc, None,
+                                      float(self.w["scale"]), head_bias.data_ptr() if head_bias is not None else None, self._step_ws.data_ptr(), self._step_ws.numel(),
+                                      buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_decoder_step")
+        cache["past"] = past + U
+        return buf[:, :V]
+
+    def forward(self, *a, **k):
+        raise NotImplementedError("WhisperDecoderEngine decodes step by step (step / greedy_decode); the teacher-forced training forward stays transformers'")
+
+    step_py = forward
+
+
+def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new_tokens, eos_token_id, pad_token_id, suppress_tokens=None, begin_suppress_tokens=None,
+                  run_ahead=2, stats=None):
+    """Greedy transcription with the loop on the device -> (B, P + n) LongTensor: per row the prompt, the generated tokens, the first EOS (kept), then pad_token_id —
+    `GenerationMixin`'s greedy layout, trimmed to the longest row.  Per token: the decoder step with the suppression vector as the head's bias (the begin-suppress ids in
+    the first generated token's only), `mi_row_argmax`, and one kernel that appends the token (pad for a finished row), hands it to the next step and sets the row's done
+    flag at EOS, writing the flags into pinned memory.  The host only enqueues, at most `run_ahead` steps in front of the flags it has seen, and stops once every row is
+    done; nothing is copied per token.  The prompt (B, P) is consumed by one step of P positions.  `stats` receives the number of steps enqueued."""
+    if not input_features.is_cuda or not prompt_ids.is_cuda:
+        raise RuntimeError("greedy_decode needs device tensors (no CPU fallback)")
+    dev = dec_engine.device
+    B, P = prompt_ids.shape
+    V = dec_engine.cfg["vocab_size"]
+    if max_new_tokens < 1:
+        raise ValueError("max_new_tokens >= 1 required")
+    dec_engine.ensure_positions(P + max_new_tokens)
+    for name, t in (("eos_token_id", eos_token_id), ("pad_token_id", pad_token_id)):
+        if not 0 <= int(t) < V:
+            raise ValueError(f"{name} {t} outside the vocabulary [0, {V})")
+    every, first = suppression_vectors(V, suppress_tokens, begin_suppress_tokens, dev)
+    enc = enc_engine.forward(input_features=input_features)
+    T2, d = enc.shape[1], enc.shape[2]
+    kvs = dec_engine.cross_kv(ops.cast_bf16(enc.reshape(B * T2, d)))
+    Lmax = P + max_new_tokens
+    cache = dec_engine.init_cache(B, Lmax)
+    ids = torch.full((B, Lmax), int(pad_token_id), dtype=torch.long, device=dev)
+    ids[:, :P] = prompt_ids
+    done = torch.zeros((B,), dtype=torch.int32, device=dev)
+    done_host = torch.zeros((max_new_tokens, B), dtype=torch.int32).pin_memory()
+    new_tok = prompt_ids.to(torch.long).contiguous()
+    L_ = _lib.lib()
+    main = torch.cuda.current_stream()
+    flags, steps = [], 0
+    while steps < max_new_tokens:
+        if len(flags) >= run_ahead:                # bounded run-ahead: the flags of step (now - run_ahead) are in pinned memory once its event has fired
+            flags[len(flags) - run_ahead].synchronize()
+            if bool(done_host[steps - run_ahead].all()):
+                break
+        logits = dec_engine.step(new_tok, cache, kvs, T2, first if steps == 0 else every)
+        best = ops.row_argmax(logits)
+        new_tok = torch.empty((B, 1), dtype=torch.long, device=dev)
+        _lib.check(L_.mi_greedy_advance(best.data_ptr(), ids.data_ptr(), Lmax, P + steps, int(eos_token_id), int(pad_token_id), done.data_ptr(), new_tok.data_ptr(),
+                                        done_host[steps].data_ptr(), B, main.cuda_stream), "mi_greedy_advance")
+        ev = torch.cuda.Event()
+        ev.record(main)
+        flags.append(ev)
+        steps += 1
+    main.synchronize()
+    n = steps
+    for t in range(steps):                         # steps enqueued past the one that finished the last row only wrote pads
+        if bool(done_host[t].all()):
+            n = t + 1
+            break
+    if stats is not None:
+        stats["steps"] = steps
+        stats["tokens"] = n
+    return ids[:, :P + n]
+
+
+_GENERATE_REFUSED = ("logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "assistant_model", "streamer", "prompt_ids", "language", "task", "is_multilingual",
+                     "negative_prompt_ids", "forced_decoder_ids")
+
+
+def _decoder_engine_for(dec) -> WhisperDecoderEngine:
+    """the HIP engine of a `WhisperDecoder` module, keyed like `_engine_for`: rebuilt when a parameter was replaced, moved or written in place"""
+    params = list(dec.parameters())
+    key = (str(params[0].device), tuple((p.data_ptr(), p._version) for p in params))
+    cached = dec.__dict__.get("_hfasr_engine")
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    c = dec.config
+    eng = WhisperDecoderEngine(dict(d_model=c.d_model, decoder_layers=c.decoder_layers, decoder_attention_heads=c.decoder_attention_heads, decoder_ffn_dim=c.decoder_ffn_dim,
+                                    vocab_size=c.vocab_size, max_target_positions=c.max_target_positions, activation_function=c.activation_function,
+                                    scale_embedding=False), params[0].device)       # transformers' WhisperDecoder.forward never applies embed_scale
+    eng.load_state_dict(dec.state_dict())
+    dec.__dict__["_hfasr_engine"] = (key, eng)
+    return eng
+
+
+def hip_generate(model, input_features, decoder_input_ids=None, max_new_tokens=None, max_length=None, **kw):
+    """Greedy transcription of a transformers `WhisperForConditionalGeneration` on the HIP path: the bound encoder, `WhisperDecoderEngine` and `greedy_decode`
+    (the recipes' case: `--num_beams=1 --predict_with_generate`).  eos / pad / suppress_tokens / begin_suppress_tokens come from `model.generation_config`; the prompt is
+    `decoder_input_ids`, or `[[decoder_start_token_id]]`.  Returns (B, P + n) ids in `GenerationMixin`'s greedy layout.  What it does not do is refused with
+    NotImplementedError before the device is touched — beams, sampling, timestamps, language / task prompts, custom processors or stopping criteria —: those stay
+    `model.generate`, which is transformers' own and not rerouted.  CPU tensors raise RuntimeError (no fallback)."""
+    gc, cfg = model.generation_config, model.config
+    if kw.pop("num_beams", None) not in (None, 1) or (getattr(gc, "num_beams", 1) or 1) > 1:
+        raise NotImplementedError("hip_generate is greedy: num_beams > 1 stays model.generate")
+    if kw.pop("do_sample", None) or getattr(gc, "do_sample", False):
+        raise NotImplementedError("hip_generate is greedy: do_sample stays model.generate")
+    if kw.pop("return_timestamps", None) or getattr(gc, "return_timestamps", False):
+        raise NotImplementedError("hip_generate does not apply the timestamp rules: return_timestamps stays model.generate")
+    for k in _GENERATE_REFUSED:
+        if kw.get(k) is not None:
+            raise NotImplementedError(f"hip_generate does not take {k}=: it stays model.generate")
+    if kw:
+        raise NotImplementedError(f"hip_generate does not take {sorted(kw)}: it stays model.generate")
+    if getattr(cfg, "scale_embedding", False):
+        raise NotImplementedError("scale_embedding: transformers' WhisperDecoder computes embed_scale and never applies it; no checkpoint sets it")
+    if input_features.dim() == 2:
+        input_features = input_features[None]
+    frames = 2 * cfg.max_source_positions
+    if input_features.dim() != 3 or input_features.shape[-1] != frames:
+        raise NotImplementedError(f"hip_generate takes (B, mel, {frames}) input features (long-form and shorter inputs stay model.generate), got {tuple(input_features.shape)}")
+    B = input_features.shape[0]
+    if decoder_input_ids is None:
+        start = gc.decoder_start_token_id if getattr(gc, "decoder_start_token_id", None) is not None else cfg.decoder_start_token_id
+        decoder_input_ids = torch.full((B, 1), int(start), dtype=torch.long, device=input_features.device)
+    P = decoder_input_ids.shape[1]
+    if max_new_tokens is None:
+        max_new_tokens = (max_length if max_length is not None else (getattr(gc, "max_length", None) or cfg.max_target_positions)) - P
+    if max_new_tokens < 1:
+        raise ValueError(f"nothing to generate: max_new_tokens = {max_new_tokens}")
+    if P + max_new_tokens > cfg.max_target_positions:
+        raise ValueError(f"prompt ({P}) + max_new_tokens ({max_new_tokens}) exceeds max_target_positions = {cfg.max_target_positions}")
+    eos = gc.eos_token_id if gc.eos_token_id is not None else cfg.eos_token_id
+    if isinstance(eos, (list, tuple)):
+        if len(eos) != 1:
+            raise NotImplementedError("hip_generate takes one eos_token_id")
+        eos = eos[0]
+    pad = gc.pad_token_id if gc.pad_token_id is not None else cfg.pad_token_id
+    if eos is None or pad is None:
+        raise ValueError("generation_config needs eos_token_id and pad_token_id")
+    if not input_features.is_cuda or not decoder_input_ids.is_cuda or not next(model.parameters()).is_cuda:
+        raise RuntimeError("hip_generate needs the model and its inputs on the GPU (no CPU fallback)")
+    enc_eng = _engine_for(model.model.encoder)
+    dec_eng = _decoder_engine_for(model.model.decoder)
+    with torch.no_grad():
+        return greedy_decode(enc_eng, dec_eng, input_features, decoder_input_ids, max_new_tokens=max_new_tokens, eos_token_id=int(eos), pad_token_id=int(pad),
+                             suppress_tokens=getattr(gc, "suppress_tokens", None), begin_suppress_tokens=getattr(gc, "begin_suppress_tokens", None))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
 # The Whisper branch of the reference (`src/utilities/model_utils.py:183`: `AutoModelForSpeechSeq2Seq.from_pretrained(...)` on a Whisper checkpoint, e.g.
 # `recipes_v0.0.1/decred/out_of_domain/decode_whisper_lumi.sh:60-66` `--from_pretrained=openai/whisper-medium --predict_with_generate`) runs HuggingFace's
 # `WhisperForConditionalGeneration` as it is, and `src/trainers/train_enc_dec_asr.py:82-83` tests `isinstance(model, WhisperForConditionalGeneration)` — so the class has
-# to stay HuggingFace's.  The drop-in is therefore a replacement of `WhisperEncoder.forward`: the encoder (the whole cost of config 4) runs on the HIP engine above, the
-# decoder, `generate`, the loss and the checkpoint format stay transformers' own.
+# to stay HuggingFace's.  The drop-in is therefore a replacement of `WhisperEncoder.forward`: the encoder (the whole cost of config 4) runs on the HIP engine above;
+# `generate`, the loss and the checkpoint format stay transformers' own.  Greedy transcription on the HIP path is the separate entry `hip_generate` above.
 def _encoder_cfg(enc) -> dict:
     c = enc.config
     return dict(d_model=c.d_model, encoder_layers=c.encoder_layers, encoder_attention_heads=c.encoder_attention_heads, encoder_ffn_dim=c.encoder_ffn_dim)

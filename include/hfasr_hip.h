@@ -522,12 +522,30 @@ typedef struct {
     int d, H, L, V;
     float eps;
     int step_form;      /* token step with one new token per row and <= 8 rows: 0 = the fused form (three launches per layer, csrc/decoder_fused.hip) where it applies
-                           (head size 64, d <= 512), 1 = always one launch per op (the cross-check; what every other shape runs) */
+                           (head size 64, d <= 512), 1 = always one launch per op (the cross-check; what every other shape runs); 2 = the streaming form
+                           (csrc/linear_rows.hip) for one new token per row and <= 64 rows, one launch per op elsewhere */
+    int act;            /* MLP activation: 0 = gelu_new (GPT-2), 1 = erf-GELU (Whisper); the fused and GEMV forms are gelu_new only: act 1 runs form 1 or 2 */
 } mi_gpt2_config;
 size_t mi_gpt2_step_workspace_bytes(const mi_gpt2_config* cfg, int B, int U);
 int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
                  void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
                  void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
+/* mi_gpt2_step with a nullable fp32 head_bias (V) added to the logits (0 / -inf: transformers' SuppressTokens processors).  The Whisper decoder
+ * (transformers WhisperDecoder.forward with a cache) is this step with act = 1 and [Wq; Wk; Wv] packed, the K bias zero. */
+int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
+                    void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
+                    const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
+/* Rows-streaming linear (csrc/linear_rows.hip): y = act(x W^T + b) for 1 <= M <= 64 rows, any N, K % 8 == 0; x (M, K) and W (N, K) bf16, 16-B aligned, ldx % 8 == ldw % 8 == 0.
+ * act 0 none / 1 erf-GELU / 2 gelu_new.  Exactly one of out32 / out16: out32 (M, ldo32) fp32 = y, or out32 += y when accumulate (the in-place residual add); out16 (M, ldo16)
+ * bf16, and with kcache != NULL (N == 3 dkv, M % U == 0) columns [dkv, 2 dkv) / [2 dkv, 3 dkv) of row m = b U + u also go to kcache / vcache (.., Lmax, dkv) at row
+ * past + u of sequence b.  workspace: mi_linear_rows_workspace_bytes(M, N, K) bytes (0 when the launch is not split over K).  No float atomics: bit-reproducible, and a
+ * row's result does not depend on the other rows. */
+size_t mi_linear_rows_workspace_bytes(int M, int N, int K);
+int mi_linear_rows(const void* x, long ldx, const void* W, long ldw, const float* bias, int act, float* out32, long ldo32, int accumulate, void* out16, long ldo16,
+                   void* kcache, void* vcache, int U, int past, int Lmax, int dkv, int M, int N, int K, void* workspace, size_t workspace_bytes, mi_stream_t stream);
+/* One step of greedy decoding between two token steps (transformers GenerationMixin greedy loop): tok = done[b] ? pad : best[b]; ids[b, col] = new_tok[b] = tok;
+ * done[b] |= tok == eos; done_host (nullable; pinned, device-mapped memory) receives the flags. */
+int mi_greedy_advance(const int* best, long* ids, long ld_ids, int col, long eos, long pad, int* done, long* new_tok, int* done_host, int B, mi_stream_t stream);
 int mi_kv_cache_reorder(const void* const* src_k, const void* const* src_v, void* const* dst_k, void* const* dst_v, const long* beam_idx,
                         int L, int BW, int rows, int Lmax, int d, mi_stream_t stream);
 
