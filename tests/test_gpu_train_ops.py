@@ -4,12 +4,20 @@
 Tolerances: bf16-stored gradients at ~1 bf16 ulp relative + a small absolute floor scaled to the gradient magnitude;
 fp32 parameter gradients (sums over thousands of bf16 products) at 1 % of the tensor's max |value|."""
 import math
+import os
+import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 from oracle import ebranchformer_ref as R
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import train_tail_ref as TR  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -937,7 +945,11 @@ def test_ce_and_embed_bwd():
     _lib.check(_lib.lib().mi_ce_label_smoothing(ld.data_ptr(), ld.stride(1), labels.to(DEV).data_ptr(), B, U, 1, V, 0.1, acc.data_ptr(), rows.data_ptr(),
                                                 torch.cuda.current_stream().cuda_stream), "ce")
     dl = T.ce_label_smoothing_bwd(ld, labels.to(DEV), acc, shift=1, eps=0.1, weight=0.6)
-    close(dl[:, :V].reshape(B, U, V), lg.grad, floor=5e-3, what="ce dlogits")
+    # elementwise, nothing exempt: a floor taken from the tensor's maximum (a target column) hid the eps / V term of every other column (tests/test_train_tail_cpu.py)
+    ref = TR.ce_ref(logits, labels, 1, 0.1, 0.6, ldo=dl.shape[1])
+    assert float((ref["grad"][:, :V].reshape(B, U, V) - lg.grad.double()).abs().max()) < 1e-8          # the fp64 reference is torch's gradient
+    rep = TR.ce_grad_report(dl, ref)
+    assert rep["ok"], f"ce dlogits: {rep}"
     # embeddings
     ids = torch.randint(0, V, (B, U), generator=torch.Generator().manual_seed(3))
     wte, wpe = rnd(V, d, seed=4).requires_grad_(True), rnd(32, d, seed=5).requires_grad_(True)
