@@ -84,6 +84,8 @@ SIGNATURES = {
     "mi_ctc_greedy": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, vp, vp, i32, vp, vp, vp],
     "mi_gemm_argmax_workspace_floats": [i32, i32],
     "mi_gemm_argmax_bf16": [vp, i64, vp, i64, vp, vp, vp, i32, i32, i32, vp],
+    "mi_gemm_ce_f32": [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
+    "mi_gemm_ce_bwd_bf16": [vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
     "mi_ctc_loss_fwd": [vp, i64, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "mi_ctc_prefix_prepare": [vp, i64, i64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "mi_ctc_prefix_score": [vp, i32, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp],

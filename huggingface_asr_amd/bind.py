@@ -14,7 +14,8 @@ so the reference's scripts run unchanged: `python -m huggingface_asr_amd.launch 
 
 The Whisper branch (`model_utils.py:183` on a Whisper checkpoint, `decode_whisper_lumi.sh:60-66`) keeps HuggingFace's `WhisperForConditionalGeneration` — the trainer tests
 for that class (`train_enc_dec_asr.py:82-83`) — and gets the HIP encoder through `whisper.install_whisper()` (called by `bind_all()`): `WhisperEncoder.forward` is replaced,
-decoder / `generate` / checkpoints stay transformers' own."""
+decoder / `generate` / checkpoints stay transformers' own — unless HFASR_WHISPER_DECODER=1 (the teacher-forced decoder pass of training on the HIP engine) or
+HFASR_WHISPER_FUSED_LOSS=1 (also the training loss out of the tied head's GEMM) is set in the environment `bind_all()` runs in."""
 import sys
 
 from transformers import AutoConfig, AutoFeatureExtractor, AutoModelForCTC, AutoModelForPreTraining, AutoModelForSpeechSeq2Seq
@@ -58,7 +59,8 @@ def bind_all():
     AutoConfig.register("custom_feature_extractor", CustomFeatureExtractorConfig, exist_ok=True)
     AutoFeatureExtractor.register(CustomFeatureExtractorConfig, CustomFeatureExtractor, exist_ok=True)
     from .whisper import install_whisper                          # the Whisper branch (model_utils.py:183 on a Whisper checkpoint): HF's classes, our encoder forward
-    install_whisper()
+    import os                                                     # HFASR_WHISPER_DECODER=1 / HFASR_WHISPER_FUSED_LOSS=1: the decoder's training pass / the fused loss (opt-in)
+    install_whisper(decoder=os.environ.get("HFASR_WHISPER_DECODER") == "1", fused_loss=os.environ.get("HFASR_WHISPER_FUSED_LOSS") == "1")
     ref_enc = sys.modules.get("models.encoders.e_branchformer")  # wav2vec2-style contrastive pre-training is not built on the HIP path: when the reference's
     ref_pt = getattr(ref_enc, "Wav2Vec2EBranchformerForPreTraining", None) if ref_enc is not None else None      # tree is loaded its own PyTorch class stays reachable
     if isinstance(ref_pt, type):                                 # through AutoModelForPreTraining, as its bind_all registers it (reference bind.py:42)

@@ -81,7 +81,8 @@ struct Ctx {
 // table behind the ring — issued before the first K tile is consumed, so its memory round trip hides under the ring's fill — and the epilogue computes
 // rstd * acc - rstd * mean * s_n + bias_n instead of acc + bias_n.
 // AMAX (with OUT32): the epilogue keeps only each row's (max, index) per wave block and stores no C (gemm_args.hpp amax_part).
-template <bool CONV, int ACT, bool OUT32 = false, bool GATED = false, bool LNF = false, bool LSE = false, bool AMAX = false>     // ACT: 0 none, 1 erf-GELU, 2 tanh-GELU — compile-time, so the epilogue is straight-line code with many independent chains in flight
+// CE (with OUT32; gemm_args.hpp ce): 1 = the LSE partials and the label's logit of every row, no C; 2 = C (bf16) = g_m * (exp(x - lse_m) - [n == label_m]), the logit gradient.
+template <bool CONV, int ACT, bool OUT32 = false, bool GATED = false, bool LNF = false, bool LSE = false, bool AMAX = false, int CE = 0>     // ACT: 0 none, 1 erf-GELU, 2 tanh-GELU — compile-time, so the epilogue is straight-line code with many independent chains in flight
 __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -322,11 +323,23 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
             // chip): out = resid + alpha * (acc + bias), and the LayerNorm-fold producer's extras (bf16 copy, per-row partial statistics over the wave's 64 columns).
             // The half's 16 residual vectors are requested once its accumulators have gone to LDS (their registers are free) and land under the LDS round trip.
             f32x4 rr[16];
-            if (!AMAX && p.resid) {
+            if (!AMAX && CE == 0 && p.resid) {
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
                     const int m = min(m0 + wr * 128 + half * 64 + u * 4 + r16, p.M - 1);
                     rr[u] = *reinterpret_cast<const f32x4*>(p.resid + (long)m * p.ldr + nb + c16 * 4);
+                }
+            }
+            // CE: the half's 16 labels per lane (and the rows' log-sum-exp and scale for the gradient form), requested like the residual vectors; a label outside [0, N) is -1
+            int clab[16];
+            float clse[16], cg[16];
+            if constexpr (CE != 0) {
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    const int m = min(m0 + wr * 128 + half * 64 + u * 4 + r16, p.M - 1);
+                    const long lb = p.ce_labels[m];
+                    clab[u] = (lb >= 0 && lb < (long)p.N) ? (int)lb : -1;
+                    if constexpr (CE == 2) { clse[u] = p.ce_lse[m]; cg[u] = p.ce_g[m]; }
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -335,6 +348,22 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
                 const int row = u * 4 + r16;
                 f32x4 v = *reinterpret_cast<const f32x4*>(reg + row * 256 + ((c16 ^ (row & 15)) << 4));
                 const int m = m0 + wr * 128 + half * 64 + row, n = nb + c16 * 4;
+                if constexpr (CE == 2) {                    // the logit gradient of the row's four columns: 16 lanes x 8 B = one 128-B line per row; columns in [N, ldc) are zeros
+                    const float xe[4] = {v.x, v.y, v.z, v.w};
+                    bf16x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float pr = __expf(xe[e] - clse[u]) - ((n + e == clab[u]) ? 1.f : 0.f);
+                        o[e] = f2bf((n + e < p.N) ? cg[u] * pr : 0.f);
+                    }
+                    if (m < p.M && n < (int)p.ldc) *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(p.C) + (long)m * p.ldc + n) = o;
+                    if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+                    continue;
+                }
+                if constexpr (CE == 1) {                    // the label's logit: the one lane of the grid whose four columns hold it (clab < N, so the column counts)
+                    const int t = clab[u] - n;
+                    if ((unsigned)t < 4u && m < p.M) p.ce_target[m] = t == 0 ? v.x : (t == 1 ? v.y : (t == 2 ? v.z : v.w));
+                }
                 if constexpr (AMAX) {                       // the row's 64 columns of this wave block -> their (max, index); columns >= N do not count; nothing else leaves
                     amax_t k = ARGMAX_EMPTY;
 #pragma unroll
@@ -346,10 +375,10 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
                     if ((u & 3) == 3) __builtin_amdgcn_sched_barrier(0);
                     continue;
                 }
-                if (p.resid) v = rr[u] + p.alpha * v;
-                if (m < p.M && n < n4) *reinterpret_cast<f32x4*>(C + (long)m * p.ldc + n) = v;
-                if (p.C2 && m < p.M) *reinterpret_cast<bf16x4*>(p.C2 + (long)m * p.ldc2 + n) = bf16x4{f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w)};
-                if (p.stats_out) {                          // 16 lanes hold a row's 64 columns: one (sum, sumsq) pair per row and wave column
+                if (CE == 0 && p.resid) v = rr[u] + p.alpha * v;
+                if (CE == 0 && m < p.M && n < n4) *reinterpret_cast<f32x4*>(C + (long)m * p.ldc + n) = v;
+                if (CE == 0 && p.C2 && m < p.M) *reinterpret_cast<bf16x4*>(p.C2 + (long)m * p.ldc2 + n) = bf16x4{f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w)};
+                if (CE == 0 && p.stats_out) {               // 16 lanes hold a row's 64 columns: one (sum, sumsq) pair per row and wave column
                     float sm = (v.x + v.y) + (v.z + v.w), sq = (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
                     sm += dpp_f32<0xB1, 0xF>(0.f, sm); sq += dpp_f32<0xB1, 0xF>(0.f, sq);
                     sm += dpp_f32<0x4E, 0xF>(0.f, sm); sq += dpp_f32<0x4E, 0xF>(0.f, sq);
@@ -357,7 +386,7 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
                     sm += dpp_f32<0x140, 0xF>(0.f, sm); sq += dpp_f32<0x140, 0xF>(0.f, sq);
                     if (c16 == 0 && m < p.M) *reinterpret_cast<f32x2*>(p.stats_out + (long)m * LN_STATS_STRIDE + (((n0 >> 8) << 2) + wc) * 2) = f32x2{sm, sq};
                 }
-                if constexpr (LSE) {                        // the row's 64 columns of this wave block -> (max, sum exp(x - max)); columns >= N do not count
+                if constexpr (LSE || CE == 1) {             // the row's 64 columns of this wave block -> (max, sum exp(x - max)); columns >= N do not count
                     float xe[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e) xe[e] = (n + e < p.N) ? xe[e] : -INFINITY;
@@ -1179,6 +1208,11 @@ bool gemm_8p_supported(const GemmArgs& a, bool conv) {
     }
     if (a.lse_part && (conv || !a.out_f32 || a.resid || a.C2 || a.stats_out || a.act != 0 || ((uintptr_t)a.lse_part & 7) || (a.lse_ld % 2) || a.lse_ld < 8 * cdiv(a.N, TB))) return false;
     if (a.amax_part && (conv || !a.out_f32 || a.resid || a.C2 || a.stats_out || a.lse_part || a.act != 0 || ((uintptr_t)a.amax_part & 7) || (a.amax_ld % 2) || a.amax_ld < 8 * cdiv(a.N, TB))) return false;
+    if (a.ce) {                      // cross-entropy epilogues: the plain fp32-epilogue GEMM, no C (forward) or a bf16 C whose padding columns the tiles cover (backward)
+        if (a.ce < 1 || a.ce > 2 || conv || !a.out_f32 || a.resid || a.C2 || a.stats_out || a.amax_part || a.act != 0 || !a.ce_labels) return false;
+        if (a.ce == 1 && (!a.lse_part || !a.ce_target)) return false;
+        if (a.ce == 2 && (a.lse_part || !a.C || !a.ce_lse || !a.ce_g || (a.ldc % 8) != 0 || a.ldc < a.N || a.ldc > (long)TB * cdiv(a.N, TB))) return false;
+    }
     if ((long)a.N * a.ldw * 2 >= (1l << 32)) return false;                                             // 32-bit source offsets
     if (conv) {
         if ((a.Cin % BK) != 0 || a.Fout <= 0 || a.Tout <= 0) return false;
@@ -1204,6 +1238,12 @@ int gemm_8p_launch(const GemmArgs& a, bool conv, hipStream_t stream) {
         (void)attr_t;
         if (a.act == 3) launch_dense(PF_8P, gemm8p_kernel<false, 3>, dim3(grid), dim3(512), (size_t)2 * BUF, stream, a);
         else launch_dense(PF_8P_GELU, gemm8p_kernel<false, 4>, dim3(grid), dim3(512), (size_t)2 * BUF, stream, a);
+        return MI_OK;
+    }
+    if (a.out_f32 && a.ce) {
+        const kern_t kc = a.ce == 1 ? gemm8p_kernel<false, 0, true, false, false, false, false, 1> : gemm8p_kernel<false, 0, true, false, false, false, false, 2>;
+        if (!set_lds_attr(kc, 2 * BUF)) return MI_ERR_LAUNCH;
+        launch_dense(PF_8P_CE, kc, dim3(grid), dim3(512), (size_t)2 * BUF, stream, a);
         return MI_OK;
     }
     if (a.out_f32 && a.amax_part) {

@@ -43,6 +43,12 @@ struct GemmArgs {
     // order, the index bit-cast beside the float, at amax_part[m * amax_ld + 2 * (n0 / 64 + wave column)] — same layout and size as the LSE partials; blocks entirely
     // beyond N leave (NaN, -1), which the merge skips.  C is NOT stored (and may be null).
     float* amax_part; int amax_ld;
+    // Cross-entropy forms of the same epilogue (mi_gemm_ce_f32 / mi_gemm_ce_bwd_bf16): the head GEMM of a language model whose logits are never stored.
+    //  ce = 1 (forward): the LSE partials into lse_part as above, and the one lane of the grid that holds column ce_labels[m] of row m stores that logit to
+    //    ce_target[m] (one writer per row: a plain store; rows with a label < 0 or >= N write nothing).  C is NOT stored (and may be null).
+    //  ce = 2 (backward): the accumulators are recomputed and C (M, ldc) bf16 = ce_g[m] * (exp(x - ce_lse[m]) - [n == ce_labels[m]]) for n < N, zeros for N <= n < ldc
+    //    (ldc % 8 == 0, N <= ldc <= 256 * ceil(N / 256): the tiles cover the padding columns); ce_g = the per-row fp32 scale (0 for ignored rows).
+    int ce; const long* ce_labels; float* ce_target; const float* ce_lse; const float* ce_g;
 };
 constexpr int LN_STATS_STRIDE = 32;       // floats per row of a partial-statistics buffer (16 (sum, sumsq) pairs)
 
@@ -62,9 +68,9 @@ int gemm_8p128_launch(const GemmArgs& a, int ring, hipStream_t stream);
 // hipExtLaunchKernelGGL and the slot's (start, stop) events, so the pair carries the DISPATCH's own begin / end timestamps — the quantity rocprofv3 --kernel-trace
 // reports — instead of bracketing the launch with two hipEventRecord markers, which also times the gap between the markers and the kernel.
 // `family`: 0 gemm8p 256x256 (bf16 out, no activation), 1 gemm8p + GELU epilogue, 2 gemm8p implicit-GEMM conv, 3 gemm8p fp32 out (CTC head), 4 gemm8p128 (N = 512 class),
-//           5 gemm_glds, 6 gemm_bf16 (generic), 7 gemm8p argmax epilogue (CTC head without logits)
+//           5 gemm_glds, 6 gemm_bf16 (generic), 7 gemm8p argmax epilogue (CTC head without logits), 8 gemm8p cross-entropy epilogues (LM head without logits)
 extern "C" int mi_profile_take_events(hipEvent_t* start, hipEvent_t* stop, int family);
-enum { PF_8P = 0, PF_8P_GELU = 1, PF_8P_CONV = 2, PF_8P_OUT32 = 3, PF_8P128 = 4, PF_GLDS = 5, PF_GENERIC = 6, PF_8P_AMAX = 7, PF_COUNT = 8 };
+enum { PF_8P = 0, PF_8P_GELU = 1, PF_8P_CONV = 2, PF_8P_OUT32 = 3, PF_8P128 = 4, PF_GLDS = 5, PF_GENERIC = 6, PF_8P_AMAX = 7, PF_8P_CE = 8, PF_COUNT = 9 };
 
 template <typename F, typename... Args>
 inline void launch_dense(int family, F kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {

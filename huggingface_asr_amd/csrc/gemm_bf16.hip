@@ -464,3 +464,87 @@ extern "C" int mi_gemm_argmax_bf16(const void* A, long lda, const void* W, long 
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
+
+// ---- Language-model head with the cross-entropy in the GEMM's epilogue: neither the loss nor its gradient ever sees an (M, N) fp32 logit tensor (Whisper-small at
+// 16 x 448 rows x 51 865 classes: 1.5 GB written once and read at least twice, to end as one scalar and a bf16 gradient).
+//   forward (mi_gemm_ce_f32): the 256x256 kernel's CE epilogue leaves the LSE partials of mi_gemm_lse_f32 in `workspace` (mi_gemm_lse_workspace_floats(M, N) floats) and target[m] = the logit of class labels[m],
+//     stored by the one lane of the grid that holds it; the merge launch gives lse[m] and nll[m] = lse[m] - target[m] (exactly 0 for an ignored row: label < 0; a label
+//     >= N counts as ignored too), and one block sums nll in a fixed order into acc = [sum, count of valid rows] (acc is written, not added to).
+//   backward (mi_gemm_ce_bwd_bf16): the accumulators are recomputed and dlogits (M, ldo) bf16 = g[m] * (exp(x - lse[m]) - [n == labels[m]]), zeros in [N, ldo) —
+//     the ldo contract of mi_ce_label_smoothing_bwd.  g (M) fp32: 0 for an ignored row, else (loss weight) / count; the caller derives it on the device.
+// No float atomics: two runs give the same bits.  MI_ERR_UNSUPPORTED outside the 256x256 kernel's shapes (K % 64 == 0, K >= 128, 32-bit source offsets; backward:
+// ldo <= 256 * ceil(N / 256)): the caller materialises the logits (mi_gemm_bf16 + mi_row_lse / mi_ce_label_smoothing + mi_ce_label_smoothing_bwd).
+namespace {
+__global__ __launch_bounds__(256) void ce_merge_kernel(const float* __restrict__ part, int ld, int npair, const long* __restrict__ labels, const float* __restrict__ target,
+                                                       int N, float* __restrict__ lse, float* __restrict__ nll, int M) {
+    const int g = threadIdx.x & 15;                                   // lse_merge_kernel's walk: 16 lanes per row, 16 rows per block
+    const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
+    const float* pr = part + (long)min(row, M - 1) * ld;
+    float mx = -INFINITY;
+    for (int t = g; t < npair; t += 16) mx = fmaxf(mx, pr[2 * t]);
+    mx = fmaxf(mx, dpp_f32<0xB1, 0xF>(mx, mx)); mx = fmaxf(mx, dpp_f32<0x4E, 0xF>(mx, mx));
+    mx = fmaxf(mx, dpp_f32<0x141, 0xF>(mx, mx)); mx = fmaxf(mx, dpp_f32<0x140, 0xF>(mx, mx));
+    float s = 0.f;
+    for (int t = g; t < npair; t += 16) {
+        const f32x2 q = *reinterpret_cast<const f32x2*>(pr + 2 * t);
+        if (q.x > -INFINITY) s += q.y * __expf(q.x - mx);
+    }
+    s += dpp_f32<0xB1, 0xF>(0.f, s); s += dpp_f32<0x4E, 0xF>(0.f, s);
+    s += dpp_f32<0x141, 0xF>(0.f, s); s += dpp_f32<0x140, 0xF>(0.f, s);
+    if (g == 0 && row < M) {
+        const float l = mx + __logf(s);
+        const long lb = labels[row];
+        lse[row] = l;
+        nll[row] = (lb >= 0 && lb < (long)N) ? l - target[row] : 0.f;
+    }
+}
+// acc = [sum of nll over the valid rows, their count]: mi_ce_label_smoothing's scheme (one block, rows strided over the threads, wave sums by DPP, the four waves in order)
+__global__ __launch_bounds__(256) void ce_nll_sum_kernel(const float* __restrict__ nll, const long* __restrict__ labels, int M, int N, float* __restrict__ acc) {
+    __shared__ float red[8];
+    float s = 0.f, c = 0.f;
+    for (int i = threadIdx.x; i < M; i += 256) { const long lb = labels[i]; if (lb >= 0 && lb < (long)N) { s += nll[i]; c += 1.f; } }
+    s = wave_sum(s); c = wave_sum(c);
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = s; red[4 + (threadIdx.x >> 6)] = c; }
+    __syncthreads();
+    if (threadIdx.x == 0) { acc[0] = (red[0] + red[1]) + (red[2] + red[3]); acc[1] = (red[4] + red[5]) + (red[6] + red[7]); }
+}
+}  // namespace
+
+extern "C" int mi_gemm_ce_f32(const void* A, long lda, const void* W, long ldw, const float* bias, const long* labels, float* acc, float* lse, float* nll, float* target,
+                              float* workspace, int M, int N, int K, hipStream_t stream) {
+    MI_ENTER();
+    if (!A || !W || !labels || !acc || !lse || !nll || !target || !workspace) return MI_ERR_ARG;
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.lda = lda; a.W = (const bf16_t*)W; a.ldw = ldw; a.bias = bias; a.bias_mode = bias ? 1 : 0;
+    a.C = nullptr; a.ldc = (N + 3) & ~3; a.out_f32 = 1; a.alpha = 1.f; a.act = 0; a.M = M; a.N = N; a.K = K;
+    a.lse_part = workspace; a.lse_ld = 8 * ((N + 255) / 256);
+    a.ce = 1; a.ce_labels = labels; a.ce_target = target;
+    if (!gemm_8p_supported(a, false)) return MI_ERR_UNSUPPORTED;
+    const int slot = mi_profile_hook_begin(stream, 2.0 * M * N * K);
+    const int rc = gemm_8p_launch(a, false, stream);
+    if (slot >= 0) mi_profile_hook_end(slot, stream);
+    if (rc != MI_OK) return rc;
+    MI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ce_merge_kernel, dim3((M + 15) / 16), dim3(256), 0, stream, workspace, a.lse_ld, a.lse_ld / 2, labels, target, N, lse, nll, M);
+    MI_CHECK_LAUNCH();
+    hipLaunchKernelGGL(ce_nll_sum_kernel, dim3(1), dim3(256), 0, stream, nll, labels, M, N, acc);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
+
+extern "C" int mi_gemm_ce_bwd_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, const long* labels, const float* lse, const float* g,
+                                   void* dlogits, long ldo, int M, int N, int K, hipStream_t stream) {
+    MI_ENTER();
+    if (!A || !W || !labels || !lse || !g || !dlogits || ldo < N || (ldo % 8) != 0) return MI_ERR_ARG;
+    GemmArgs a{};
+    a.A = (const bf16_t*)A; a.lda = lda; a.W = (const bf16_t*)W; a.ldw = ldw; a.bias = bias; a.bias_mode = bias ? 1 : 0;
+    a.C = dlogits; a.ldc = ldo; a.out_f32 = 1; a.alpha = 1.f; a.act = 0; a.M = M; a.N = N; a.K = K;
+    a.ce = 2; a.ce_labels = labels; a.ce_lse = lse; a.ce_g = g;
+    if (!gemm_8p_supported(a, false)) return MI_ERR_UNSUPPORTED;
+    const int slot = mi_profile_hook_begin(stream, 2.0 * M * N * K);
+    const int rc = gemm_8p_launch(a, false, stream);
+    if (slot >= 0) mi_profile_hook_end(slot, stream);
+    if (rc != MI_OK) return rc;
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}

@@ -394,6 +394,35 @@ def gemm_argmax(a, w, bias):
     return best
 
 
+def gemm_ce(a, w, labels, *, return_target=False):
+    """the language-model head with its cross-entropy, without the logits: a (M, K), w (N, K) bf16, labels (M) int64 (negative = ignored, CrossEntropyLoss's ignore_index)
+    -> (acc [sum of the valid rows' nll, their count] fp32, lse (M) fp32, nll (M) fp32 = lse - logit[label], exactly 0 on ignored rows) out of the GEMM's epilogue
+    (mi_gemm_ce_f32: no (M, N) tensor is written).  Shapes outside that kernel: the fp32 GEMM into a scratch, row_lse and ce_label_smoothing(shift=0, eps=0).
+    return_target: also the label's logit per row (M) fp32 (tests; undefined on ignored rows)."""
+    _req(a, BF16); _req(w, BF16); _req(labels, torch.int64)
+    M, K = a.shape
+    N = w.shape[0]
+    labels = labels.contiguous()
+    L = _lib.lib()
+    dev = a.device
+    acc, lse, nll, tgt = (torch.empty((n,), device=dev, dtype=torch.float32) for n in (2, M, M, M))
+    ws = torch.empty((int(L.mi_gemm_lse_workspace_floats(M, N)),), device=dev, dtype=torch.float32)
+    rc = L.mi_gemm_ce_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), None, labels.data_ptr(), acc.data_ptr(), lse.data_ptr(), nll.data_ptr(), tgt.data_ptr(),
+                          ws.data_ptr(), M, N, K, _stream())
+    if rc == _lib.ERR_UNSUPPORTED:
+        logits = gemm(a, w, out_dtype=torch.float32)
+        lse = row_lse(logits)
+        acc = torch.zeros((2,), device=dev, dtype=torch.float32)
+        L_rc = L.mi_ce_label_smoothing(logits.data_ptr(), logits.stride(0), labels.data_ptr(), 1, M, 0, N, 0.0, acc.data_ptr(), nll.data_ptr(), _stream())
+        _lib.check(L_rc, "mi_ce_label_smoothing")
+        nll = torch.nan_to_num_(nll, nan=0.0)                           # the kernel marks ignored rows with NaN
+        if return_target:
+            tgt = logits.gather(1, labels.clamp(0, N - 1)[:, None])[:, 0]
+    else:
+        _lib.check(rc, "mi_gemm_ce_f32")
+    return (acc, lse, nll, tgt) if return_target else (acc, lse, nll)
+
+
 def _lengths_i32(lengths, B, device):
     if lengths is None:
         return None

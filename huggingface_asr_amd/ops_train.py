@@ -718,6 +718,27 @@ def ce_label_smoothing_bwd(logits, labels, acc, *, shift=1, eps=0.0, weight=1.0,
     return out
 
 
+def gemm_ce_bwd(a, w, labels, lse, g, ldo=None):
+    """backward of `ops.gemm_ce` up to the logits: -> dl (M, ldo) bf16 = g[m] * (softmax(a w^T)[m] - onehot(labels[m])), columns [N, ldo) zero — the head GEMM recomputed
+    with the gradient in its epilogue (mi_gemm_ce_bwd_bf16: no fp32 logits).  lse (M) fp32 from the forward; g (M) fp32 = 0 on ignored rows, else weight / count.
+    Shapes outside that kernel: the fp32 GEMM into a scratch and ce_label_smoothing_bwd, scaled per row."""
+    _req(a, BF16); _req(w, BF16); _req(labels, torch.int64)
+    M, K = a.shape
+    N = w.shape[0]
+    labels = labels.contiguous()
+    ldo = (N + 7) // 8 * 8 if ldo is None else ldo
+    out = torch.empty((M, ldo), device=a.device, dtype=BF16)
+    rc = _L().mi_gemm_ce_bwd_bf16(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), None, labels.data_ptr(), lse.data_ptr(), g.data_ptr(), out.data_ptr(), ldo,
+                                  M, N, K, _stream())
+    if rc == _lib.ERR_UNSUPPORTED:
+        logits = gemm(a, w, out_dtype=F32)
+        one = torch.ones((2,), device=a.device, dtype=F32)              # [sum, count] = [., 1]: the kernel's weight / count is 1, the per-row scale follows
+        dl = ce_label_smoothing_bwd(logits.view(1, M, N), labels.view(1, M), one, shift=0, eps=0.0, weight=1.0, ldo=ldo)
+        return (dl.float() * g[:, None]).to(BF16)
+    _lib.check(rc, "mi_gemm_ce_bwd_bf16")
+    return out
+
+
 def embed_tokens_bwd(ids, dx, dwte, dwpe=None, *, scale=1.0, pos_offset=0, heavy_id=None):
     """dwte[ids[m]] += scale * dx[m]; dwpe[pos_offset + m % U] += dx[m].  heavy_id: a token expected on a large share of the rows (the padding token the shifted decoder
     input is filled with): summed as a masked column sum instead of one block's walk over its rows."""

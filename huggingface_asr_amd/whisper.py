@@ -5,7 +5,10 @@ The reference uses HuggingFace's Whisper classes as they are (`src/utilities/mod
 engine that takes a `WhisperEncoder` state dict and reproduces `WhisperEncoder.forward` / `WhisperFeatureExtractor`:
 Conv1d(80->d,k3)+GELU and Conv1d(d->d,k3,s2)+GELU as implicit GEMMs over a channels-last layout, + learned positions,
 pre-LN layers (fused QKV GEMM with a zero bias block for k_proj, LDS-staged attention hd=64, out-proj / FFN GEMMs with the
-residual fused), final LayerNorm."""
+residual fused), final LayerNorm.
+
+Training: the encoder's forward / backward (`WhisperEncoderEngine.forward_train` / `backward`) and, opt-in through `install_whisper(decoder=True, fused_loss=True)`, the
+decoder's teacher-forced forward / backward (`WhisperDecoderEngine.forward_train` / `backward`) and the loss out of the tied head's GEMM (`TiedHeadCE`)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -323,6 +326,7 @@ class WhisperDecoderEngine(GPT2DecoderEngine):
         for lw in w["layers"]:
             ptrs += [lw["ln1"][0], lw["ln1"][1], lw["wqkv"], lw["bqkv"], lw["wo"], lw["bo"], lw["lnc"][0], lw["lnc"][1], lw["wq"], lw["bq"],
                      lw["wco"], lw["bco"], lw["ln2"][0], lw["ln2"][1], lw["wfc"], lw["bfc"], lw["wpr"], lw["bpr"]]
+        self.__dict__.pop("_wT_cache", None)                  # the transposed copies of the training backward belong to the previous weights
         self._wtable = (C.c_void_p * len(ptrs))(*[t.data_ptr() for t in ptrs])
         self._gcfg = _lib.Gpt2Config(d=d, H=c["decoder_attention_heads"], L=L, V=c["vocab_size"], eps=1e-5, step_form=1, act=1)
         self._step_ws = None
@@ -366,6 +370,142 @@ class WhisperDecoderEngine(GPT2DecoderEngine):
         raise NotImplementedError("WhisperDecoderEngine decodes step by step (step / greedy_decode); the teacher-forced training forward stays transformers'")
 
     step_py = forward
+
+    # ---------------------------------------------------------------------------------------------------------------------------------------------
+    # Training: the teacher-forced pass over all U positions at once and its analytic backward — the block of `train_aed.JointAEDTrainer._layer_fwd` / `_layer_bwd`
+    # (causal self-attention, cross-attention over the encoder frames, MLP) with erf-GELU in the FFN-in GEMM's epilogue and transformers' parameter names, shaped like
+    # `WhisperEncoderEngine.forward_train` / `backward`.  Dropout is not covered (the binding hands such calls to transformers).
+    _wT = WhisperEncoderEngine._wT
+
+    def forward_train(self, input_ids: torch.Tensor, encoder_hidden: torch.Tensor, skip=None) -> tuple[torch.Tensor, dict]:
+        """input_ids (B, U) int64, encoder_hidden (B, T2, d) -> (last_hidden_state (B, U, d) fp32, saved).  skip: per layer, True = LayerDrop skipped it."""
+        from . import ops_train as OT
+        c, w, dev = self.cfg, self.w, self.device
+        d, H = c["d_model"], c["decoder_attention_heads"]
+        if not input_ids.is_cuda or not encoder_hidden.is_cuda:
+            raise RuntimeError("WhisperDecoderEngine needs device tensors (no CPU fallback)")
+        ids = input_ids.detach().to(torch.long).contiguous()
+        B, U = ids.shape
+        T2 = encoder_hidden.shape[1]
+        self.ensure_positions(U)
+        M, Me = B * U, B * T2
+        f32 = torch.float32
+        e16 = lambda *sh: torch.empty(sh, dtype=BF16, device=dev)
+        e32 = lambda *sh: torch.empty(sh, dtype=f32, device=dev)
+        enc_bf = ops.cast_bf16(encoder_hidden.detach().reshape(Me, d).to(f32).contiguous())
+        x = ops.embed_tokens(ids, w["wte"], w["pos"], scale=w["scale"])
+        skip = skip or [False] * len(w["layers"])
+        layers = []
+        for lw, sk in zip(w["layers"], skip):
+            if sk:
+                layers.append(None)
+                continue
+            S = dict(x=x)
+            S["a1"] = a1 = e16(M, d)
+            ops.layernorm_chain(x, lna=lw["ln1"], outa=a1)
+            S["qkv"] = qkv = ops.gemm(a1, lw["wqkv"], lw["bqkv"])
+            S["ctx1"], S["lse1"] = OT.attention_x_lse(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], B, U, U, H, causal=True)
+            S["x1"] = x1 = ops.gemm(S["ctx1"], lw["wo"], lw["bo"], out=e32(M, d), resid=x, alpha=1.0)
+            S["a2"] = a2 = e16(M, d)
+            ops.layernorm_chain(x1, lna=lw["lnc"], outa=a2)
+            S["qq"] = qq = ops.gemm(a2, lw["wq"], lw["bq"])
+            S["kv"] = kv = ops.gemm(enc_bf, lw["wkv"], lw["bkv"])
+            S["ctx2"], S["lse2"] = OT.attention_x_lse(qq, kv[:, :d], kv[:, d:], B, U, T2, H)
+            S["x2"] = x2 = ops.gemm(S["ctx2"], lw["wco"], lw["bco"], out=e32(M, d), resid=x1, alpha=1.0)
+            S["a3"] = a3 = e16(M, d)
+            ops.layernorm_chain(x2, lna=lw["ln2"], outa=a3)
+            S["mp"], S["mm"] = OT.gemm_act_fwd(a3, lw["wfc"], lw["bfc"], "gelu")
+            x = ops.gemm(S["mm"], lw["wpr"], lw["bpr"], out=e32(M, d), resid=x2, alpha=1.0)
+            layers.append(S)
+        out = e32(M, d)
+        ops.layernorm_chain(x, lna=w["lnf"], outa32=out)
+        saved = dict(B=B, U=U, T2=T2, ids=ids, enc_bf=enc_bf, x_last=x, layers=layers)
+        return out.view(B, U, d), saved
+
+    def backward(self, saved: dict, d_last_hidden: torch.Tensor, want) -> dict:
+        """Gradients keyed by the HF `WhisperDecoder` parameter names (`want(name)` -> bool; absent for what is not wanted), fp32 in the parameters' shapes, plus
+        "encoder_hidden_states" (B, T2, d) when want("encoder_hidden_states")."""
+        from . import ops_train as OT
+        from .train_aed import attention_bwd_fused
+        c, w, dev = self.cfg, self.w, self.device
+        d, H = c["d_model"], c["decoder_attention_heads"]
+        B, U, T2 = saved["B"], saved["U"], saved["T2"]
+        M, Me = B * U, B * T2
+        f32 = torch.float32
+        z = lambda *shape: torch.zeros(shape, dtype=f32, device=dev)
+        e16 = lambda *sh: torch.empty(sh, dtype=BF16, device=dev)
+        G = {}
+
+        def slot(name, *shape):
+            if want(name):
+                G[name] = z(*shape)
+                return G[name]
+            return None
+
+        def packed_rows(names, rows, cols=None):
+            """one zeroed buffer for parameters the engine keeps stacked ([Wq; Wk; Wv], [Wk; Wv] and their biases; names[i] None: a block without a parameter) when any
+            of them is wanted, and the wanted ones as row views of it"""
+            if not any(n is not None and want(n) for n in names):
+                return None
+            buf = z(rows * len(names), cols) if cols else z(rows * len(names))
+            for i, n in enumerate(names):
+                if n is not None and want(n):
+                    G[n] = buf[i * rows:(i + 1) * rows]
+            return buf
+        enc_bf = saved["enc_bf"]
+        want_enc = want("encoder_hidden_states")
+        denc = z(Me, d) if want_enc else None               # every layer's cross-attention adds its share, from the last layer down
+        dy = d_last_hidden.detach().reshape(M, d).to(f32).contiguous()
+        dx = torch.empty((M, d), dtype=f32, device=dev)
+        OT.layernorm_bwd(saved["x_last"], w["lnf"][0], dy, dx, accumulate=False, dgamma=slot("layer_norm.weight", d), dbeta=slot("layer_norm.bias", d))
+        for l in reversed(range(len(w["layers"]))):
+            S, lw = saved["layers"][l], w["layers"][l]
+            if S is None:                                   # LayerDrop skipped it: identity, no gradient
+                continue
+            p = f"layers.{l}."
+            sa, ca = p + "self_attn.", p + "encoder_attn."
+            ffn = lw["wfc"].shape[0]
+            # FFN: x3 = x2 + fc2(gelu(fc1(LN(x2))))
+            dyb = OT.add_cast(dx)
+            dw2, db2 = slot(p + "fc2.weight", d, ffn), slot(p + "fc2.bias", d)
+            if dw2 is not None or db2 is not None:
+                OT.linear_bwd(dyb, S["mm"], None, dw=dw2, db=db2, need_dx=False)
+            dmp = OT.gemm_act_bwd(dyb, self._wT((l, "wpr"), lw["wpr"]), S["mp"], "gelu")
+            da3 = OT.linear_bwd(dmp, S["a3"], self._wT((l, "wfc"), lw["wfc"]), dw=slot(p + "fc1.weight", ffn, d), db=slot(p + "fc1.bias", ffn))
+            OT.layernorm_bwd(S["x2"], lw["ln2"][0], da3, dx, accumulate=True, dgamma=slot(p + "final_layer_norm.weight", d), dbeta=slot(p + "final_layer_norm.bias", d))
+            # cross-attention: x2 = x1 + out_proj(attn(q(LN(x1)), k(enc), v(enc)))
+            dyb = OT.add_cast(dx)
+            dctx2 = OT.linear_bwd(dyb, S["ctx2"], self._wT((l, "wco"), lw["wco"]), dw=slot(ca + "out_proj.weight", d, d), db=slot(ca + "out_proj.bias", d))
+            dqq, dkv = e16(M, d), e16(Me, 2 * d)
+            kv = S["kv"]
+            attention_bwd_fused(S["qq"], kv[:, :d], kv[:, d:], S["ctx2"], dctx2, S["lse2"], dqq, dkv[:, :d], dkv[:, d:], B, U, T2, H)
+            da2 = OT.linear_bwd(dqq, S["a2"], self._wT((l, "wq"), lw["wq"]), dw=slot(ca + "q_proj.weight", d, d), db=slot(ca + "q_proj.bias", d))
+            dwkv = packed_rows([ca + "k_proj.weight", ca + "v_proj.weight"], d, d)
+            dbkv = packed_rows([None, ca + "v_proj.bias"], d)                      # k_proj has no bias
+            if dwkv is not None or dbkv is not None:
+                OT.linear_bwd(dkv, enc_bf, None, dw=dwkv, db=dbkv, need_dx=False)
+            if want_enc:
+                ops.gemm(dkv, self._wT((l, "wkv"), lw["wkv"])[:, :2 * d], out=denc, resid=denc, alpha=1.0)
+            OT.layernorm_bwd(S["x1"], lw["lnc"][0], da2, dx, accumulate=True, dgamma=slot(p + "encoder_attn_layer_norm.weight", d),
+                             dbeta=slot(p + "encoder_attn_layer_norm.bias", d))
+            # causal self-attention: x1 = x + out_proj(attn(LN(x)))
+            dyb = OT.add_cast(dx)
+            dctx1 = OT.linear_bwd(dyb, S["ctx1"], self._wT((l, "wo"), lw["wo"]), dw=slot(sa + "out_proj.weight", d, d), db=slot(sa + "out_proj.bias", d))
+            qkv = S["qkv"]
+            dqkv = e16(M, 3 * d)
+            attention_bwd_fused(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], S["ctx1"], dctx1, S["lse1"], dqkv[:, :d], dqkv[:, d:2 * d], dqkv[:, 2 * d:], B, U, U, H, causal=True)
+            dwqkv = packed_rows([sa + f"{n}_proj.weight" for n in "qkv"], d, d)
+            dbqkv = packed_rows([sa + "q_proj.bias", None, sa + "v_proj.bias"], d)
+            da1 = OT.linear_bwd(dqkv, S["a1"], self._wT((l, "wqkv"), lw["wqkv"]), dw=dwqkv, db=dbqkv)
+            OT.layernorm_bwd(S["x"], lw["ln1"][0], da1, dx, accumulate=True, dgamma=slot(p + "self_attn_layer_norm.weight", d), dbeta=slot(p + "self_attn_layer_norm.bias", d))
+        # x0 = embed_tokens[ids] + embed_positions[0 .. U)
+        V, P = w["wte"].shape[0], w["pos"].shape[0]
+        dwte, dwpe = slot("embed_tokens.weight", V, d), slot("embed_positions.weight", P, d)
+        if dwte is not None or dwpe is not None:
+            OT.embed_tokens_bwd(saved["ids"], dx, dwte if dwte is not None else z(V, d), dwpe, scale=w["scale"])
+        if want_enc:
+            G["encoder_hidden_states"] = denc.view(B, T2, d)
+        return G
 
 
 def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new_tokens, eos_token_id, pad_token_id, suppress_tokens=None, begin_suppress_tokens=None,
@@ -597,11 +737,193 @@ def hip_whisper_encoder_forward(self, input_features, attention_mask=None, **kwa
     return BaseModelOutput(last_hidden_state=out.to(self.layer_norm.weight.dtype))
 
 
-def install_whisper():
-    """Give transformers' `WhisperEncoder` the HIP forward (idempotent).  The original stays reachable as `WhisperEncoder._hfasr_reference_forward` (tests compare against it)."""
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# Decoder training (opt-in: `install_whisper(decoder=True)`).  `WhisperDecoder.forward` is replaced like the encoder's; the replacement sees the RAW keyword arguments
+# (transformers' `merge_with_config_defaults` decorator, which would turn use_cache=None into config.use_cache, wraps the original only), so a teacher-forced training call
+# (use_cache None / False, no cache) can be told from `generate`'s cached steps.
+_DECODER_KNOWN = ("input_ids", "attention_mask", "encoder_hidden_states", "past_key_values", "inputs_embeds", "position_ids", "use_cache", "output_attentions",
+                  "output_hidden_states")
+
+
+def decoder_route(kw: dict, *, training: bool, cfg) -> tuple[str, str | None]:
+    """Where a `WhisperDecoder.forward` call with the raw keyword arguments `kw` runs: ("hip", None) — the teacher-forced pass on the HIP engine —, ("stock", None) —
+    transformers' own forward, silently: cached calls, i.e. everything `generate` does —, or ("stock", reason) — transformers' own forward for a cache-less call the HIP
+    path does not cover (said once per reason; HFASR_WHISPER_STRICT=1 raises).  Pure: tensors are only asked for `.is_cuda`, `cfg` for its dropout / output attributes."""
+    g = kw.get
+    if g("past_key_values") is not None or g("use_cache") is True:
+        return "stock", None
+    if g("input_ids") is None or g("inputs_embeds") is not None:
+        return "stock", "inputs_embeds instead of input_ids"
+    if g("encoder_hidden_states") is None:
+        return "stock", "no encoder_hidden_states"
+    if g("attention_mask") is not None:
+        return "stock", "decoder attention_mask given"
+    if g("position_ids") is not None:
+        return "stock", "position_ids given"
+    if g("output_attentions") or g("output_hidden_states") or getattr(cfg, "output_attentions", False) or getattr(cfg, "output_hidden_states", False):
+        return "stock", "attentions / hidden states requested"
+    # (num_items_in_batch: what `Trainer` hands to a forward with **kwargs; transformers' Whisper classes pass it down and nothing reads it)
+    extra = sorted(k for k, v in kw.items() if k not in _DECODER_KNOWN and v is not None and k != "num_items_in_batch" and not (k == "return_dict" and v is True))
+    if extra:
+        return "stock", f"keyword arguments {extra}"
+    if not (getattr(g("input_ids"), "is_cuda", False) and getattr(g("encoder_hidden_states"), "is_cuda", False)):
+        return "stock", "CPU tensors"
+    if training and any(float(getattr(cfg, n, 0.0) or 0.0) > 0.0 for n in ("dropout", "attention_dropout", "activation_dropout")):
+        return "stock", "dropout > 0 in training: the library's dropout masks cannot match torch's"
+    return "hip", None
+
+
+def _stock_decoder_forward(self, why, kw):
+    """`_stock_forward` for the decoder: transformers' own `WhisperDecoder.forward`; `why` None = a cached call (silent, also under HFASR_WHISPER_STRICT=1)"""
+    import os
+    import warnings
     from transformers.models.whisper import modeling_whisper as MW
-    if getattr(MW.WhisperEncoder.forward, "_hfasr_hip", False):
+    if why is not None:
+        if os.environ.get("HFASR_WHISPER_STRICT") == "1":
+            raise NotImplementedError(f"huggingface_asr_amd: the HIP Whisper decoder does not cover this call ({why}) and HFASR_WHISPER_STRICT=1 forbids transformers' own forward")
+        if why not in _stock_decoder_forward.said:
+            _stock_decoder_forward.said.add(why)
+            warnings.warn(f"huggingface_asr_amd: WhisperDecoder.forward runs transformers' own PyTorch implementation for this call ({why}); the HIP engine covers the "
+                          "teacher-forced pass (input_ids + encoder_hidden_states, no cache, no masks, dropout 0) on GPU tensors", stacklevel=3)
+    return MW.WhisperDecoder._hfasr_reference_forward(self, **kw)
+
+
+_stock_decoder_forward.said = set()
+
+
+class _WhisperDecoderFn(torch.autograd.Function):
+    """forward = `WhisperDecoderEngine.forward_train`, backward = `WhisperDecoderEngine.backward` (every pass on the HIP kernels).
+    Inputs: (dec, skip, input_ids, encoder_hidden_states, *parameters in `dec.named_parameters()` order)."""
+
+    @staticmethod
+    def forward(ctx, dec, skip, input_ids, encoder_hidden, *params):
+        eng = _decoder_engine_for(dec)
+        out, saved = eng.forward_train(input_ids, encoder_hidden, skip)
+        ctx.eng, ctx.saved_fw = eng, saved
+        ctx.names = [n for n, _ in dec.named_parameters()]
+        ctx.enc_dtype = encoder_hidden.dtype
+        ctx.dtypes = [p.dtype for p in params]
+        return out.to(dec.layer_norm.weight.dtype)
+
+    @staticmethod
+    def backward(ctx, dout):
+        wanted = {n for n, need in zip(ctx.names, ctx.needs_input_grad[4:]) if need}
+        if ctx.needs_input_grad[3]:
+            wanted.add("encoder_hidden_states")
+        G = ctx.eng.backward(ctx.saved_fw, dout, lambda n: n in wanted)
+        ctx.saved_fw = None
+        genc = G.get("encoder_hidden_states")
+        out = [None, None, None, genc.to(ctx.enc_dtype) if genc is not None else None]
+        for n, dt in zip(ctx.names, ctx.dtypes):
+            g = G.get(n)
+            out.append(g.to(dt).contiguous() if g is not None else None)
+        return tuple(out)
+
+
+def hip_whisper_decoder_forward(self, input_ids=None, attention_mask=None, encoder_hidden_states=None, past_key_values=None, inputs_embeds=None, position_ids=None,
+                                use_cache=None, **kwargs):
+    """`transformers.models.whisper.modeling_whisper.WhisperDecoder.forward`: the teacher-forced pass (what `WhisperForConditionalGeneration.forward` with labels runs
+    under `train_enc_dec_asr.py --do_train`) on the HIP engine through `_WhisperDecoderFn`, LayerDrop drawn as transformers draws it; everything else — `decoder_route` —
+    is transformers' own forward."""
+    from transformers.modeling_outputs import BaseModelOutputWithPastAndCrossAttentions
+    kw = dict(input_ids=input_ids, attention_mask=attention_mask, encoder_hidden_states=encoder_hidden_states, past_key_values=past_key_values, inputs_embeds=inputs_embeds,
+              position_ids=position_ids, use_cache=use_cache, **kwargs)
+    route, why = decoder_route(kw, training=self.training, cfg=self.config)
+    if route != "hip":
+        return _stock_decoder_forward(self, why, kw)
+    skip = [bool(self.training and torch.rand([]) < self.layerdrop) for _ in range(len(self.layers))]
+    out = _WhisperDecoderFn.apply(self, skip, input_ids, encoder_hidden_states, *[p for _, p in self.named_parameters()])
+    return BaseModelOutputWithPastAndCrossAttentions(last_hidden_state=out, past_key_values=None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# The loss of the training step (opt-in: `install_whisper(fused_loss=True)`): proj_out — the tied (V, d) embedding — and CrossEntropyLoss as `ops.gemm_ce` /
+# `ops_train.gemm_ce_bwd`: the (B U, V) fp32 logits are never written.
+class TiedHeadCE(torch.autograd.Function):
+    """loss = CrossEntropyLoss()(last_hidden @ weight^T, labels): the mean over the rows with label >= 0 (NaN when there is none, every gradient then exactly zero, as
+    torch's).  backward -> (d last_hidden, d weight (V, d)); with the weight tied to embed_tokens autograd adds the embedding's share."""
+
+    @staticmethod
+    def forward(ctx, last_hidden, weight, labels):
+        V, d = weight.shape
+        hid = ops.cast_bf16(last_hidden.detach().reshape(-1, d).to(torch.float32).contiguous())
+        w16 = ops.cast_bf16(weight.detach().to(torch.float32).contiguous())
+        lab = labels.detach().reshape(-1).to(torch.long).contiguous()
+        acc, lse, _ = ops.gemm_ce(hid, w16, lab)
+        ctx.saved_fw = (hid, w16, lab, lse, acc)
+        ctx.shape, ctx.dtypes = last_hidden.shape, (last_hidden.dtype, weight.dtype)
+        return (acc[0] / acc[1]).to(last_hidden.dtype)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from . import ops_train as OT
+        hid, w16, lab, lse, acc = ctx.saved_fw
+        ctx.saved_fw = None
+        V, d = w16.shape
+        g = torch.where(lab >= 0, dloss.to(torch.float32) / acc[1], torch.zeros((), dtype=torch.float32, device=lab.device)).contiguous()
+        dl = OT.gemm_ce_bwd(hid, w16, lab, lse, g, OT.pad64(V))                    # (M, pad64(V)): the K extent of the transposed weight copy below
+        dh = dw = None
+        if ctx.needs_input_grad[0]:
+            dh = ops.gemm(dl, OT.transpose(w16), out_dtype=torch.float32).view(ctx.shape).to(ctx.dtypes[0])
+        if ctx.needs_input_grad[1]:
+            dw = OT.gemm_tn_(torch.zeros((V, d), dtype=torch.float32, device=lab.device), dl, hid, n_store=V).to(ctx.dtypes[1])
+        return dh, dw, None
+
+
+def fused_loss_route(model, kw: dict) -> bool:
+    """True when `WhisperForConditionalGeneration.forward(**kw)` (raw keyword arguments) takes the fused loss: training mode with labels, the decoder ids derived from
+    them, and a decoder call that `decoder_route` sends to the HIP path"""
+    g = kw.get
+    labels = g("labels")
+    if labels is None or not model.training or g("decoder_input_ids") is not None or g("decoder_inputs_embeds") is not None or g("return_dict") is False:
+        return False
+    if labels.shape[1] > model.max_target_positions or not getattr(labels, "is_cuda", False):
+        return False
+    src = g("input_features") if g("encoder_outputs") is None else g("encoder_outputs")[0]
+    known = ("input_features", "attention_mask", "decoder_input_ids", "decoder_attention_mask", "encoder_outputs", "past_key_values", "decoder_inputs_embeds",
+             "decoder_position_ids", "labels", "use_cache", "return_dict")
+    dkw = dict({k: v for k, v in kw.items() if k not in known}, input_ids=labels, attention_mask=g("decoder_attention_mask"), encoder_hidden_states=src,
+               past_key_values=g("past_key_values"), position_ids=g("decoder_position_ids"), use_cache=g("use_cache"))
+    return src is not None and decoder_route(dkw, training=True, cfg=model.config)[0] == "hip"
+
+
+def hip_whisper_lm_forward(self, input_features=None, attention_mask=None, decoder_input_ids=None, decoder_attention_mask=None, encoder_outputs=None, past_key_values=None,
+                           decoder_inputs_embeds=None, decoder_position_ids=None, labels=None, use_cache=None, **kwargs):
+    """`WhisperForConditionalGeneration.forward`: a training call with labels gets its loss from `TiedHeadCE` and returns `logits=None` (`Trainer.training_step` never reads
+    them); eval mode, calls without labels and everything else `fused_loss_route` declines run the original forward and return logits as before."""
+    from transformers.modeling_outputs import Seq2SeqLMOutput
+    from transformers.models.whisper import modeling_whisper as MW
+    kw = dict(input_features=input_features, attention_mask=attention_mask, decoder_input_ids=decoder_input_ids, decoder_attention_mask=decoder_attention_mask,
+              encoder_outputs=encoder_outputs, past_key_values=past_key_values, decoder_inputs_embeds=decoder_inputs_embeds, decoder_position_ids=decoder_position_ids,
+              labels=labels, use_cache=use_cache, **kwargs)
+    if not fused_loss_route(self, kw):
+        return MW.WhisperForConditionalGeneration._hfasr_reference_forward(self, **kw)
+    kwargs.pop("return_dict", None)
+    kwargs.pop("num_items_in_batch", None)                  # CrossEntropyLoss() takes its own mean, as the original forward's does
+    ids = MW.shift_tokens_right(labels, self.config.pad_token_id, self.config.decoder_start_token_id)
+    o = self.model(input_features, attention_mask=attention_mask, decoder_input_ids=ids, encoder_outputs=encoder_outputs, use_cache=use_cache, **kwargs)
+    loss = TiedHeadCE.apply(o.last_hidden_state, self.proj_out.weight, labels)
+    return Seq2SeqLMOutput(loss=loss, logits=None, past_key_values=o.past_key_values, decoder_hidden_states=o.decoder_hidden_states, decoder_attentions=o.decoder_attentions,
+                           cross_attentions=o.cross_attentions, encoder_last_hidden_state=o.encoder_last_hidden_state, encoder_hidden_states=o.encoder_hidden_states,
+                           encoder_attentions=o.encoder_attentions)
+
+
+def _replace_forward(cls, ours):
+    if getattr(cls.forward, "_hfasr_hip", False):
         return
-    MW.WhisperEncoder._hfasr_reference_forward = MW.WhisperEncoder.forward
-    hip_whisper_encoder_forward._hfasr_hip = True
-    MW.WhisperEncoder.forward = hip_whisper_encoder_forward
+    cls._hfasr_reference_forward = cls.forward
+    ours._hfasr_hip = True
+    cls.forward = ours
+
+
+def install_whisper(decoder: bool = False, fused_loss: bool = False):
+    """Give transformers' `WhisperEncoder` the HIP forward (idempotent).  The original stays reachable as `WhisperEncoder._hfasr_reference_forward` (tests compare against it).
+    Opt-in: decoder=True also replaces `WhisperDecoder.forward` (`hip_whisper_decoder_forward`: the teacher-forced training pass on the HIP engine), fused_loss=True
+    (implies decoder=True) wraps `WhisperForConditionalGeneration.forward` (`hip_whisper_lm_forward`: the training loss out of the tied head's GEMM, no logits); their
+    originals stay reachable under the same name.  With neither, both classes are left untouched."""
+    from transformers.models.whisper import modeling_whisper as MW
+    _replace_forward(MW.WhisperEncoder, hip_whisper_encoder_forward)
+    if decoder or fused_loss:
+        _replace_forward(MW.WhisperDecoder, hip_whisper_decoder_forward)
+    if fused_loss:
+        _replace_forward(MW.WhisperForConditionalGeneration, hip_whisper_lm_forward)

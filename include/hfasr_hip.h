@@ -34,7 +34,7 @@ void mi_profile_reset(void);
 int mi_profile_count(void);
 int mi_profile_summary(double* total_ms, double* total_flops);
 int mi_profile_calibrate(mi_stream_t stream, int n, double* median_ms);   /* event pair around an EMPTY kernel, median of n: what the bracket adds + the empty kernel's ~1.3 us */
-int mi_profile_summary_family(int family, double* total_ms, double* total_flops, int* launches);   /* family < 0: all; 0 gemm8p, 1 gemm8p+GELU, 2 gemm8p conv, 3 gemm8p fp32 out, 4 gemm8p128, 5 gemm_glds, 6 generic, 7 gemm8p argmax epilogue */
+int mi_profile_summary_family(int family, double* total_ms, double* total_flops, int* launches);   /* family < 0: all; 0 gemm8p, 1 gemm8p+GELU, 2 gemm8p conv, 3 gemm8p fp32 out, 4 gemm8p128, 5 gemm_glds, 6 generic, 7 gemm8p argmax epilogue, 8 gemm8p cross-entropy epilogues */
 
 /* ---- nn.Linear / lm_head / projections: C[M,N] = epi(A[M,K] * W[N,K]^T), bf16 in, fp32 accumulate (MFMA).
  * replaces: every nn.Linear on the path — reference src/models/encoders/e_branchformer.py:96-98,139,212-216,247,456-457;
@@ -273,6 +273,18 @@ int mi_ctc_greedy(const void* logits, long ld_row, long ld_batch, int dtype, int
  * scratch + mi_row_argmax. */
 size_t mi_gemm_argmax_workspace_floats(int M, int N);
 int mi_gemm_argmax_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, int* best, float* workspace, int M, int N, int K, mi_stream_t stream);
+/* ---- Language-model head with the cross-entropy in its epilogue. replaces: proj_out (the tied (V, d) embedding) + CrossEntropyLoss of transformers'
+ * WhisperForConditionalGeneration.forward under train_enc_dec_asr.py, forward and backward, without the (M, N) fp32 logits (1.5 GB at Whisper-small, 16 x 448 rows).
+ * forward: labels (M) int64, negative = ignored (CrossEntropyLoss's ignore_index; a label >= N counts as ignored too).  The 256 x 256 GEMM's epilogue leaves the LSE partials
+ * in `workspace` (mi_gemm_lse_workspace_floats(M, N) floats) and target[m] = the logit of class labels[m] (rows without a valid label: not written); a merge launch gives
+ * lse[m] and nll[m] = lse[m] - target[m] (exactly 0 for ignored rows), one block sums them in a fixed order: acc = [sum, count of valid rows] (written, not added to).
+ * backward: the accumulators are recomputed, dlogits (M, ldo) bf16 = g[m] * (exp(x - lse[m]) - [n == labels[m]]) for n < N and zeros for N <= n < ldo (ldo % 8 == 0:
+ * mi_ce_label_smoothing_bwd's layout); g (M) fp32 = 0 for ignored rows, else weight / count.  No float atomics.  MI_ERR_UNSUPPORTED outside the 256 x 256 kernel's
+ * shapes (K % 64, K >= 128, 16-B aligned operands, 32-bit source offsets; backward: ldo <= 256 * ceil(N / 256)): the caller materialises the logits. */
+int mi_gemm_ce_f32(const void* A, long lda, const void* W, long ldw, const float* bias, const long* labels, float* acc, float* lse, float* nll, float* target,
+                   float* workspace, int M, int N, int K, mi_stream_t stream);
+int mi_gemm_ce_bwd_bf16(const void* A, long lda, const void* W, long ldw, const float* bias, const long* labels, const float* lse, const float* g,
+                        void* dlogits, long ldo, int M, int N, int K, mi_stream_t stream);
 int mi_ctc_loss_fwd(const void* logits, long ld_b, long ld_t, int dtype, const float* lse, int T,
                     const long* labels, int U, const int* in_len, int blank, int B,
                     int reduction, int zero_infinity, float* nll, int* tgt_len, float* loss, mi_stream_t stream);
