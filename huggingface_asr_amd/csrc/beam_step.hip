@@ -13,6 +13,10 @@
 // The host loop did this with two device -> host copies, a Python walk and three host -> device copies per token (~0.3 ms of a 0.8 ms token); here it is one
 // launch, nothing leaves the device until decoding ends, and the host only enqueues.  Arithmetic is the host loop's, operation for operation (fp32 subtract,
 // two multiplies and an add without contraction, fp32 beam add, fp32 division for the kept hypotheses), so both produce the same hypotheses bit for bit.
+//
+// Shallow fusion (mi_beam_step_lm; reference src/decoding/shallow_fussion.py:41-53, appended behind the CTC processor, ctc_encoder_plus_autoregressive_decoder.py:398-403):
+//     scores = scores + lm_weight * log_softmax(LM logits)        — one more (B * W, V) stream and its row log-sum-exp, added between the CTC mix and the beam add.
+// The kernel is a template on the LM term: the LM-off instantiation is the kernel as it was.
 #include "common.hpp"
 #include "../../include/hfasr_hip.h"
 
@@ -42,9 +46,14 @@ struct BeamArgs {
     int* done; int* nfin; float* fin_score; int* fin_len; long* fin_tok;      // (B), (B), (B, W), (B, W), (B, W, Lmax): the kept hypotheses, best first
     float* top_s; int* top_i;             // optional (B, 2W): the candidates the step walked
     int* done_out;                        // optional (B): copy of the done flags after the step (host-mapped pinned memory: the host polls it without a copy on the stream)
+    // shallow fusion (read by the LM instantiation only; appended, so every field above keeps its kernel-argument offset)
+    const float* lm_logits; long ldlm;    // (B * W, V) logits of the external LM for the same prefixes
+    const float* lm_lse;                  // (B * W) their row log-sum-exp
+    float w_lm;
 };
 
 // the host loop's arithmetic, one rounding per operation: no multiply-add contraction here (HIP's __fmul_rn / __fadd_rn are plain operators, so the pragma is what holds it)
+template <bool LM>
 __device__ __forceinline__ float cand_value(const BeamArgs& p, int b, int e) {
 #pragma clang fp contract(off)
     const int beam = e / p.V, tok = e - beam * p.V;
@@ -54,6 +63,11 @@ __device__ __forceinline__ float cand_value(const BeamArgs& p, int b, int e) {
     if (p.ctc) {
         const float a = p.w_att * s, c = p.w_ctc * p.ctc[row * p.V + tok];
         s = a + c;
+    }
+    if (LM) {                                                          // scores + lm_weight * log_softmax(lm): subtract, multiply, add — each rounded
+        const float l = p.lm_logits[row * p.ldlm + tok] - p.lm_lse[row];
+        const float m = p.w_lm * l;
+        s = s + m;
     }
     return s + p.beam_scores[row];
 }
@@ -79,6 +93,27 @@ __device__ __forceinline__ void load_pass(const BeamArgs& p, int b, int W, int t
     }
 }
 
+// LM form of the cached pass: a thread's 32 candidates in two halves of 16.  Three input streams of 32 values beside cv[32] would not fit the 128 registers a lane of a
+// 1024-thread block has; a half holds 3 x 16.  Candidates e0 + 1024 i, i < 8 NG (clamped addresses past the last candidate; the rest zero), every load of the half
+// requested before the first is used.
+template <int NG>
+__device__ __forceinline__ void load_half_lm(const BeamArgs& p, int b, int W, int e0, int qstep, int rstep, float (&lg)[16], float (&ct)[16], float (&lm)[16]) {
+    int beam = e0 / p.V, tok = e0 - beam * p.V;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (i < NG * 8) {
+            const int bc = beam < W ? beam : W - 1;
+            const long row = (long)b * W + bc;
+            lg[i] = p.logits[row * p.ldl + tok];
+            ct[i] = p.ctc ? p.ctc[row * p.V + tok] : 0.f;
+            lm[i] = p.lm_logits[row * p.ldlm + tok];
+            beam += qstep; tok += rstep;
+            if (tok >= p.V) { tok -= p.V; ++beam; }
+        } else { lg[i] = 0.f; ct[i] = 0.f; lm[i] = 0.f; }
+    }
+}
+
+template <bool LM>
 __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     long* stage = reinterpret_cast<long*>(smem);                       // [W][cur_len] the utterance's input ids before the step
@@ -119,6 +154,52 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
             __shared__ float row_lse[BS_MAXW], row_bs[BS_MAXW];
             if (tid < W) { row_lse[tid] = p.lse[(long)b * W + tid]; row_bs[tid] = p.beam_scores[(long)b * W + tid]; }
             const int qstep = BS_THREADS / p.V, rstep = BS_THREADS - qstep * p.V;
+            if constexpr (LM) {
+                __shared__ float row_lmlse[BS_MAXW];
+                if (tid < W) row_lmlse[tid] = p.lm_lse[(long)b * W + tid];
+                const int ng = (N + 8 * BS_THREADS - 1) / (8 * BS_THREADS);  // groups of eight candidates per thread that hold any at all (block-uniform)
+#pragma unroll
+                for (int half = 0; half < 2; ++half) {
+                    const int ngh = ng - 2 * half;                           // groups of this half
+                    if (ngh <= 0) {                                          // (block-uniform) nothing here: the thread's candidates 16 .. 31 do not exist
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) cv[16 * half + i] = -INFINITY;
+                        alive &= ~(0xffffu << (16 * half));
+                        continue;
+                    }
+                    const int e0 = tid + 16 * half * BS_THREADS;
+                    float lg[16], ct[16], lm[16];
+                    if (ngh >= 2) load_half_lm<2>(p, b, W, e0, qstep, rstep, lg, ct, lm);
+                    else load_half_lm<1>(p, b, W, e0, qstep, rstep, lg, ct, lm);
+                    if (half == 0) __syncthreads();                          // the per-row scalars are in LDS (the first half's loads are already in flight)
+                    {
+#pragma clang fp contract(off)
+                        int beam = e0 / p.V, tok = e0 - beam * p.V;
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) {
+                            const int e = e0 + i * BS_THREADS;
+                            const int bc = beam < W ? beam : 0;
+                            float sc = lg[i] - row_lse[bc];
+                            if (p.mask_pad && tok == p.pad) sc = LOGZERO;
+                            if (p.ctc) {
+                                const float a = p.w_att * sc, c = p.w_ctc * ct[i];
+                                sc = a + c;
+                            }
+                            const float l = lm[i] - row_lmlse[bc];
+                            const float m = p.w_lm * l;
+                            sc = sc + m;
+                            sc = sc + row_bs[bc];
+                            cv[16 * half + i] = sc;
+                            if (e < N) {
+                                if (better(sc, e, mv, me)) { mv2 = mv; me2 = me; mv = sc; me = e; }
+                                else if (better(sc, e, mv2, me2)) { mv2 = sc; me2 = e; }
+                            } else alive &= ~(1u << (16 * half + i));
+                            beam += qstep; tok += rstep;
+                            if (tok >= p.V) { tok -= p.V; ++beam; }
+                        }
+                    }
+                }
+            } else {
             float lg[CPT], ct[CPT];
             const int ng = (N + 8 * BS_THREADS - 1) / (8 * BS_THREADS);      // groups of eight candidates per thread that hold any at all (block-uniform)
             if (ng >= 4) load_pass<4>(p, b, W, tid, qstep, rstep, lg, ct);     // one straight-line block per count: every load of the pass is in flight together
@@ -149,9 +230,10 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
                     if (tok >= p.V) { tok -= p.V; ++beam; }
                 }
             }
+            }
         } else
             for (int e = tid; e < N; e += BS_THREADS) {
-                const float v = cand_value(p, b, e);
+                const float v = cand_value<LM>(p, b, e);
                 if (better(v, e, mv, me)) { mv = v; me = e; }
             }
     }
@@ -184,7 +266,7 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
             } else {
                 mv = -INFINITY; me = 0x7fffffff;
                 for (int e = tid; e < N; e += BS_THREADS) {
-                    const float v = cand_value(p, b, e);
+                    const float v = cand_value<LM>(p, b, e);
                     if (comes_after(v, e, bv, be) && better(v, e, mv, me)) { mv = v; me = e; }
                 }
             }
@@ -281,20 +363,36 @@ __global__ __launch_bounds__(BS_THREADS) void beam_step_kernel(BeamArgs p) {
 
 }  // namespace
 
-extern "C" int mi_beam_step(const float* logits, long ldl, const float* lse, const float* ctc, float w_att, float w_ctc, int mask_pad, int pad, int eos, int B, int W,
-                            int V, int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok,
-                            long* beam_idx, int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out, hipStream_t stream) {
+// lm_logits (B * W, ld_lm) fp32 / lm_lse (B * W) / w_lm: the shallow-fusion term, added behind the CTC mix; lm_logits == NULL: no term (lm_lse / w_lm ignored) —
+// the LM-off instantiation, which is mi_beam_step
+extern "C" int mi_beam_step_lm(const float* logits, long ldl, const float* lse, const float* ctc, float w_att, float w_ctc, int mask_pad, int pad, int eos, int B, int W,
+                               int V, int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok,
+                               long* beam_idx, int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out,
+                               const float* lm_logits, long ld_lm, const float* lm_lse, float w_lm, hipStream_t stream) {
     MI_ENTER();
     if (!logits || !lse || !ids || !beam_scores || !new_tok || !beam_idx || !done || !nfin || !fin_score || !fin_len || !fin_tok) return MI_ERR_ARG;
     if (B <= 0 || W <= 0 || W > BS_MAXW || V <= 1 || (long)W * V >= (1l << 24) || cur_len <= 0 || cur_len >= Lmax || cur_len >= max_length || max_length > Lmax || pad < 0 ||
         pad >= V || !(denom > 0.f) || !(heur_denom > 0.f) || early_stopping < 0 || early_stopping > 2)
         return MI_ERR_ARG;
+    if (lm_logits && (!lm_lse || ld_lm < V)) return MI_ERR_ARG;
     const size_t lds = (size_t)W * (cur_len + Lmax) * sizeof(long);
     if (lds > 96 * 1024) return MI_ERR_UNSUPPORTED;
     BeamArgs a{logits, ldl, lse, ctc, w_att, w_ctc, mask_pad, pad, eos, B, W, V, cur_len, max_length, Lmax, denom, heur_denom, early_stopping, ids, beam_scores, new_tok, beam_idx,
-               done, nfin, fin_score, fin_len, fin_tok, top_s, top_i, done_out};
-    if (!ensure_dynamic_lds<0>(reinterpret_cast<const void*>(beam_step_kernel), 96 * 1024)) return MI_ERR_LAUNCH;        // per device (a function-local static configured only the first one)
-    hipLaunchKernelGGL(beam_step_kernel, dim3(B), dim3(BS_THREADS), lds, stream, a);
+               done, nfin, fin_score, fin_len, fin_tok, top_s, top_i, done_out, lm_logits, ld_lm, lm_lse, w_lm};
+    if (lm_logits) {
+        if (!ensure_dynamic_lds<1>(reinterpret_cast<const void*>(beam_step_kernel<true>), 96 * 1024)) return MI_ERR_LAUNCH;
+        hipLaunchKernelGGL(beam_step_kernel<true>, dim3(B), dim3(BS_THREADS), lds, stream, a);
+    } else {
+        if (!ensure_dynamic_lds<0>(reinterpret_cast<const void*>(beam_step_kernel<false>), 96 * 1024)) return MI_ERR_LAUNCH;        // per device (a function-local static configured only the first one)
+        hipLaunchKernelGGL(beam_step_kernel<false>, dim3(B), dim3(BS_THREADS), lds, stream, a);
+    }
     MI_CHECK_LAUNCH();
     return MI_OK;
+}
+
+extern "C" int mi_beam_step(const float* logits, long ldl, const float* lse, const float* ctc, float w_att, float w_ctc, int mask_pad, int pad, int eos, int B, int W,
+                            int V, int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok,
+                            long* beam_idx, int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out, hipStream_t stream) {
+    return mi_beam_step_lm(logits, ldl, lse, ctc, w_att, w_ctc, mask_pad, pad, eos, B, W, V, cur_len, max_length, Lmax, denom, heur_denom, early_stopping, ids, beam_scores,
+                           new_tok, beam_idx, done, nfin, fin_score, fin_len, fin_tok, top_s, top_i, done_out, nullptr, 0, nullptr, 0.f, stream);
 }

@@ -15,6 +15,9 @@
 // dependent loads are consumed, so a launch is ~two memory round trips deep.
 //
 // Eligible: one new token per row (U = 1), M = B <= 8 rows, head size 64, d <= 512 a multiple of 64; everything else runs the launch-per-op step.
+//
+// A block without cross-attention (cross_kv == NULL: the GPT-2 language model of shallow fusion) is TWO launches per layer: B is not enqueued, and C's prologue — the
+// same Pending sum, unchanged kernels — takes A's per-head partials and bo where it took B's and bco.  Same fixed summation order, no atomics, no grid barrier.
 // Replaces per token what the reference runs through transformers' GPT2Model.forward with a KV cache (multi_head_gpt2.py:80-170, tf gpt2 modeling :262-310).
 #include "common.hpp"
 #include "../../include/hfasr_hip.h"
@@ -396,7 +399,7 @@ size_t gpt2_step_fused_floats(const mi_gpt2_config& c, int M) {
 }
 
 // ids: (M) int64 new tokens, embedded by the first launch (wte = weights[0] scaled by emb_scale, + position row `past` of weights[1]); fws: gpt2_step_fused_floats(c, M)
-// floats; hid: (M, d) bf16 out = ln_f(stream) for the lm head.  Weight table as mi_gpt2_step.
+// floats; hid: (M, d) bf16 out = ln_f(stream) for the lm head.  Weight table as mi_gpt2_step.  cross_kv null: no cross-attention launch (T_enc / enc_len unused).
 int gpt2_step_fused(const mi_gpt2_config& c, const void* const* weights, const long* ids, float emb_scale, int M, int past, int Lmax, void* const* kcache, void* const* vcache,
                     const void* const* cross_kv, int T_enc, const int* enc_len, float* fws, bf16_t* hid, hipStream_t st) {
     const int d = c.d, H = c.H, J = d / 16;
@@ -422,12 +425,15 @@ int gpt2_step_fused(const mi_gpt2_config& c, const void* const* weights, const l
         a.part_out = pb[pi]; a.kc = (bf16_t*)kcache[l]; a.vc = (bf16_t*)vcache[l]; a.past = past; a.Lmax = Lmax;
         hipLaunchKernelGGL(fused_self_kernel, dim3(M * H), dim3(256), 0, st, a);
         advance(pb[pi], Lf(l, 5), H); pi ^= 1;
-        FusedArgs b{};
-        b.M = M; b.d = d; b.H = H; b.scale = scale; b.eps = c.eps;
-        b.pd = pd; b.ln_g = Lf(l, 6); b.ln_b = Lf(l, 7); b.Win = (const bf16_t*)Lw(l, 8); b.bin = Lf(l, 9); b.Wout = (const bf16_t*)Lw(l, 10);
-        b.part_out = pb[pi]; b.ckv = (const bf16_t*)cross_kv[l]; b.T_enc = T_enc; b.enc_len = enc_len;
-        hipLaunchKernelGGL(fused_cross_kernel, dim3(M * H), dim3(256), 0, st, b);
-        advance(pb[pi], Lf(l, 11), H); pi ^= 1;
+        if (cross_kv) {
+            FusedArgs b{};
+            b.M = M; b.d = d; b.H = H; b.scale = scale; b.eps = c.eps;
+            b.pd = pd; b.ln_g = Lf(l, 6); b.ln_b = Lf(l, 7); b.Win = (const bf16_t*)Lw(l, 8); b.bin = Lf(l, 9); b.Wout = (const bf16_t*)Lw(l, 10);
+            b.part_out = pb[pi]; b.ckv = (const bf16_t*)cross_kv[l]; b.T_enc = T_enc; b.enc_len = enc_len;
+            hipLaunchKernelGGL(fused_cross_kernel, dim3(M * H), dim3(256), 0, st, b);
+            advance(pb[pi], Lf(l, 11), H); pi ^= 1;
+        }
+        // (without cross-attention the MLP launch's pending sum is A's: base = the row A stored — layer 0: the embedded row —, H per-head partials, bias bo)
         FusedArgs m{};
         m.M = M; m.d = d; m.H = H; m.eps = c.eps;
         m.pd = pd; m.ln_g = Lf(l, 12); m.ln_b = Lf(l, 13); m.Win = (const bf16_t*)Lw(l, 14); m.bin = Lf(l, 15); m.Wout = (const bf16_t*)Lw(l, 16);

@@ -321,6 +321,8 @@ extern "C" size_t mi_gpt2_step_workspace_bytes(const mi_gpt2_config* cfg, int B,
 // ids_new (B,U) int64; kcache / vcache: L pointers to (B, Lmax, d) bf16; cross_kv: L pointers to (B*T_enc, 2d) bf16 [K | V];
 // logits (B, ld_logits) f32 of the LAST new position (+ head_bias (V) f32 when not null: 0 / -inf token suppression).  Appends the new tokens' K/V at rows [past, past + U).
 // cfg->act selects the MLP activation (0 gelu_new, 1 erf-GELU: the Whisper decoder block, which is this block with separate q / k / v matrices packed into wqkv).
+// cross_kv == NULL: the plain causal GPT-2 block (transformers GPT2LMHeadModel without add_cross_attention: the language model of shallow fusion) — ln_1, self-attention
+// over the cache, ln_2, MLP; the four cross ops are skipped in every form, the table keeps its 18 slots per layer (the six cross entries unread), T_enc / enc_len ignored.
 extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
                                void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
                                float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
@@ -342,7 +344,8 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         return mi_layernorm_chain(x, ldx, nullptr, 1, nullptr, nullptr, 0.f, nullptr, 0, g, b, c.eps, out, d, nullptr, 0, nullptr, nullptr, nullptr, 0, rows, d, st);
     };
     if (c.step_form == 0 && c.act == 0 && w.fws) {
-        // ---- fused token step (decoder_fused.hip): three launches per layer, every cross-workgroup reduction folded into the next launch's prologue (the embedding too)
+        // ---- fused token step (decoder_fused.hip): three launches per layer (two without cross-attention), every cross-workgroup reduction folded into the next launch's
+        // prologue (the embedding too)
         RUN(gpt2_step_fused(c, weights, ids_new, emb_scale, M, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, w.fws, w.hid, st));
         SkArgs a{}; a.x16 = w.hid; a.ldx16 = d; a.W = (const bf16_t*)weights[4]; a.ldw = d; a.out32 = logits; a.ldo32 = ld_logits; a.M = B; a.N = c.V; a.K = d; a.act = 0;
         a.bias = head_bias;
@@ -359,15 +362,17 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         for (int l = 0; l < c.L; ++l) {
             bf16_t* kc = (bf16_t*)kcache[l];
             bf16_t* vc = (bf16_t*)vcache[l];
-            const bf16_t* ckv = (const bf16_t*)cross_kv[l];
+            const bf16_t* ckv = cross_kv ? (const bf16_t*)cross_kv[l] : nullptr;          // null: a block without cross-attention
             RUN(ln(w.x, d, Lf(l, 0), Lf(l, 1), w.a, M));
             RUN(lin(w.a, d, Lw(l, 2), Lf(l, 3), 3 * d, 0, nullptr, 0, 0, w.qkv, kc, vc));
             RUN(decode_attn(DecAttnArgs{w.qkv, 3 * d, kc, vc, d, (long)Lmax * d, nullptr, w.ctx, d, M, U, c.H, past, 1, 0, scale}, hd, st));
             RUN(lin(w.ctx, d, Lw(l, 4), Lf(l, 5), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
-            RUN(ln(w.x, d, Lf(l, 6), Lf(l, 7), w.a, M));
-            RUN(lin(w.a, d, Lw(l, 8), Lf(l, 9), d, 0, nullptr, 0, 0, w.qq, nullptr, nullptr));
-            RUN(decode_attn(DecAttnArgs{w.qq, d, ckv, ckv + d, 2 * d, (long)T_enc * 2 * d, enc_len, w.ctx, d, M, U, c.H, 0, 0, T_enc, scale}, hd, st));
-            RUN(lin(w.ctx, d, Lw(l, 10), Lf(l, 11), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
+            if (ckv) {
+                RUN(ln(w.x, d, Lf(l, 6), Lf(l, 7), w.a, M));
+                RUN(lin(w.a, d, Lw(l, 8), Lf(l, 9), d, 0, nullptr, 0, 0, w.qq, nullptr, nullptr));
+                RUN(decode_attn(DecAttnArgs{w.qq, d, ckv, ckv + d, 2 * d, (long)T_enc * 2 * d, enc_len, w.ctx, d, M, U, c.H, 0, 0, T_enc, scale}, hd, st));
+                RUN(lin(w.ctx, d, Lw(l, 10), Lf(l, 11), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
+            }
             RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
             RUN(lin(w.a, d, Lw(l, 14), Lf(l, 15), 4 * d, mlp_act, nullptr, 0, 0, w.m, nullptr, nullptr));
             RUN(lin(w.m, 4 * d, Lw(l, 16), Lf(l, 17), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
@@ -392,7 +397,7 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         for (int l = 0; l < c.L; ++l) {
             bf16_t* kc = (bf16_t*)kcache[l];
             bf16_t* vc = (bf16_t*)vcache[l];
-            const bf16_t* ckv = (const bf16_t*)cross_kv[l];
+            const bf16_t* ckv = cross_kv ? (const bf16_t*)cross_kv[l] : nullptr;          // null: a block without cross-attention
             {   // LN1 + fused QKV projection; its K / V columns go straight into the caches as well
                 SkArgs a{}; a.x32 = w.x; a.ldx = d; a.ln_g = Lf(l, 0); a.ln_b = Lf(l, 1); a.eps = c.eps; a.W = (const bf16_t*)Lw(l, 2); a.ldw = d; a.bias = Lf(l, 3);
                 a.out16 = w.qkv; a.ldo16 = 3 * d; a.M = M; a.N = 3 * d; a.K = d; a.act = 0;
@@ -401,9 +406,11 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
             }
             RUN(decode_attn(DecAttnArgs{w.qkv, 3 * d, kc, vc, d, (long)Lmax * d, nullptr, w.ctx, d, M, U, c.H, past, 1, 0, scale}, hd, st));
             RUN(lin_res(w.ctx, d, Lw(l, 4), Lf(l, 5)));
-            RUN(lin_ln(Lf(l, 6), Lf(l, 7), Lw(l, 8), Lf(l, 9), d, w.qq, 0));
-            RUN(decode_attn(DecAttnArgs{w.qq, d, ckv, ckv + d, 2 * d, (long)T_enc * 2 * d, enc_len, w.ctx, d, M, U, c.H, 0, 0, T_enc, scale}, hd, st));
-            RUN(lin_res(w.ctx, d, Lw(l, 10), Lf(l, 11)));
+            if (ckv) {
+                RUN(lin_ln(Lf(l, 6), Lf(l, 7), Lw(l, 8), Lf(l, 9), d, w.qq, 0));
+                RUN(decode_attn(DecAttnArgs{w.qq, d, ckv, ckv + d, 2 * d, (long)T_enc * 2 * d, enc_len, w.ctx, d, M, U, c.H, 0, 0, T_enc, scale}, hd, st));
+                RUN(lin_res(w.ctx, d, Lw(l, 10), Lf(l, 11)));
+            }
             RUN(lin_ln(Lf(l, 12), Lf(l, 13), Lw(l, 14), Lf(l, 15), 4 * d, w.m, 2));
             RUN(lin_res(w.m, 4 * d, Lw(l, 16), Lf(l, 17)));
         }
@@ -417,7 +424,7 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
     for (int l = 0; l < c.L; ++l) {
         bf16_t* kc = (bf16_t*)kcache[l];
         bf16_t* vc = (bf16_t*)vcache[l];
-        const bf16_t* ckv = (const bf16_t*)cross_kv[l];
+        const bf16_t* ckv = cross_kv ? (const bf16_t*)cross_kv[l] : nullptr;          // null: a block without cross-attention
         RUN(ln(w.x, d, Lf(l, 0), Lf(l, 1), w.a, M));
         RUN(mi_gemm_bf16(w.a, d, Lw(l, 2), d, Lf(l, 3), 1, w.qkv, 3 * d, 0, nullptr, 0, 1.f, 0, M, 3 * d, d, 0, 0, st));
         {
@@ -427,10 +434,12 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         RUN(mi_attention_qkv_bf16(w.qkv, 3 * d, kc, d, vc, d, nullptr, 0, nullptr, nullptr, nullptr, w.ctx, d, B, U, past + U, (long)Lmax * d, c.H, hd,
                                   scale, 1, st));
         RUN(mi_gemm_bf16(w.ctx, d, Lw(l, 4), d, Lf(l, 5), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, d, 0, 0, st));
-        RUN(ln(w.x, d, Lf(l, 6), Lf(l, 7), w.a, M));
-        RUN(mi_gemm_bf16(w.a, d, Lw(l, 8), d, Lf(l, 9), 1, w.qq, d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
-        RUN(mi_attention_qkv_bf16(w.qq, d, ckv, 2 * d, ckv + d, 2 * d, nullptr, 0, nullptr, nullptr, enc_len, w.ctx, d, B, U, T_enc, 0, c.H, hd, scale, 0, st));
-        RUN(mi_gemm_bf16(w.ctx, d, Lw(l, 10), d, Lf(l, 11), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, d, 0, 0, st));
+        if (ckv) {
+            RUN(ln(w.x, d, Lf(l, 6), Lf(l, 7), w.a, M));
+            RUN(mi_gemm_bf16(w.a, d, Lw(l, 8), d, Lf(l, 9), 1, w.qq, d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
+            RUN(mi_attention_qkv_bf16(w.qq, d, ckv, 2 * d, ckv + d, 2 * d, nullptr, 0, nullptr, nullptr, enc_len, w.ctx, d, B, U, T_enc, 0, c.H, hd, scale, 0, st));
+            RUN(mi_gemm_bf16(w.ctx, d, Lw(l, 10), d, Lf(l, 11), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, d, 0, 0, st));
+        }
         RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
         RUN(mi_gemm_bf16(w.a, d, Lw(l, 14), d, Lf(l, 15), 1, w.m, 4 * d, 0, nullptr, 0, 1.f, mlp_act, M, 4 * d, d, 0, 0, st));
         RUN(mi_gemm_bf16(w.m, 4 * d, Lw(l, 16), 4 * d, Lf(l, 17), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, 4 * d, 0, 0, st));

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib, ops
 from .engine import EBranchformerEngine
-from .packing import _dec_map, decoder_specs, mapped_fp32, packed
+from .packing import _dec_map, _lm_map, decoder_specs, lm_specs, mapped_fp32, packed
 
 BF16 = torch.bfloat16
 
@@ -219,6 +219,84 @@ class GPT2DecoderEngine:
         return self._logits(hid, w["lm_head"])
 
 
+def lm_cfg_dict(c) -> dict:
+    """the fields of a transformers `GPT2Config` that `GPT2LMEngine` reads"""
+    return dict(vocab_size=c.vocab_size, n_embd=c.n_embd, n_layer=c.n_layer, n_head=c.n_head, n_positions=c.n_positions, n_inner=getattr(c, "n_inner", None),
+                layer_norm_epsilon=c.layer_norm_epsilon, activation_function=c.activation_function,
+                scale_attn_weights=bool(getattr(c, "scale_attn_weights", True)),
+                scale_attn_by_inverse_layer_idx=bool(getattr(c, "scale_attn_by_inverse_layer_idx", False)),
+                reorder_and_upcast_attn=bool(getattr(c, "reorder_and_upcast_attn", False)), add_cross_attention=bool(getattr(c, "add_cross_attention", False)))
+
+
+class GPT2LMEngine(GPT2DecoderEngine):
+    """transformers' `GPT2LMHeadModel` as a KV-cached token step on the HIP path: the external language model of shallow fusion (reference
+    src/decoding/shallow_fussion.py:41-53, which re-runs the LM over the whole prefix for every token).  `GPT2DecoderEngine` without the cross parts: the same pointer
+    table with the six cross entries of a layer null, `mi_gpt2_step` called without encoder K/V; cache, beam re-ordering and the position check are inherited."""
+
+    def __init__(self, cfg: dict, device="cuda:0"):
+        super().__init__(cfg, device)                      # head size 64 / 128, gelu_new
+        d = cfg["n_embd"]
+        if cfg.get("n_inner") not in (None, 4 * d):
+            raise NotImplementedError(f"GPT-2 LM with n_inner = {cfg['n_inner']}: the HIP block has a 4 * n_embd MLP")
+        if not cfg.get("scale_attn_weights", True):
+            raise NotImplementedError("GPT-2 LM with scale_attn_weights = False")
+        for k in ("scale_attn_by_inverse_layer_idx", "reorder_and_upcast_attn", "add_cross_attention"):
+            if cfg.get(k, False):
+                raise NotImplementedError(f"GPT-2 LM with {k} = True is not implemented on the HIP path")
+
+    def load_state_dict(self, sd: dict, prefix: str = ""):
+        """every packed parameter of packing.lm_specs; a state dict without `lm_head.weight` has the token embedding as its head"""
+        c, dev = self.cfg, self.device
+        d, L = c["n_embd"], c["n_layer"]
+        c = dict(c, tie_word_embeddings=(prefix + "lm_head.weight") not in sd)
+        m = _lm_map(c, prefix)
+        P = {s.name: (t.to(BF16) if s.mat and s.name != "wte" else t).contiguous() for s, t in packed(lm_specs(c), m, mapped_fp32(m, sd, dev))}
+        w = dict(wte=P["wte"], scale=1.0, pos=P["wpe"], lnf=(P["lnf_g"], P["lnf_b"]), lm_head=P["lm_head"] if "lm_head" in P else P["wte"].to(BF16))
+        w["layers"] = [dict({n: P[f"h{l}.{n}"] for n in ("wqkv", "bqkv", "wo", "bo", "wfc", "bfc", "wpr", "bpr")},
+                            **{n: (P[f"h{l}.{n}_g"], P[f"h{l}.{n}_b"]) for n in ("ln1", "ln2")}) for l in range(L)]
+        self.w = w
+        ptr = lambda t: t.data_ptr()
+        ptrs = [ptr(w["wte"]), ptr(w["pos"]), ptr(w["lnf"][0]), ptr(w["lnf"][1]), ptr(w["lm_head"])]
+        for lw in w["layers"]:                             # mi_gpt2_step's 18 slots per layer, the six cross entries null
+            ptrs += [ptr(lw["ln1"][0]), ptr(lw["ln1"][1]), ptr(lw["wqkv"]), ptr(lw["bqkv"]), ptr(lw["wo"]), ptr(lw["bo"]), None, None, None, None, None, None,
+                     ptr(lw["ln2"][0]), ptr(lw["ln2"][1]), ptr(lw["wfc"]), ptr(lw["bfc"]), ptr(lw["wpr"]), ptr(lw["bpr"])]
+        self._wtable = (C.c_void_p * len(ptrs))(*ptrs)
+        self._gcfg = _lib.Gpt2Config(d=d, H=c["n_head"], L=L, V=w["lm_head"].shape[0], eps=float(c.get("layer_norm_epsilon", 1e-5)))
+        self._step_ws = None
+
+    def step(self, ids_new: torch.Tensor, cache):
+        """ids_new (rows, U_new) -> fp32 logits (rows, V) of the LAST new position; appends to the KV cache.  One C call (mi_gpt2_step without cross-attention)."""
+        ids_new = ids_new.contiguous()
+        B, U = ids_new.shape
+        past, Lmax = cache["past"], cache["Lmax"]
+        self.ensure_positions(past + U)
+        L_ = _lib.lib()
+        nbytes = L_.mi_gpt2_step_workspace_bytes(C.byref(self._gcfg), B, U)
+        if self._step_ws is None or self._step_ws.numel() < nbytes:
+            self._step_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        V = self._gcfg.V
+        Vp = (V + 7) // 8 * 8
+        buf = torch.empty((B, Vp), device=self.device, dtype=torch.float32)
+        _lib.check(L_.mi_gpt2_step(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, U, past, Lmax, cache["tk"], cache["tv"], None, 0, None, 1.0,
+                                   self._step_ws.data_ptr(), self._step_ws.numel(), buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_gpt2_step")
+        cache["past"] = past + U
+        return buf[:, :V]
+
+
+def lm_engine_for(lm, device) -> GPT2LMEngine:
+    """the HIP engine of a transformers `GPT2LMHeadModel` module on `device` (its parameters are copied there by the load, as the reference's `.to(device)` does): one per
+    module, cached on it, rebuilt when a parameter was replaced, moved or written in place (keyed like whisper._decoder_engine_for)"""
+    params = list(lm.parameters())
+    key = (str(torch.device(device)), tuple((p.data_ptr(), p._version) for p in params))
+    cached = lm.__dict__.get("_hfasr_lm_engine")
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    eng = GPT2LMEngine(lm_cfg_dict(lm.config), device)
+    eng.load_state_dict(lm.state_dict())
+    lm.__dict__["_hfasr_lm_engine"] = (key, eng)
+    return eng
+
+
 def shift_tokens_right(labels: torch.Tensor, pad_id: int, start_id: int) -> torch.Tensor:
     out = labels.new_zeros(labels.shape)
     out[:, 1:] = labels[:, :-1]
@@ -299,26 +377,46 @@ def _stop_rule(num_beams, cur_len, max_length, length_penalty, early_stopping):
     return denom, heur, _ES_MODE[early_stopping]
 
 
-def _check_generate_args(joint, num_beams, max_length, early_stopping):
+def check_lm_args(lm_vocab, lm_positions, dec_vocab, max_length):
+    """what shallow fusion needs of the LM, checked on the host before anything is enqueued: the decoder's vocabulary (the two score rows are added token by token) and a
+    learned position table that reaches the last step (position max_length - 2)"""
+    if lm_vocab != dec_vocab:
+        raise ValueError(f"the language model has {lm_vocab} tokens, the decoder {dec_vocab}: shallow fusion needs one vocabulary")
+    if lm_positions < max_length - 1:
+        raise ValueError(f"decoding to max_length = {max_length} needs {max_length - 1} positions but the language model's position table (wpe) has n_positions = {lm_positions} rows")
+
+
+def _check_generate_args(joint, num_beams, max_length, early_stopping, lm=None, lm_weight=0.0):
+    """-> the LM engine to use (None when the term is off)"""
     if early_stopping not in _ES_MODE:
         raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
     if num_beams < 1 or max_length < 2:
         raise ValueError(f"num_beams >= 1 and max_length >= 2 required, got {num_beams}, {max_length}")
     joint.dec.ensure_positions(max_length - 1)           # the last step feeds position max_length - 2: a learned table too short is refused before decoding starts
+    if lm is None or not lm_weight > 0:                   # the reference appends its LM processor only for lm_weight > 0 (ctc_encoder_plus_autoregressive_decoder.py:398)
+        return None
+    if not isinstance(lm, GPT2LMEngine):
+        raise TypeError(f"lm must be a GPT2LMEngine (decoder.lm_engine_for(module, device)), got {type(lm)}")
+    check_lm_args(lm.w["lm_head"].shape[0], lm.w["pos"].shape[0], joint.dec.w["lm_head"].shape[0], max_length)
+    return lm
 
 
 def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_length=64, ctc_weight=0.3, length_penalty=1.0, early_stopping=False,
              eos_token_id=1, pad_token_id=None, start_token_id=None, space_token_id=-1, apply_eos_space_trick=False, eos_space_trick_weight=1.0,
-             run_ahead=2, stats=None, trace=None):
+             run_ahead=2, stats=None, trace=None, lm=None, lm_weight=0.0, lm_side_stream=False):
     """Device-resident decoding loop: per token the decoder step (one C call), the row log-sum-exp and ONE launch that mixes the CTC prefix scores in, takes the top 2W
     candidates, applies the beam loop's rules and moves ids / beam scores / kept hypotheses on the device (csrc/beam_step.hip).  The CTC prefix scorer of step t
     depends on the prefixes only, not on the decoder's logits: it runs on a second stream beside the decoder step.  Nothing is copied to the host until decoding ends, except
     the per-utterance `done` flags (the kernel writes them into pinned, device-mapped memory): the host stays at most `run_ahead` steps in front of the GPU and stops enqueuing once every utterance is done.
     Returns per utterance dict(tokens, score, hypotheses = the kept (score, tokens), best first, at most W).  Same hypotheses, scores and order as `generate_stepwise`
     (same arithmetic, operation for operation).  `stats` (a dict) receives the host time spent enqueuing the token loop and the number of steps enqueued; `trace` (a list)
-    receives per step the (B, 2W) candidate values and indices the kernel walked and the (B) done flags before the step (device tensors)."""
+    receives per step the (B, 2W) candidate values and indices the kernel walked and the (B) done flags before the step (device tensors).
+    Shallow fusion (`lm`: a GPT2LMEngine, `lm_weight` > 0; reference src/decoding/shallow_fussion.py): the LM is one more KV-cached token step on the same new tokens, its
+    cache follows the same `beam_idx`, and the kernel adds lm_weight * (lm logits - their row log-sum-exp) behind the CTC mix (`mi_beam_step_lm`); the candidate values of
+    `trace` include it.  The LM step reads only what the decoder step reads: `lm_side_stream` runs it on a stream of its own beside the decoder step (off by default: not
+    measured, DESIGN.md)."""
     from .decoding import CTCRescorerLogitsProcessor
-    _check_generate_args(joint, num_beams, max_length, early_stopping)
+    lm = _check_generate_args(joint, num_beams, max_length, early_stopping, lm, lm_weight)
     dev = joint.device
     c = joint.jcfg
     pad = c["pad_token_id"] if pad_token_id is None else pad_token_id
@@ -333,7 +431,8 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
         # stages in 96 KiB of LDS) the bookkeeping runs on the host as well (still the HIP kernels for everything else) — decided here, not by an error in the middle of a decode
         return generate_stepwise(joint, feats, feat_len, num_beams=num_beams, max_length=max_length, ctc_weight=ctc_weight, length_penalty=length_penalty,
                                  early_stopping=early_stopping, eos_token_id=eos_token_id, pad_token_id=pad_token_id, start_token_id=start_token_id,
-                                 space_token_id=space_token_id, apply_eos_space_trick=apply_eos_space_trick, eos_space_trick_weight=eos_space_trick_weight)
+                                 space_token_id=space_token_id, apply_eos_space_trick=apply_eos_space_trick, eos_space_trick_weight=eos_space_trick_weight,
+                                 lm=lm, lm_weight=lm_weight)
     enc_out, enc_bf, T2, key_len = joint.encode(feats, feat_len)
     B = feats.shape[0]
     d = enc_bf.shape[1]
@@ -341,6 +440,10 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
     key_rep = key_len.repeat_interleave(W) if key_len is not None else None
     kvs = joint.dec.cross_kv(enc_rep)
     cache = joint.dec.init_cache(B * W, Lmax)
+    lm_cache = lm.init_cache(B * W, Lmax) if lm is not None else None
+    lm_st = torch.cuda.Stream(device=dev) if (lm is not None and lm_side_stream) else None       # the LM step beside the decoder step (event discipline of the CTC scorer's stream)
+    w_lm = float(lm_weight)
+    lm_idx = None                              # beam_idx of the previous step: the LM's cache follows it before the LM's next step, on the stream the LM runs on
     proc, side = None, None
     if ctc_weight > 0:
         lens = enc_out["outer_len"].clamp(max=T2)
@@ -385,10 +488,32 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
                 ev_ctc = torch.cuda.Event()
                 ev_ctc.record(side)
             ctc.record_stream(main)            # allocated on the side stream, read by the main stream below: the only tensor of the loop that crosses streams
+        lm_logits = lm_lse = None
+        if lm_st is not None:                  # the LM's step of this token on its own stream (needs the new tokens and beam indices the previous step left)
+            with torch.cuda.stream(lm_st):
+                lm_st.wait_event(ev_ids)
+                if lm_idx is not None:
+                    lm.reorder_cache(lm_cache, lm_idx)
+                lm_logits = lm.step(new_tok, lm_cache)
+                lm_lse = ops.row_lse(lm_logits)
+                ev_lm = torch.cuda.Event()
+                ev_lm.record(lm_st)
+            new_tok.record_stream(lm_st)       # allocated on the main stream, read on the LM's
+            if lm_idx is not None:
+                lm_idx.record_stream(lm_st)
+            lm_logits.record_stream(main)      # allocated on the LM's stream, read by the main stream below
+            lm_lse.record_stream(main)
         logits = joint.dec.step(new_tok, cache, kvs, T2, key_rep)                       # (B*W, V), row stride padded to 8
         lse = ops.row_lse(logits)
+        if lm is not None and lm_st is None:
+            if lm_idx is not None:
+                lm.reorder_cache(lm_cache, lm_idx)
+            lm_logits = lm.step(new_tok, lm_cache)
+            lm_lse = ops.row_lse(lm_logits)
         if proc is not None:
             main.wait_event(ev_ctc)
+        if lm_st is not None:
+            main.wait_event(ev_lm)
         new_tok = torch.empty((n_bh, 1), dtype=torch.long, device=dev)
         beam_idx = torch.empty((n_bh,), dtype=torch.long, device=dev)
         top_s = top_i = None
@@ -396,15 +521,19 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
             top_s, top_i = torch.empty((B, 2 * W), device=dev), torch.empty((B, 2 * W), dtype=torch.int32, device=dev)
             trace.append((top_s, top_i, done.clone()))          # the done flags BEFORE the step
         denom, heur, es_mode = _stop_rule(W, cur_len, max_length, length_penalty, early_stopping)
-        _lib.check(L_.mi_beam_step(logits.data_ptr(), logits.stride(0), lse.data_ptr(), ctc.data_ptr() if ctc is not None else None, w_att, w_ctc, int(proc is not None), pad,
-                                   eos_token_id, B, W, V, cur_len, max_length, Lmax, denom, heur, es_mode, ids.data_ptr(), beam_scores.data_ptr(), new_tok.data_ptr(),
-                                   beam_idx.data_ptr(), done.data_ptr(), nfin.data_ptr(), fin_score.data_ptr(), fin_len.data_ptr(), fin_tok.data_ptr(),
-                                   top_s.data_ptr() if top_s is not None else None, top_i.data_ptr() if top_i is not None else None, done_host[steps].data_ptr(),
-                                   main.cuda_stream), "mi_beam_step")
+        step_args = (logits.data_ptr(), logits.stride(0), lse.data_ptr(), ctc.data_ptr() if ctc is not None else None, w_att, w_ctc, int(proc is not None), pad,
+                     eos_token_id, B, W, V, cur_len, max_length, Lmax, denom, heur, es_mode, ids.data_ptr(), beam_scores.data_ptr(), new_tok.data_ptr(),
+                     beam_idx.data_ptr(), done.data_ptr(), nfin.data_ptr(), fin_score.data_ptr(), fin_len.data_ptr(), fin_tok.data_ptr(),
+                     top_s.data_ptr() if top_s is not None else None, top_i.data_ptr() if top_i is not None else None, done_host[steps].data_ptr())
+        if lm is None:
+            _lib.check(L_.mi_beam_step(*step_args, main.cuda_stream), "mi_beam_step")
+        else:
+            _lib.check(L_.mi_beam_step_lm(*step_args, lm_logits.data_ptr(), lm_logits.stride(0), lm_lse.data_ptr(), w_lm, main.cuda_stream), "mi_beam_step_lm")
         ev_ids = torch.cuda.Event()
         ev_ids.record(main)
         if W > 1:
             joint.dec.reorder_cache(cache, beam_idx)
+            lm_idx = beam_idx
         flags.append((ev_ids, steps))          # the flags of this step are in pinned memory once the step's event has fired
         cur_len += 1
         steps += 1
@@ -413,6 +542,8 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
         stats["steps"] = steps
     if side is not None:
         main.wait_stream(side)
+    if lm_st is not None:
+        main.wait_stream(lm_st)
     nfin_c, fs_c, fl_c, ft_c = nfin.cpu(), fin_score.cpu(), fin_len.cpu(), fin_tok.cpu()             # the first copy synchronises with everything enqueued
     out = []
     for b in range(B):                         # every utterance ends with kept hypotheses: at max_length the step's first W candidates all stop
@@ -422,13 +553,15 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
 
 
 def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_length=64, ctc_weight=0.3, length_penalty=1.0, early_stopping=False,
-                      eos_token_id=1, pad_token_id=None, start_token_id=None, space_token_id=-1, apply_eos_space_trick=False, eos_space_trick_weight=1.0):
+                      eos_token_id=1, pad_token_id=None, start_token_id=None, space_token_id=-1, apply_eos_space_trick=False, eos_space_trick_weight=1.0,
+                      lm=None, lm_weight=0.0):
     """The same decoding with the beam bookkeeping on the host, one token at a time (two device -> host copies and three host -> device copies per token): the form the
     reference's generate() has, kept as the cross-check of `generate` (tests/test_gpu_config5.py, tests/test_gpu_aed.py compare the two hypothesis for hypothesis) and as
-    the route of the eos / space trick (the processor applies it, ctc_scorer.py:333-349)."""
+    the route of the eos / space trick (the processor applies it, ctc_scorer.py:333-349).  With `lm` / `lm_weight` it adds the shallow-fusion term the way the reference's
+    processor does (shallow_fussion.py:50-51), in the kernel's arithmetic: one fp32 subtract, one multiply, one add."""
     import numpy as np
     from .decoding import CTCRescorerLogitsProcessor
-    _check_generate_args(joint, num_beams, max_length, early_stopping)
+    lm = _check_generate_args(joint, num_beams, max_length, early_stopping, lm, lm_weight)
     dev = joint.device
     c = joint.jcfg
     pad = c["pad_token_id"] if pad_token_id is None else pad_token_id
@@ -442,6 +575,7 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
     key_rep = key_len.repeat_interleave(W) if key_len is not None else None
     kvs = joint.dec.cross_kv(enc_rep)
     cache = joint.dec.init_cache(B * W, max_length + 1)
+    lm_cache = lm.init_cache(B * W, max_length + 1) if lm is not None else None
     proc = None
     if ctc_weight > 0:
         lens = enc_out["outer_len"].clamp(max=T2)
@@ -460,6 +594,10 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
         scores = logits - ops.row_lse(logits.contiguous())[:, None]                      # log_softmax
         if proc is not None:
             scores = proc(ids, scores.clone())
+        if lm is not None:                                                               # LMRescorerLogitsProcessor: scores + lm_weight * log_softmax(lm logits)
+            lm_logits = lm.step(new_tok, lm_cache)
+            lm_scores = lm_logits - ops.row_lse(lm_logits.contiguous())[:, None]
+            scores = scores + float(lm_weight) * lm_scores
         cand = (scores + beam_scores[:, None]).view(B, W * V)
         top_s, top_i = cand.topk(2 * W, dim=1)
         top_s, top_i = top_s.cpu().numpy(), top_i.cpu().numpy()
@@ -498,4 +636,6 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
         beam_scores = nb_scores.view(-1).to(dev)
         ids = torch.cat([ids.index_select(0, beam_idx), new_tok], 1)
         joint.dec.reorder_cache(cache, beam_idx)
+        if lm is not None:
+            lm.reorder_cache(lm_cache, beam_idx)
     return [dict(tokens=kept[b][0][1], score=float(kept[b][0][0]), hypotheses=[(float(s), t) for s, t in kept[b]]) for b in range(B)]

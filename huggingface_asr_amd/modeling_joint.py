@@ -18,7 +18,7 @@ from transformers.modeling_outputs import Seq2SeqLMOutput
 from transformers.models.speech_encoder_decoder.configuration_speech_encoder_decoder import SpeechEncoderDecoderConfig
 
 from .configuration_ebranchformer import Wav2Vec2EBranchformerConfig
-from .decoder import JointAEDEngine, generate as _generate
+from .decoder import GPT2LMEngine, JointAEDEngine, check_lm_args, generate as _generate, lm_cfg_dict, lm_engine_for
 from .engine import cfg_from_hf
 from .modeling_ebranchformer import _dropout_seed, Wav2Vec2EBranchformerForCTC, _Holder
 
@@ -349,9 +349,25 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
                        "bad_words_ids": (None,), "force_words_ids": (None,), "constraints": (None,), "forced_bos_token_id": (None,), "forced_eos_token_id": (None,),
                        "remove_invalid_values": (None, False), "exponential_decay_length_penalty": (None,), "suppress_tokens": (None,), "begin_suppress_tokens": (None,),
                        "sequence_bias": (None,), "guidance_scale": (None, 1.0), "renormalize_logits": (None, False), "diversity_penalty": (None, 0.0),
-                       "lm_weight": (None, 0, 0.0), "output_logits": (None, False), "low_memory": (None, False), "token_healing": (None, False),
+                       "output_logits": (None, False), "low_memory": (None, False), "token_healing": (None, False),
                        "max_time": (None,), "stop_strings": (None,), "prompt_lookup_num_tokens": (None,), "watermarking_config": (None,)}
     _MODEL_KWARGS = ("attention_mask", "labels", "use_cache", "output_attentions", "output_hidden_states", "return_dict")
+
+    def _check_lm(self, lm_model, max_length):
+        """shallow fusion's language model, checked on the host before the device is touched: transformers' GPT2LMHeadModel in eval mode with a configuration the HIP
+        token step implements, the decoder's vocabulary, positions for the whole decode"""
+        from transformers import GPT2LMHeadModel
+        if lm_model is None:
+            raise NotImplementedError("JointCTCAttentionEncoderDecoder.generate (HIP): generation option `lm_weight` > 0 needs `lm_model` (a transformers GPT2LMHeadModel, "
+                                      "as src/trainers/train_clm.py trains) in the generation configuration or as a keyword argument")
+        if not isinstance(lm_model, GPT2LMHeadModel):
+            raise NotImplementedError(f"JointCTCAttentionEncoderDecoder.generate (HIP): shallow fusion runs transformers' GPT2LMHeadModel on the HIP token step; "
+                                      f"`lm_model` is a {type(lm_model).__name__} (no PyTorch fallback)")
+        if lm_model.training:
+            raise NotImplementedError(f"JointCTCAttentionEncoderDecoder.generate (HIP): `lm_model` ({type(lm_model).__name__}) is in training mode; the HIP step has no "
+                                      f"dropout — call .eval()")
+        GPT2LMEngine(lm_cfg_dict(lm_model.config), "cpu")             # the constructor refuses what the step does not implement (no device call)
+        check_lm_args(int(lm_model.config.vocab_size), int(lm_model.config.n_positions), int(self.config.decoder.vocab_size), max_length)
 
     @torch.no_grad()
     def generate(self, inputs=None, generation_config=None, logits_processor=None, stopping_criteria=None, prefix_allowed_tokens_fn=None, synced_gpus=None,
@@ -364,6 +380,8 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
         `return_dict_in_generate` — `GenerateBeamEncoderDecoderOutput(sequences, sequences_scores)` (beam search; best first per utterance) /
         `GenerateEncoderDecoderOutput(sequences)` (greedy: no sequence scores, as in transformers).  Per-step `scores` are not collected (None).
         As in the reference, the CTC processor's parameters come from the MODEL's `generation_config` (:385-396) while the passed configuration only gates it (:382).
+        Shallow fusion (:398-403): `lm_weight` > 0 in the PASSED configuration (or as a keyword argument) adds `lm_weight * log_softmax(lm_model logits)` behind the CTC mix;
+        `lm_model` is a transformers `GPT2LMHeadModel` in eval mode, run as a KV-cached HIP token step beside the decoder's (decoder.GPT2LMEngine).
         Every other option that would change the decoding raises instead of being ignored."""
         import copy
 
@@ -374,7 +392,19 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
                 raise NotImplementedError(f"JointCTCAttentionEncoderDecoder.generate (HIP): `{name}` is not supported")
         if synced_gpus:
             raise NotImplementedError("JointCTCAttentionEncoderDecoder.generate (HIP): synced_gpus=True is not supported (every rank decodes its own batch to the end)")
-        g = copy.deepcopy(generation_config if generation_config is not None else self.generation_config)
+        src = generation_config if generation_config is not None else self.generation_config
+        had_lm = "lm_model" in src.__dict__               # the language model stays ONE object: a deep copy per call would clone it and its engine cache would never hit
+        lm_model = src.__dict__.get("lm_model")
+        if had_lm:
+            src.__dict__["lm_model"] = None
+        try:
+            g = copy.deepcopy(src)
+        finally:
+            if had_lm:
+                src.__dict__["lm_model"] = lm_model
+        g.lm_model = lm_model
+        if not hasattr(g, "lm_weight"):
+            g.lm_weight = None
         model_kwargs = {}
         for k, v in kwargs.items():                       # transformers: generation attributes passed as keyword arguments override the configuration, the rest is for the model
             if hasattr(g, k):
@@ -392,7 +422,8 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
             if v not in off:
                 raise NotImplementedError(f"JointCTCAttentionEncoderDecoder.generate (HIP): generation option `{name}={v!r}` is not implemented "
                                           f"(implemented: num_beams, max_length / max_new_tokens, length_penalty, early_stopping, num_return_sequences, ctc_weight, "
-                                          f"ctc_margin, space_token_id, apply_eos_space_trick, eos_space_trick_weight, return_dict_in_generate, output_scores)")
+                                          f"ctc_margin, space_token_id, apply_eos_space_trick, eos_space_trick_weight, lm_weight, lm_model, return_dict_in_generate, "
+                                          f"output_scores)")
         inputs = self._pick_inputs(inputs, input_values, input_features)
         attention_mask = model_kwargs.get("attention_mask")
         W = int(getattr(g, "num_beams", None) or 1)
@@ -422,6 +453,12 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
         pad = self.config.pad_token_id if pad is None else int(pad)
         start = getattr(g, "decoder_start_token_id", None)
         start = self.config.decoder_start_token_id if start is None else int(start)
+        lm_w = getattr(g, "lm_weight", None)
+        lm_w = 0.0 if lm_w is None else float(lm_w)
+        lm_model = None
+        if lm_w > 0:                                      # reference :398-403: the PASSED configuration gates the LM processor and supplies model and weight
+            lm_model = getattr(g, "lm_model", None)
+            self._check_lm(lm_model, max_length)
         ctc = dict(ctc_weight=0.0, space_token_id=-1, apply_eos_space_trick=False, eos_space_trick_weight=1.0)
         if getattr(g, "ctc_weight", None) is not None and g.ctc_weight > 0:            # reference :382 gates on the PASSED configuration ...
             mg = self.generation_config                                                # ... and reads the processor's parameters from the MODEL's (:385-396)
@@ -440,8 +477,9 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
             raise RuntimeError("JointCTCAttentionEncoderDecoder (HIP): inputs must be on the GPU; there is no CPU fallback")
         eng = self._get_engine(inputs.device)
         fl = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        lm = lm_engine_for(lm_model, inputs.device) if lm_model is not None else None
         hyps = _generate(eng, inputs, fl, num_beams=W, max_length=max_length, length_penalty=lp, early_stopping=es, eos_token_id=eos, pad_token_id=pad,
-                         start_token_id=start, **ctc)
+                         start_token_id=start, lm=lm, lm_weight=lm_w, **ctc)
         rows = [h["hypotheses"][k] for h in hyps for k in range(nret)]
         L = max(len(t) for _, t in rows)                  # (greedy: transformers runs every row until all have stopped and closed rows take pad tokens — the same layout)
         seq = torch.full((len(rows), L), pad, dtype=torch.long)

@@ -252,6 +252,48 @@ def _dec_map(c: dict, with_proj: bool, prefix="decoder."):
     return m
 
 
+# ====================================================================================================== GPT-2 language model parameters (shallow fusion)
+def lm_specs(c: dict) -> list[Spec]:
+    """transformers' `GPT2LMHeadModel` without cross-attention — the external language model of shallow fusion (reference src/decoding/shallow_fussion.py; trained by
+    src/trainers/train_clm.py) — in the names of `decoder_specs`: the same block minus its six cross parameters, learned positions, a tied or separate head."""
+    d, L, V = c["n_embd"], c["n_layer"], c["vocab_size"]
+    S = []
+    mat = lambda n, *sh: S.append(Spec(n, tuple(sh), True, True))
+    vec = lambda n, *sh, decay=False: S.append(Spec(n, tuple(sh), False, decay))
+    mat("wte", V, d)
+    vec("wpe", c.get("n_positions", 1024), d, decay=True)
+    for l in range(L):
+        p = f"h{l}."
+        vec(p + "ln1_g", d); vec(p + "ln1_b", d); mat(p + "wqkv", 3 * d, d); vec(p + "bqkv", 3 * d); mat(p + "wo", d, d); vec(p + "bo", d)
+        vec(p + "ln2_g", d); vec(p + "ln2_b", d); mat(p + "wfc", 4 * d, d); vec(p + "bfc", 4 * d); mat(p + "wpr", d, 4 * d); vec(p + "bpr", d)
+    vec("lnf_g", d); vec("lnf_b", d)
+    if not c.get("tie_word_embeddings", True):
+        mat("lm_head", V, d)
+    return S
+
+
+def _lm_map(c: dict, prefix: str = ""):
+    """packed name -> Ref for transformers' `GPT2LMHeadModel` state-dict names (Conv1D weights (in, out) transposed, as `_dec_map` does)"""
+    m = {}
+    one = partial(_one, m)
+    tr_in = lambda t: t.t().contiguous()
+    tr = lambda t: t.t()
+    t = prefix + "transformer."
+    one("wte", t + "wte.weight"); one("wpe", t + "wpe.weight")
+    for l in range(c["n_layer"]):
+        p, r = f"h{l}.", f"{t}h.{l}."
+        one(p + "ln1_g", r + "ln_1.weight"); one(p + "ln1_b", r + "ln_1.bias")
+        one(p + "wqkv", r + "attn.c_attn.weight", tr_in, tr); one(p + "bqkv", r + "attn.c_attn.bias")
+        one(p + "wo", r + "attn.c_proj.weight", tr_in, tr); one(p + "bo", r + "attn.c_proj.bias")
+        one(p + "ln2_g", r + "ln_2.weight"); one(p + "ln2_b", r + "ln_2.bias")
+        one(p + "wfc", r + "mlp.c_fc.weight", tr_in, tr); one(p + "bfc", r + "mlp.c_fc.bias")
+        one(p + "wpr", r + "mlp.c_proj.weight", tr_in, tr); one(p + "bpr", r + "mlp.c_proj.bias")
+    one("lnf_g", t + "ln_f.weight"); one("lnf_b", t + "ln_f.bias")
+    if not c.get("tie_word_embeddings", True):
+        one("lm_head", prefix + "lm_head.weight")
+    return m
+
+
 # ====================================================================================================== Whisper decoder parameters
 def _whisper_as_gpt2(c: dict) -> dict:
     """a transformers `WhisperConfig`'s decoder fields in the keys `decoder_specs` reads: learned positions, the token embedding tied as the head"""

@@ -529,7 +529,11 @@ int mi_mask_noise_f32(float* x, long ld, const unsigned char* time_mask, int M, 
                       mi_stream_t stream);
 
 /* ---- GPT-2 decoder token step as one call (KV cache, cross-attention over cached encoder K/V) + beam re-ordering of the caches.
- * replaces: GPT2LMMultiHeadModel.forward with past_key_values (multi_head_gpt2.py:80-170; tf gpt2 :262-310) and `_reorder_cache`. */
+ * replaces: GPT2LMMultiHeadModel.forward with past_key_values (multi_head_gpt2.py:80-170; tf gpt2 :262-310) and `_reorder_cache`.
+ * cross_kv == NULL: the block without cross-attention (ln_1, causal self-attention over the cache, ln_2, MLP) — transformers' GPT2LMHeadModel with a cache, the
+ * external language model of shallow fusion (src/decoding/shallow_fussion.py re-runs it over the whole prefix per token).  The weight table keeps 5 + 18 L entries,
+ * the six cross entries of a layer (lnc_g/b, wq, bq, wco, bco) are not read and may be NULL; T_enc and enc_len are ignored.  Every step form applies: the fused form
+ * then takes two launches per layer instead of three. */
 typedef struct {
     int d, H, L, V;
     float eps;
@@ -575,6 +579,15 @@ int mi_kv_cache_reorder(const void* const* src_k, const void* const* src_v, void
 int mi_beam_step(const float* logits, long ldl, const float* lse, const float* ctc, float w_att, float w_ctc, int mask_pad, int pad, int eos, int B, int W, int V,
                  int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok, long* beam_idx,
                  int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out, mi_stream_t stream);
+/* mi_beam_step with the shallow-fusion term of an external language model (src/decoding/shallow_fussion.py:41-53, appended behind the CTC processor,
+   ctc_encoder_plus_autoregressive_decoder.py:398-403): lm_logits (B*W, ld_lm) fp32 logits of the LM for the same prefixes, lm_lse (B*W) their row log-sum-exp, w_lm the weight.
+   One rounding per operation, in the reference's order:
+       s = logit - lse;  pad -> logzero when mask_pad;  [ctc: s = w_att s + w_ctc ctc];  l = lm_logit - lm_lse;  m = w_lm l;  s = s + m;  cand = s + beam_score
+   lm_logits == NULL: no term (lm_lse, w_lm ignored) — exactly mi_beam_step, which is this call with the LM off.  Same limits. */
+int mi_beam_step_lm(const float* logits, long ldl, const float* lse, const float* ctc, float w_att, float w_ctc, int mask_pad, int pad, int eos, int B, int W, int V,
+                    int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok, long* beam_idx,
+                    int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out,
+                    const float* lm_logits, long ld_lm, const float* lm_lse, float w_lm, mi_stream_t stream);
 
 /* ---- Whisper-style front end + glue (BASELINE config 4).  replaces: transformers WhisperFeatureExtractor numpy path
  *      (selected by configs/default_data_preprocessing_whisper.json:20-29) and the conv/position prologue of WhisperEncoder. */
