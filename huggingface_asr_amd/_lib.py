@@ -173,6 +173,7 @@ SIGNATURES = {
     "mi_gpt2_step_workspace_bytes": [C.POINTER(Gpt2Config), i32, i32],
     "mi_gpt2_step": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, sz, vp, i64, vp],
     "mi_decoder_step": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
+    "mi_decoder_step_beams": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
     "mi_linear_rows_workspace_bytes": [i32, i32, i32],
     "mi_linear_rows": [vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp],
     "mi_greedy_advance": [vp, vp, i64, i32, i64, i64, vp, vp, vp, i32, vp],
@@ -182,6 +183,8 @@ SIGNATURES = {
     "mi_beam_step": [vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi_beam_step_lm": [vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                         vp, i64, vp, f32, vp],
+    "mi_beam_step_wide": [vp, i64, vp, vp, f32, f32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                          vp, i64, vp, f32, vp],
     "mi_ebf_workspace_bytes": [C.POINTER(EbfConfig)],
     "mi_ebf_forward": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp],
     "mi_ebf_forward_hs": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp],

@@ -323,14 +323,20 @@ extern "C" size_t mi_gpt2_step_workspace_bytes(const mi_gpt2_config* cfg, int B,
 // cfg->act selects the MLP activation (0 gelu_new, 1 erf-GELU: the Whisper decoder block, which is this block with separate q / k / v matrices packed into wqkv).
 // cross_kv == NULL: the plain causal GPT-2 block (transformers GPT2LMHeadModel without add_cross_attention: the language model of shallow fusion) — ln_1, self-attention
 // over the cache, ln_2, MLP; the four cross ops are skipped in every form, the table keeps its 18 slots per layer (the six cross entries unread), T_enc / enc_len ignored.
-extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
-                               void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
-                               float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
+// beams > 1 (mi_decoder_step_beams): the B rows are B / beams utterances x `beams` hypotheses, utterance-major, and the hypotheses of an utterance share its encoder frames:
+// cross_kv is (B / beams * T_enc, 2d) per layer and enc_len (B / beams).  One new token per row; the step runs one launch per op whatever the row count (the fused, GEMV
+// and streaming forms index the cross tables by row), and its cross-attention is the teacher-forced forward's call: B / beams batches of `beams` queries, so an utterance's
+// K / V tiles are fetched once for all its hypotheses instead of once per hypothesis.  Everything else — self-attention over the per-row cache included — is per row.
+extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                                     void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                                     float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
     MI_ENTER();
     const mi_gpt2_config& c = *cfg;
     if (c.act < 0 || c.act > 1 || c.step_form < 0 || c.step_form > 2) return MI_ERR_ARG;
     const int mlp_act = c.act == 1 ? 1 : 2;                           // mi_gemm_bf16 / linear_rows activation codes
     if (B <= 0 || U <= 0 || past < 0 || past + U > Lmax || c.L <= 0 || c.L > MAX_LAYERS || c.d % c.H || (c.d % 8)) return MI_ERR_ARG;
+    if (beams < 1 || (beams > 1 && (B % beams || U != 1 || !cross_kv))) return MI_ERR_ARG;
+    const bool shared = beams > 1;
     const int hd = c.d / c.H;
     if (hd != 64 && hd != 128) return MI_ERR_UNSUPPORTED;
     const int M = B * U, d = c.d;
@@ -343,7 +349,7 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
     auto ln = [&](const float* x, long ldx, const float* g, const float* b, bf16_t* out, int rows) {
         return mi_layernorm_chain(x, ldx, nullptr, 1, nullptr, nullptr, 0.f, nullptr, 0, g, b, c.eps, out, d, nullptr, 0, nullptr, nullptr, nullptr, 0, rows, d, st);
     };
-    if (c.step_form == 0 && c.act == 0 && w.fws) {
+    if (!shared && c.step_form == 0 && c.act == 0 && w.fws) {
         // ---- fused token step (decoder_fused.hip): three launches per layer (two without cross-attention), every cross-workgroup reduction folded into the next launch's
         // prologue (the embedding too)
         RUN(gpt2_step_fused(c, weights, ids_new, emb_scale, M, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, w.fws, w.hid, st));
@@ -354,7 +360,7 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         return MI_OK;
     }
     RUN(mi_embed_tokens(ids_new, Gf(0), emb_scale, Gf(1), past, U, d, M, c.V, w.x, st));
-    if (step_streams(c, M, U)) {
+    if (!shared && step_streams(c, M, U)) {
         // ---- streaming token step (linear_rows.hip): up to 64 rows, one new token each; every linear reads its weights once, spread over the chip by N and K
         auto lin = [&](const bf16_t* in, int K, const void* W, const float* bias, int N, int act, float* o32, long ldo32, int accumulate, bf16_t* o16, bf16_t* kc, bf16_t* vc) {
             return linear_rows(in, K, (const bf16_t*)W, K, bias, act, o32, ldo32, accumulate, o16, N, kc, vc, 1, past, Lmax, d, M, N, K, w.part, w.part_floats, st);
@@ -382,7 +388,7 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         MI_CHECK_LAUNCH();
         return MI_OK;
     }
-    if (c.act == 0 && M <= SK_MAXM && (d % 8) == 0 && 4 * d <= 2048) {
+    if (!shared && c.act == 0 && M <= SK_MAXM && (d % 8) == 0 && 4 * d <= 2048) {
         // ---- skinny token step: LayerNorms, biases, activations and residual adds fused into GEMV-style linears (8 launches per layer)
         auto lin_ln = [&](const float* g, const float* b, const void* W, const float* bias, int N, bf16_t* out, int act) {
             SkArgs a{}; a.x32 = w.x; a.ldx = d; a.ln_g = g; a.ln_b = b; a.eps = c.eps; a.W = (const bf16_t*)W; a.ldw = d; a.bias = bias;
@@ -437,7 +443,8 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
         if (ckv) {
             RUN(ln(w.x, d, Lf(l, 6), Lf(l, 7), w.a, M));
             RUN(mi_gemm_bf16(w.a, d, Lw(l, 8), d, Lf(l, 9), 1, w.qq, d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
-            RUN(mi_attention_qkv_bf16(w.qq, d, ckv, 2 * d, ckv + d, 2 * d, nullptr, 0, nullptr, nullptr, enc_len, w.ctx, d, B, U, T_enc, 0, c.H, hd, scale, 0, st));
+            RUN(mi_attention_qkv_bf16(w.qq, d, ckv, 2 * d, ckv + d, 2 * d, nullptr, 0, nullptr, nullptr, enc_len, w.ctx, d, B / beams, U * beams, T_enc, 0, c.H, hd, scale, 0,
+                                      st));           // (beams = 1: B batches of U queries, as ever)
             RUN(mi_gemm_bf16(w.ctx, d, Lw(l, 10), d, Lf(l, 11), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, d, 0, 0, st));
         }
         RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
@@ -449,6 +456,13 @@ extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* wei
     RUN(mi_gemm_bf16(w.hid, d, weights[4], d, head_bias, head_bias ? 1 : 0, logits, ld_logits, 1, nullptr, 0, 1.f, 0, B, c.V, d, 0, 0, st));
     MI_CHECK_LAUNCH();
     return MI_OK;
+}
+
+extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
+                               void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                               float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
+    return mi_decoder_step_beams(cfg, weights, ids_new, B, 1, U, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, emb_scale, head_bias, workspace, workspace_bytes, logits,
+                                 ld_logits, st);
 }
 
 // the GPT-2 entry: the same step without a head bias

@@ -179,8 +179,10 @@ class GPT2DecoderEngine:
         cache["tk"], cache["tk2"] = cache["tk2"], cache["tk"]
         cache["tv"], cache["tv2"] = cache["tv2"], cache["tv"]
 
-    def step(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, enc_len):
-        """ids_new (B, U_new) -> logits (B, V) of the LAST new position; appends to the KV cache.  One C call (mi_gpt2_step)."""
+    def step(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, enc_len, beams: int = 1):
+        """ids_new (B, U_new) -> logits (B, V) of the LAST new position; appends to the KV cache.  One C call (mi_gpt2_step).
+        `beams` > 1: the B rows are B / beams utterances x `beams` hypotheses that share their utterance's encoder frames — `kvs` are (B / beams * T_enc, 2d) and
+        `enc_len` (B / beams) (mi_decoder_step_beams; one new token per row)."""
         c, w = self.cfg, self.w
         ids_new = ids_new.contiguous()
         B, U = ids_new.shape
@@ -196,6 +198,14 @@ class GPT2DecoderEngine:
         V = self._gcfg.V
         Vp = (V + 7) // 8 * 8
         buf = torch.empty((B, Vp), device=self.device, dtype=torch.float32)
+        if beams != 1:
+            if beams < 1 or B % beams or U != 1 or kvs[0].shape[0] != B // beams * T_enc or (enc_len is not None and enc_len.numel() != B // beams):
+                raise ValueError(f"step(beams={beams}): {B} rows of {U} new tokens over cross tables of {kvs[0].shape[0]} rows (T_enc = {T_enc})")
+            _lib.check(L_.mi_decoder_step_beams(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, beams, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc,
+                                                enc_len.data_ptr() if enc_len is not None else None, float(w["scale"]), None, self._step_ws.data_ptr(),
+                                                self._step_ws.numel(), buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_decoder_step_beams")
+            cache["past"] = past + U
+            return buf[:, :V]
         _lib.check(L_.mi_gpt2_step(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc,
                                    enc_len.data_ptr() if enc_len is not None else None, float(w["scale"]), self._step_ws.data_ptr(), self._step_ws.numel(),
                                    buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_gpt2_step")
@@ -401,9 +411,48 @@ def _check_generate_args(joint, num_beams, max_length, early_stopping, lm=None, 
     return lm
 
 
+BEAM_STEP_MAXW, BEAM_STEP_LDS, BEAM_WIDE_MAXW, BEAM_MAX_CANDIDATES = 16, 96 * 1024, 64, 1 << 24        # csrc/beam_step.hip (BS_MAXW, its id buffers in LDS), csrc/beam_step_wide.hip
+SKINNY_MAX_ROWS = 8                        # csrc/decoder_step.hip SK_MAXM: up to here the token step is the fused / GEMV form, which indexes the cross tables by row
+
+
+def beam_loop_route(W: int, V: int, max_length: int, eos_space_trick: bool = False) -> str:
+    """Which loop serves a decoding request: "device" (`generate` with mi_beam_step / mi_beam_step_lm: W <= 16 and the utterance's two id buffers within 96 KiB of LDS),
+    "device_wide" (`generate` with mi_beam_step_wide: W <= 64, any max_length) or "host" (`generate_stepwise`: the eos / space trick, which lives in the processor the host
+    loop calls; more than 64 beams; W * V >= 2^24 candidates, whose indices the kernels keep in 24 bits)."""
+    if eos_space_trick or W > BEAM_WIDE_MAXW or W * V >= BEAM_MAX_CANDIDATES:
+        return "host"
+    if W <= BEAM_STEP_MAXW and W * (max_length + max_length + 1) * 8 <= BEAM_STEP_LDS:
+        return "device"
+    return "device_wide"
+
+
+def cross_kv_layout(B: int, W: int, T_enc: int, d: int, n_layer: int, share=None) -> dict:
+    """How the W hypotheses of each of B utterances see their encoder K/V in the token step: `beams` = 1 — every row has its own copy of its utterance's tables (B * W
+    * T_enc rows per layer) — or `beams` = W — one table per utterance (B * T_enc rows), shared (`GPT2DecoderEngine.step(beams=W)`).  Shared when the step has more than 8
+    rows, the rule by which it leaves its fused / GEMV forms (which index the tables by row; config 5 keeps its kernels and its bits); `share` = True / False overrides.
+    `bytes`: bf16 K and V of all layers."""
+    if share is None:
+        share = B * W > SKINNY_MAX_ROWS
+    share = bool(share) and W > 1
+    kv_rows = (B if share else B * W) * T_enc
+    return dict(beams=W if share else 1, kv_rows=kv_rows, bytes=kv_rows * 2 * d * 2 * n_layer)
+
+
+def _beam_cross_kv(joint, enc_bf, key_len, B, W, T2, share=None):
+    """-> (per-layer cross K/V, key lengths, `beams` of the token step) for B utterances x W hypotheses: the arrangement `generate` and `generate_stepwise` both decode on
+    (the same step on the same tables: that is what keeps the two loops bit-identical to each other)"""
+    d = enc_bf.shape[1]
+    lay = cross_kv_layout(B, W, T2, joint.dec.cfg["n_embd"], joint.dec.cfg["n_layer"], share)
+    if lay["beams"] > 1:
+        return joint.dec.cross_kv(enc_bf), key_len, lay["beams"]
+    enc_rep = enc_bf.view(B, T2, d).repeat_interleave(W, 0).reshape(B * W * T2, d)          # every beam attends to its utterance's encoder frames
+    key_rep = key_len.repeat_interleave(W) if key_len is not None else None
+    return joint.dec.cross_kv(enc_rep), key_rep, 1
+
+
 def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_length=64, ctc_weight=0.3, length_penalty=1.0, early_stopping=False,
              eos_token_id=1, pad_token_id=None, start_token_id=None, space_token_id=-1, apply_eos_space_trick=False, eos_space_trick_weight=1.0,
-             run_ahead=2, stats=None, trace=None, lm=None, lm_weight=0.0, lm_side_stream=False):
+             run_ahead=2, stats=None, trace=None, lm=None, lm_weight=0.0, lm_side_stream=False, share_cross_kv=None):
     """Device-resident decoding loop: per token the decoder step (one C call), the row log-sum-exp and ONE launch that mixes the CTC prefix scores in, takes the top 2W
     candidates, applies the beam loop's rules and moves ids / beam scores / kept hypotheses on the device (csrc/beam_step.hip).  The CTC prefix scorer of step t
     depends on the prefixes only, not on the decoder's logits: it runs on a second stream beside the decoder step.  Nothing is copied to the host until decoding ends, except
@@ -414,7 +463,9 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
     Shallow fusion (`lm`: a GPT2LMEngine, `lm_weight` > 0; reference src/decoding/shallow_fussion.py): the LM is one more KV-cached token step on the same new tokens, its
     cache follows the same `beam_idx`, and the kernel adds lm_weight * (lm logits - their row log-sum-exp) behind the CTC mix (`mi_beam_step_lm`); the candidate values of
     `trace` include it.  The LM step reads only what the decoder step reads: `lm_side_stream` runs it on a stream of its own beside the decoder step (off by default: not
-    measured, DESIGN.md)."""
+    measured, DESIGN.md).
+    `beam_loop_route` picks the step kernel (mi_beam_step / mi_beam_step_lm within their limits, mi_beam_step_wide up to 64 beams and any max_length) or hands the request
+    to `generate_stepwise`; `cross_kv_layout` decides whether the hypotheses share their utterance's cross K/V (`share_cross_kv` = True / False overrides its rule)."""
     from .decoding import CTCRescorerLogitsProcessor
     lm = _check_generate_args(joint, num_beams, max_length, early_stopping, lm, lm_weight)
     dev = joint.device
@@ -426,19 +477,17 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
     main = torch.cuda.current_stream()
     V = joint.dec.w["lm_head"].shape[0]
     Lmax = max_length + 1
-    if apply_eos_space_trick or W > 16 or W * V >= (1 << 24) or W * (max_length + Lmax) * 8 > 96 * 1024:
-        # the eos / space trick (ctc_scorer.py:333-349) lives in the processor the host loop calls; beyond mi_beam_step's limits (beams, candidates, the two id buffers it
-        # stages in 96 KiB of LDS) the bookkeeping runs on the host as well (still the HIP kernels for everything else) — decided here, not by an error in the middle of a decode
+    route = beam_loop_route(W, V, max_length, bool(apply_eos_space_trick))
+    if route == "host":
+        # the eos / space trick (ctc_scorer.py:333-349) lives in the processor the host loop calls; beyond the step kernels' limits (beams, candidates) the bookkeeping
+        # runs on the host as well (still the HIP kernels for everything else) — decided here, not by an error in the middle of a decode
         return generate_stepwise(joint, feats, feat_len, num_beams=num_beams, max_length=max_length, ctc_weight=ctc_weight, length_penalty=length_penalty,
                                  early_stopping=early_stopping, eos_token_id=eos_token_id, pad_token_id=pad_token_id, start_token_id=start_token_id,
                                  space_token_id=space_token_id, apply_eos_space_trick=apply_eos_space_trick, eos_space_trick_weight=eos_space_trick_weight,
-                                 lm=lm, lm_weight=lm_weight)
+                                 lm=lm, lm_weight=lm_weight, share_cross_kv=share_cross_kv)
     enc_out, enc_bf, T2, key_len = joint.encode(feats, feat_len)
     B = feats.shape[0]
-    d = enc_bf.shape[1]
-    enc_rep = enc_bf.view(B, T2, d).repeat_interleave(W, 0).reshape(B * W * T2, d)
-    key_rep = key_len.repeat_interleave(W) if key_len is not None else None
-    kvs = joint.dec.cross_kv(enc_rep)
+    kvs, key_rep, kv_beams = _beam_cross_kv(joint, enc_bf, key_len, B, W, T2, share_cross_kv)
     cache = joint.dec.init_cache(B * W, Lmax)
     lm_cache = lm.init_cache(B * W, Lmax) if lm is not None else None
     lm_st = torch.cuda.Stream(device=dev) if (lm is not None and lm_side_stream) else None       # the LM step beside the decoder step (event discipline of the CTC scorer's stream)
@@ -503,7 +552,7 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
                 lm_idx.record_stream(lm_st)
             lm_logits.record_stream(main)      # allocated on the LM's stream, read by the main stream below
             lm_lse.record_stream(main)
-        logits = joint.dec.step(new_tok, cache, kvs, T2, key_rep)                       # (B*W, V), row stride padded to 8
+        logits = joint.dec.step(new_tok, cache, kvs, T2, key_rep, beams=kv_beams)       # (B*W, V), row stride padded to 8
         lse = ops.row_lse(logits)
         if lm is not None and lm_st is None:
             if lm_idx is not None:
@@ -525,7 +574,10 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
                      eos_token_id, B, W, V, cur_len, max_length, Lmax, denom, heur, es_mode, ids.data_ptr(), beam_scores.data_ptr(), new_tok.data_ptr(),
                      beam_idx.data_ptr(), done.data_ptr(), nfin.data_ptr(), fin_score.data_ptr(), fin_len.data_ptr(), fin_tok.data_ptr(),
                      top_s.data_ptr() if top_s is not None else None, top_i.data_ptr() if top_i is not None else None, done_host[steps].data_ptr())
-        if lm is None:
+        if route == "device_wide":
+            lm_args = (lm_logits.data_ptr(), lm_logits.stride(0), lm_lse.data_ptr(), w_lm) if lm is not None else (None, 0, None, 0.0)
+            _lib.check(L_.mi_beam_step_wide(*step_args, *lm_args, main.cuda_stream), "mi_beam_step_wide")
+        elif lm is None:
             _lib.check(L_.mi_beam_step(*step_args, main.cuda_stream), "mi_beam_step")
         else:
             _lib.check(L_.mi_beam_step_lm(*step_args, lm_logits.data_ptr(), lm_logits.stride(0), lm_lse.data_ptr(), w_lm, main.cuda_stream), "mi_beam_step_lm")
@@ -540,6 +592,8 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
     if stats is not None:                      # host time spent enqueuing the token loop (the GPU may still be running it)
         stats["host_loop_ms"] = (time.perf_counter() - t_loop) * 1e3
         stats["steps"] = steps
+        stats["route"] = route
+        stats["kv_beams"] = kv_beams
     if side is not None:
         main.wait_stream(side)
     if lm_st is not None:
@@ -554,7 +608,7 @@ def generate(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_lengt
 
 def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, max_length=64, ctc_weight=0.3, length_penalty=1.0, early_stopping=False,
                       eos_token_id=1, pad_token_id=None, start_token_id=None, space_token_id=-1, apply_eos_space_trick=False, eos_space_trick_weight=1.0,
-                      lm=None, lm_weight=0.0):
+                      lm=None, lm_weight=0.0, share_cross_kv=None):
     """The same decoding with the beam bookkeeping on the host, one token at a time (two device -> host copies and three host -> device copies per token): the form the
     reference's generate() has, kept as the cross-check of `generate` (tests/test_gpu_config5.py, tests/test_gpu_aed.py compare the two hypothesis for hypothesis) and as
     the route of the eos / space trick (the processor applies it, ctc_scorer.py:333-349).  With `lm` / `lm_weight` it adds the shallow-fusion term the way the reference's
@@ -569,11 +623,7 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
     W = num_beams
     enc_out, enc_bf, T2, key_len = joint.encode(feats, feat_len)
     B = feats.shape[0]
-    d = enc_bf.shape[1]
-    # every beam attends to its utterance's encoder frames
-    enc_rep = enc_bf.view(B, T2, d).repeat_interleave(W, 0).reshape(B * W * T2, d)
-    key_rep = key_len.repeat_interleave(W) if key_len is not None else None
-    kvs = joint.dec.cross_kv(enc_rep)
+    kvs, key_rep, kv_beams = _beam_cross_kv(joint, enc_bf, key_len, B, W, T2, share_cross_kv)          # `generate`'s arrangement (share_cross_kv=False: one copy per beam)
     cache = joint.dec.init_cache(B * W, max_length + 1)
     lm_cache = lm.init_cache(B * W, max_length + 1) if lm is not None else None
     proc = None
@@ -590,7 +640,7 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
     V = joint.dec.w["lm_head"].shape[0]
     NEG = np.float32(-1.0e9)
     while ids.shape[1] < max_length and not all(done):
-        logits = joint.dec.step(new_tok, cache, kvs, T2, key_rep)                       # (B*W, V)
+        logits = joint.dec.step(new_tok, cache, kvs, T2, key_rep, beams=kv_beams)       # (B*W, V)
         scores = logits - ops.row_lse(logits.contiguous())[:, None]                      # log_softmax
         if proc is not None:
             scores = proc(ids, scores.clone())

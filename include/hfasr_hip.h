@@ -551,6 +551,13 @@ int mi_gpt2_step(const mi_gpt2_config* cfg, const void* const* weights, const lo
 int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,
                     void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
                     const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
+/* mi_decoder_step for beam search whose hypotheses share their utterance's encoder frames: the B rows are B / beams utterances x `beams` hypotheses (row = utterance *
+ * beams + k), cross_kv holds L pointers to (B / beams * T_enc, 2d) and enc_len is (B / beams) — the cross K/V of an utterance exist once, not once per hypothesis.
+ * beams > 1 needs U == 1, B % beams == 0 and cross_kv; the step then runs one launch per op whatever the row count, its cross-attention as B / beams batches of
+ * `beams` queries (the teacher-forced forward's call).  beams == 1 is mi_decoder_step.  KV caches, logits and workspace are per row, as there. */
+int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                          void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
+                          const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
 /* Rows-streaming linear (csrc/linear_rows.hip): y = act(x W^T + b) for 1 <= M <= 64 rows, any N, K % 8 == 0; x (M, K) and W (N, K) bf16, 16-B aligned, ldx % 8 == ldw % 8 == 0.
  * act 0 none / 1 erf-GELU / 2 gelu_new.  Exactly one of out32 / out16: out32 (M, ldo32) fp32 = y, or out32 += y when accumulate (the in-place residual add); out16 (M, ldo16)
  * bf16, and with kcache != NULL (N == 3 dkv, M % U == 0) columns [dkv, 2 dkv) / [2 dkv, 3 dkv) of row m = b U + u also go to kcache / vcache (.., Lmax, dkv) at row
@@ -588,6 +595,15 @@ int mi_beam_step_lm(const float* logits, long ldl, const float* lse, const float
                     int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok, long* beam_idx,
                     int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out,
                     const float* lm_logits, long ld_lm, const float* lm_lse, float w_lm, mi_stream_t stream);
+/* mi_beam_step_lm for wide beams and long outputs (csrc/beam_step_wide.hip): the same arguments, rules, arithmetic and outputs, W <= 64, W * V < 2^24, no limit on
+   max_length / Lmax (ids and kept hypotheses move through LDS in column chunks instead of living there).  Two launches: every (utterance, beam) row selects its
+   min(2W, V) best candidates (exact radix select on order-preserving keys), one block per utterance merges them, walks the top 2W and moves the state.  A candidate
+   value of -0 is reported as +0 in top_s.  The table between the two launches is allocated by the library per (device, stream) at the first call and when a later call
+   needs more (hipMalloc: do not make the first call inside a stream capture); MI_ERR_LAUNCH when that fails. */
+int mi_beam_step_wide(const float* logits, long ldl, const float* lse, const float* ctc, float w_att, float w_ctc, int mask_pad, int pad, int eos, int B, int W, int V,
+                      int cur_len, int max_length, int Lmax, float denom, float heur_denom, int early_stopping, long* ids, float* beam_scores, long* new_tok, long* beam_idx,
+                      int* done, int* nfin, float* fin_score, int* fin_len, long* fin_tok, float* top_s, int* top_i, int* done_out,
+                      const float* lm_logits, long ld_lm, const float* lm_lse, float w_lm, mi_stream_t stream);
 
 /* ---- Whisper-style front end + glue (BASELINE config 4).  replaces: transformers WhisperFeatureExtractor numpy path
  *      (selected by configs/default_data_preprocessing_whisper.json:20-29) and the conv/position prologue of WhisperEncoder. */
