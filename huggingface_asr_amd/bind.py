@@ -15,13 +15,16 @@ so the reference's scripts run unchanged: `python -m huggingface_asr_amd.launch 
 The Whisper branch (`model_utils.py:183` on a Whisper checkpoint, `decode_whisper_lumi.sh:60-66`) keeps HuggingFace's `WhisperForConditionalGeneration` — the trainer tests
 for that class (`train_enc_dec_asr.py:82-83`) — and gets the HIP encoder through `whisper.install_whisper()` (called by `bind_all()`): `WhisperEncoder.forward` is replaced,
 decoder / `generate` / checkpoints stay transformers' own — unless HFASR_WHISPER_DECODER=1 (the teacher-forced decoder pass of training on the HIP engine) or
-HFASR_WHISPER_FUSED_LOSS=1 (also the training loss out of the tied head's GEMM) is set in the environment `bind_all()` runs in."""
+HFASR_WHISPER_FUSED_LOSS=1 (also the training loss out of the tied head's GEMM) is set in the environment `bind_all()` runs in.
+
+HFASR_CTC_BEAM=1 in the environment `install()` runs in also swaps `utilities.eval_utils.ctc_beam_decode` for the device prefix beam search (`decoding.ctc_beam_decode`);
+without it that function stays the reference's, because the two do not compute the same thing."""
 import sys
 
 from transformers import AutoConfig, AutoFeatureExtractor, AutoModelForCTC, AutoModelForPreTraining, AutoModelForSpeechSeq2Seq
 
 from .configuration_ebranchformer import Wav2Vec2EBranchformerConfig
-from .decoding import ctc_greedy_decode
+from .decoding import ctc_beam_decode, ctc_greedy_decode
 from .feature_extraction import CustomFeatureExtractor, CustomFeatureExtractorConfig
 from .modeling_bestrq import BestRQEBranchformerForCTC, BestRQEBranchformerForPreTraining, BestRQEBranchformerForPreTrainingConfig
 from .modeling_ebranchformer import Wav2Vec2EBranchformerForCTC
@@ -43,6 +46,11 @@ REBIND = {
 # preprocess_logits_for_metrics (train_ctc_asr.py:77-85): a Python groupby over a device tensor there, two kernel launches here.
 REBIND_FUNCTIONS = {
     "utilities.eval_utils": {"ctc_greedy_decode": ctc_greedy_decode},
+}
+# HFASR_CTC_BEAM=1 (read when install() runs) adds these: ctc_beam_decode (eval_utils.py:46-62, the same trainer's choice with --generation_num_beams > 1) is torchaudio's
+# flashlight decoder there and the device prefix search of csrc/ctc_beam.hip here — other numbers by design (sum over alignments instead of the best path), hence opt-in.
+REBIND_FUNCTIONS_CTC_BEAM = {
+    "utilities.eval_utils": {"ctc_beam_decode": ctc_beam_decode},
 }
 _REF_PACKAGES = ("models", "utilities", "decoding", "trainers", "augmentations")
 
@@ -85,7 +93,12 @@ def _install_functions():
     """REBIND's job for the function table: the defining module gets ours (for importers that come later), and every already-imported reference module or
     `__main__` that holds the reference's function under its own name (`from utilities.eval_utils import ctc_greedy_decode`) gets it too."""
     import importlib
-    for modname, names in REBIND_FUNCTIONS.items():
+    import os
+    table = {m: dict(names) for m, names in REBIND_FUNCTIONS.items()}
+    if os.environ.get("HFASR_CTC_BEAM") == "1":
+        for m, names in REBIND_FUNCTIONS_CTC_BEAM.items():
+            table.setdefault(m, {}).update(names)
+    for modname, names in table.items():
         try:
             mod = importlib.import_module(modname)
         except (ImportError, OSError):      # jiwer / torchaudio / wandb absent, or a shared library of theirs that does not load: the module cannot be in use either

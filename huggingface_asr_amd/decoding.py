@@ -43,6 +43,27 @@ def ctc_greedy_decode(logits: torch.Tensor, blank, pad_token_id) -> torch.Tensor
     return ops.ctc_greedy_decode(logits, int(blank), int(pad_token_id))["tokens"]
 
 
+def ctc_beam_decode(logits: torch.Tensor, _, tokenizer, beam_size: int) -> torch.Tensor:
+    """The reference's ctc_beam_decode by position (src/utilities/eval_utils.py:46-62: logits, an unused argument, the tokenizer, the beam size): logits (B, T, V+1)
+    -> (B, L) int64 on the logits' device, every utterance's best hypothesis then tokenizer.pad_token_id, L the longest of them.  Blank = the last class, as the model
+    and the greedy binding have it; every frame counts.  NOT the reference's numbers: that function runs torchaudio's flashlight lexicon-free decoder (the best single
+    alignment path, a `sil` token), this one the sum-over-alignments prefix search of csrc/ctc_beam.hip on the device (ops.ctc_beam_decode also returns n-best,
+    scores and frames) — which is why bind.install() swaps it in only on request (HFASR_CTC_BEAM=1)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise TypeError("ctc_beam_decode: (B, T, V+1) logits")
+    if not logits.is_cuda:
+        raise RuntimeError("ctc_beam_decode (HIP) needs a device tensor; there is no CPU fallback")
+    from . import ops
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        logits = logits.float()
+    pad = tokenizer.pad_token_id
+    if pad is None:
+        raise ValueError("ctc_beam_decode: tokenizer.pad_token_id is not set")
+    out = ops.ctc_beam_decode(logits, logits.shape[-1] - 1, int(pad), beams=int(beam_size))
+    longest = int(out["n_tokens"].max())
+    return out["tokens"][:, 0, :longest].contiguous()
+
+
 class CTCRescorerLogitsProcessor(LogitsProcessor):
     FULL_STATE_BYTES = 1 << 30      # keep every (hypothesis, token) chain between calls while that tensor stays below this (else: re-run the selected chains)
 

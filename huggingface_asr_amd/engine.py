@@ -258,13 +258,28 @@ class EBranchformerEngine:
         return feats, cs, T2, ws, pos, posp, compute
 
     def transcribe(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, span="valid", pad_id=0, slot=0, want_hidden=False, return_frames=False,
-                   dtype=torch.int64):
-        """CTC greedy transcription on the device: feats (B,T,F) -> dict(tokens (B,T2) `dtype` = the token ids then pad_id, n_tokens (B) int32, best (B,T2) int32 = the
+                   dtype=torch.int64, beams=None, token_topk=None, nbest=1):
+        """CTC transcription on the device, greedy or (with `beams`) by prefix beam search.
+        beams=None: feats (B,T,F) -> dict(tokens (B,T2) `dtype` = the token ids then pad_id, n_tokens (B) int32, best (B,T2) int32 = the
         per-frame classes, inner_len, outer_len[, frames (B,T2) int32 = the frame each token starts at, then -1][, last_hidden]).  Blank = the last class.
         span "valid": frames beyond outer_len (the lengths the CTC loss is trained with) are cut; "all": every frame counts, as in the reference's ctc_greedy_decode.
-        With `head_argmax` on (the default; and a head that fits the fused kernel) no logits tensor is allocated; `slot` as in forward()."""
+        With `head_argmax` on (the default; and a head that fits the fused kernel) no logits tensor is allocated; `slot` as in forward().
+        beams=W (1..64): the forward with fp32-or-`logits_dtype` logits, then ops.ctc_beam_decode over them with the same lengths (W hypotheses, the `token_topk` best
+        classes per frame, None = min(W, V)): tokens / n_tokens[/ frames] are the best hypothesis' (tokens (B,T2)), and the dict gains nbest_tokens (B,nbest,T2),
+        nbest_n (B,nbest), scores (B,nbest) fp32[, nbest_frames (B,nbest,T2)]; no `best`."""
         if span not in ("valid", "all"):
             raise ValueError(f"transcribe: span must be 'valid' or 'all', got {span!r}")
+        if beams is not None:
+            fwd = self.forward(feats, feat_lengths, want_hidden=want_hidden, want_logits=True, slot=slot)
+            bo = ops.ctc_beam_decode(fwd["logits"], self.cfg["vocab_size"], pad_id, fwd["outer_len"] if span == "valid" else None, beams=beams, token_topk=token_topk,
+                                     nbest=nbest, return_frames=return_frames, dtype=dtype)
+            out = dict(tokens=bo["tokens"][:, 0], n_tokens=bo["n_tokens"][:, 0], nbest_tokens=bo["tokens"], nbest_n=bo["n_tokens"], scores=bo["scores"],
+                       inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
+            if return_frames:
+                out.update(frames=bo["frames"][:, 0], nbest_frames=bo["frames"])
+            if want_hidden:
+                out["last_hidden"] = fwd["last_hidden"]
+            return out
         feats, cs, T2, ws, pos, posp, compute = self._prepare(feats, slot)
         B, c = feats.shape[0], self.cfg
         d, V1, L = c["hidden_size"], c["vocab_size"] + 1, _lib.lib()

@@ -478,6 +478,81 @@ def ctc_greedy_decode(logits, blank, pad_id, lengths=None, *, return_frames=Fals
     return out
 
 
+def _ctc_beam_logits(logits, blank, what):
+    _req(logits)
+    if logits.dtype not in (torch.float32, BF16) or logits.dim() != 3:
+        raise TypeError(f"{what}: (B, T, V+1) fp32 / bf16 logits")
+    if logits.shape[0] < 1 or logits.shape[1] < 1 or logits.shape[2] < 2:
+        raise ValueError(f"{what}: at least one utterance, one frame and two classes, got {tuple(logits.shape)}")
+    if not 0 <= int(blank) < logits.shape[2]:
+        raise ValueError(f"{what}: blank {blank} outside [0, {logits.shape[2]})")
+    return logits if logits.stride(2) == 1 else logits.contiguous()
+
+
+def ctc_beam_cut(logits, blank, token_topk, lengths=None):
+    """the first launch of ctc_beam_decode on its own (mi_ctc_beam_cut): logits (B, T, V+1) f32|bf16 -> dict(lse (B, T), lp_blank (B, T), lp (B, T, K) fp32,
+    ids (B, T, K) int32): per frame t < n_b the row's log-sum-exp, the blank's log-probability and the min(K, V) non-blank classes with the largest logits, best first,
+    equal values by lower class (entries past V: -inf / -1).  Rows past n_b are not written."""
+    K = int(token_topk)
+    if not 1 <= K <= 64:
+        raise ValueError(f"ctc_beam_cut: token_topk must be in 1..64, got {token_topk}")
+    logits = _ctc_beam_logits(logits, blank, "ctc_beam_cut")
+    B, T, V1 = logits.shape
+    dev = logits.device
+    lengths = _lengths_i32(lengths, B, dev)
+    lse, lpb = torch.empty((B, T), device=dev, dtype=torch.float32), torch.empty((B, T), device=dev, dtype=torch.float32)
+    lp, ids = torch.empty((B, T, K), device=dev, dtype=torch.float32), torch.empty((B, T, K), device=dev, dtype=torch.int32)
+    rc = _lib.lib().mi_ctc_beam_cut(logits.data_ptr(), logits.stride(1), logits.stride(0), 0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(lengths), int(blank), K,
+                                    lse.data_ptr(), lpb.data_ptr(), lp.data_ptr(), ids.data_ptr(), _stream())
+    _lib.check(rc, "mi_ctc_beam_cut")
+    return dict(lse=lse, lp_blank=lpb, lp=lp, ids=ids)
+
+
+def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=None, nbest=1, return_frames=False, dtype=torch.int64):
+    """CTC prefix beam search (csrc/ctc_beam.hip states the semantics: the sum over alignments, not the flashlight decoder's max) of logits (B, T, V+1) f32|bf16
+    (last dim contiguous, any row / batch strides) with `beams` <= 64 hypotheses per utterance over the `token_topk` <= 64 best non-blank classes of every frame
+    (None: min(beams, V), as the reference passes beam_size_token = beam_size).  -> dict(tokens (B, nbest, T) `dtype` = each hypothesis' ids then pad_id, best first,
+    n_tokens (B, nbest) int32, scores (B, nbest) fp32 = log of the summed alignment probability[, frames (B, nbest, T) int32 = the frame at which each token's prefix
+    entered the beam, then -1]); hypotheses that do not exist: 0 tokens, score -inf.  lengths (B): frames that count per utterance (None: all).  Two launches."""
+    if not isinstance(beams, int) or isinstance(beams, bool) or not isinstance(nbest, int) or isinstance(nbest, bool):
+        raise TypeError("ctc_beam_decode: beams and nbest are ints")
+    if token_topk is not None and (not isinstance(token_topk, int) or isinstance(token_topk, bool)):
+        raise TypeError("ctc_beam_decode: token_topk is an int or None")
+    if not 1 <= beams <= 64:
+        raise ValueError(f"ctc_beam_decode: beams must be in 1..64, got {beams}")
+    if not 1 <= nbest <= beams:
+        raise ValueError(f"ctc_beam_decode: nbest must be in 1..beams, got {nbest} with {beams} beams")
+    if token_topk is not None and not 1 <= token_topk <= 64:
+        raise ValueError(f"ctc_beam_decode: token_topk must be in 1..64, got {token_topk}")
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError("ctc_beam_decode: token dtype int32 or int64")
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
+        raise TypeError("ctc_beam_decode: (B, T, V+1) fp32 / bf16 logits")
+    logits = _ctc_beam_logits(logits, blank, "ctc_beam_decode")
+    B, T, V1 = logits.shape
+    K = min(beams, V1 - 1) if token_topk is None else token_topk
+    dev = logits.device
+    lengths = _lengths_i32(lengths, B, dev)
+    cut = ctc_beam_cut(logits, blank, K, lengths)
+    L = _lib.lib()
+    nbytes = int(L.mi_ctc_beam_workspace_bytes(B, T, beams))
+    if nbytes == 0:
+        raise ValueError(f"ctc_beam_decode: {T} frames x {beams} beams is beyond the node table (T * beams < 2^22 - 2)")
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    tokens = torch.empty((B, nbest, T), device=dev, dtype=dtype)
+    n = torch.empty((B, nbest), device=dev, dtype=torch.int32)
+    scores = torch.empty((B, nbest), device=dev, dtype=torch.float32)
+    frames = torch.empty((B, nbest, T), device=dev, dtype=torch.int32) if return_frames else None
+    rc = L.mi_ctc_beam_walk(logits.data_ptr(), logits.stride(1), logits.stride(0), 0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(lengths), int(blank), int(pad_id),
+                            beams, K, nbest, cut["lse"].data_ptr(), cut["lp_blank"].data_ptr(), cut["lp"].data_ptr(), cut["ids"].data_ptr(), ws.data_ptr(), nbytes,
+                            tokens.data_ptr(), int(dtype == torch.int64), n.data_ptr(), scores.data_ptr(), _p(frames), _stream())
+    _lib.check(rc, "mi_ctc_beam_walk")
+    out = dict(tokens=tokens, n_tokens=n, scores=scores)
+    if return_frames:
+        out["frames"] = frames
+    return out
+
+
 def ctc_loss(logits, labels, in_len, *, reduction="mean", zero_infinity=False, lse=None):
     """logits (B,T,V+1) f32|bf16 (blank = last class), labels (B,U) int64 (<0 = padding), in_len (B) int32.
     Returns (loss scalar tensor | per-utterance nll for reduction='none', nll (B), tgt_len (B))."""

@@ -267,6 +267,23 @@ int mi_ctc_collapse(const int* best, int B, int T, const int* lengths, int blank
 /* the two above over logits (B, T, V1) with element strides (ld_batch, ld_row); best (B, T) int32: scratch of the caller, left holding the per-frame classes */
 int mi_ctc_greedy(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, long pad_id,
                   int* best, void* tokens, int tokens_dtype, int* n_tokens, int* frames, mi_stream_t stream);
+
+/* ---- CTC prefix beam search (csrc/ctc_beam.hip, whose header states the semantics): the sum-over-alignments search, NOT a clone of the flashlight decoder behind the
+ * reference's ctc_beam_decode (src/utilities/eval_utils.py:46-62).  Two launches.
+ * mi_ctc_beam_cut: one pass over logits (B, T, V1) fp32 (dtype 0) / bf16 (1) with element strides (ld_batch, ld_row), rows t < n_b only (n_b = lengths[b] clamped to
+ * [0, T], or T when lengths is null): lse (B, T) the rows' log-sum-exp, lp_blank (B, T) = x[blank] - lse, cut_lp / cut_id (B, T, K) the min(K, V1 - 1) non-blank classes
+ * with the largest logits as (x - lse, class), best first, equal values by lower class (entries past V1 - 1: -inf / -1).
+ * mi_ctc_beam_walk: one block per utterance walks its frames with W hypotheses over the cut (the same logits, lengths, blank and K as the cut) and writes the nbest <= W
+ * best, best first: tokens (B, nbest, T) int32 (tokens_dtype 0) / int64 (1) then pad_id, n_tokens (B, nbest) int32, scores (B, nbest) fp32, frames (B, nbest, T) int32
+ * (nullable): the frame at which each token's prefix first entered the beam, then -1; rows beyond the hypotheses that exist: 0, -inf, pad_id / -1.  workspace:
+ * mi_ctc_beam_workspace_bytes(B, T, W) bytes, 16-B aligned, contents irrelevant before and after.  No float atomics: bit-identical run to run.
+ * MI_ERR_ARG before any launch: W or K outside 1..64, nbest outside 1..W, blank outside [0, V1), V1 < 2.  MI_ERR_UNSUPPORTED: V1 > 2^20 or T W >= 2^22 - 2. */
+size_t mi_ctc_beam_workspace_bytes(int B, int T, int W);
+int mi_ctc_beam_cut(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, int K, float* lse, float* lp_blank,
+                    float* cut_lp, int* cut_id, mi_stream_t stream);
+int mi_ctc_beam_walk(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, long pad_id, int W, int K, int nbest,
+                     const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* workspace, size_t workspace_bytes, void* tokens,
+                     int tokens_dtype, int* n_tokens, float* scores, int* frames, mi_stream_t stream);
 /* the CTC head without its logits: best[m] = argmax_n (A W^T + b)[m][n] out of the 256 x 256 GEMM's epilogue, which leaves one (max, index) pair per row and 64 columns
  * in `workspace` (mi_gemm_argmax_workspace_floats(M, N) floats) and stores no C; a small second launch folds a row's pairs.  Equals mi_row_argmax over the fp32 output of
  * mi_gemm_bf16 on the same operands.  MI_ERR_UNSUPPORTED outside that kernel's shapes (K % 64, K >= 128, 16-B aligned operands): the caller runs mi_gemm_bf16 into a
