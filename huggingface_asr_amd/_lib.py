@@ -167,6 +167,9 @@ SIGNATURES = {
     "mi_ctc_loss_bwd_nll": [vp, i64, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, f32, vp, sz, vp, i64, vp, vp, vp, vp],
     "mi_ctc_reduce": [vp, vp, i32, i32, i32, vp, vp],
     "mi_ce_label_smoothing_bwd": [vp, i64, vp, i32, i32, i32, i32, f32, f32, vp, vp, i64, vp],
+    "mi_mix_ce_fwd": [vp, i64, i64, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp],
+    "mi_mix_ce_bwd_workspace_floats": [i32, i32, i32],
+    "mi_mix_ce_bwd": [vp, i64, i64, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, sz, vp, vp],
     "mi_embed_tokens_bwd": [vp, vp, f32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp],
     "mi_embed_tokens_bwd_workspace_bytes": [i32, i32, i32],
     "mi_specaug_f32": [vp, vp, i32, i32, i32, vp, i32, i32, f32, vp],
@@ -177,6 +180,8 @@ SIGNATURES = {
     "mi_gpt2_step": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, sz, vp, i64, vp],
     "mi_decoder_step": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
     "mi_decoder_step_beams": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
+    "mi_decoder_step_taps_workspace_bytes": [C.POINTER(Gpt2Config), i32, i32, i32],
+    "mi_decoder_step_taps": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, i32, vp, sz, vp, i64, vp],
     "mi_linear_rows_workspace_bytes": [i32, i32, i32],
     "mi_linear_rows": [vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp],
     "mi_greedy_advance": [vp, vp, i64, i32, i64, i64, vp, vp, vp, i32, vp],
@@ -220,7 +225,7 @@ def lib():
             fn.argtypes = args
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
-                                          "mi_gpt2_step_workspace_bytes", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes") else i32
+                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None
         h.mi_profile_reset.argtypes = []; h.mi_profile_reset.restype = None

@@ -28,16 +28,18 @@ from .decoding import ctc_beam_decode, ctc_greedy_decode
 from .feature_extraction import CustomFeatureExtractor, CustomFeatureExtractorConfig
 from .modeling_bestrq import BestRQEBranchformerForCTC, BestRQEBranchformerForPreTraining, BestRQEBranchformerForPreTrainingConfig
 from .modeling_ebranchformer import Wav2Vec2EBranchformerForCTC
-from .modeling_joint import GPT2LMMultiHeadModel, GPT2MultiHeadConfig, JointCTCAttentionEncoderDecoder, JointCTCAttentionEncoderDecoderConfig, Seq2SeqLMOutputLosses
+from .modeling_joint import (GPT2LMMultiHeadModel, GPT2LMMultiHeadModelMixing, GPT2MultiHeadConfig, GPT2MultiHeadMixingConfig, JointCTCAttentionEncoderDecoder,
+                             JointCTCAttentionEncoderDecoderConfig, Seq2SeqLMOutputLosses)
 
-# reference module -> {name it exports: our class}.  (Classes the HIP path does not build — Wav2Vec2EBranchformerForPreTraining, the mixing / residual
-# GPT-2 variants — keep their reference definitions)
+# reference module -> {name it exports: our class}.  (Classes the HIP path does not build — Wav2Vec2EBranchformerForPreTraining, the residual
+# GPT-2 variant — keep their reference definitions)
 REBIND = {
     "models.ctc_encoder_plus_autoregressive_decoder": {"JointCTCAttentionEncoderDecoder": JointCTCAttentionEncoderDecoder,
                                                       "JointCTCAttentionEncoderDecoderConfig": JointCTCAttentionEncoderDecoderConfig,
                                                       "Seq2SeqLMOutputLosses": Seq2SeqLMOutputLosses},
     "models.encoders.e_branchformer": {"Wav2Vec2EBranchformerConfig": Wav2Vec2EBranchformerConfig, "Wav2Vec2EBranchformerForCTC": Wav2Vec2EBranchformerForCTC},
     "models.decoders.multi_head_gpt2": {"GPT2MultiHeadConfig": GPT2MultiHeadConfig, "GPT2LMMultiHeadModel": GPT2LMMultiHeadModel},
+    "models.decoders.multi_head_gpt2_mixing": {"GPT2MultiHeadMixingConfig": GPT2MultiHeadMixingConfig, "GPT2LMMultiHeadModelMixing": GPT2LMMultiHeadModelMixing},
     "models.bestrq": {"BestRQEBranchformerForCTC": BestRQEBranchformerForCTC, "BestRQEBranchformerForPreTraining": BestRQEBranchformerForPreTraining,
                       "BestRQEBranchformerForPreTrainingConfig": BestRQEBranchformerForPreTrainingConfig},
     "utilities.feature_extractors": {"CustomFeatureExtractor": CustomFeatureExtractor, "CustomFeatureExtractorConfig": CustomFeatureExtractorConfig},
@@ -62,6 +64,7 @@ def bind_all():
     AutoModelForCTC.register(BestRQEBranchformerForPreTrainingConfig, BestRQEBranchformerForCTC, exist_ok=True)
     AutoModelForPreTraining.register(BestRQEBranchformerForPreTrainingConfig, BestRQEBranchformerForPreTraining, exist_ok=True)
     AutoConfig.register("gpt2-multi-head", GPT2MultiHeadConfig, exist_ok=True)
+    AutoConfig.register("gpt2-multi-head-mixing", GPT2MultiHeadMixingConfig, exist_ok=True)
     AutoConfig.register("joint_aed_ctc_speech-encoder-decoder", JointCTCAttentionEncoderDecoderConfig, exist_ok=True)
     AutoModelForSpeechSeq2Seq.register(JointCTCAttentionEncoderDecoderConfig, JointCTCAttentionEncoderDecoder, exist_ok=True)
     AutoConfig.register("custom_feature_extractor", CustomFeatureExtractorConfig, exist_ok=True)
@@ -77,6 +80,7 @@ def bind_all():
     ref_auto = sys.modules.get("models.auto_wrappers")          # the reference's own decoder registry (bind.py:48-49), when its tree is loaded
     if ref_auto is not None:
         ref_auto.CustomModelForCausalLM.register(GPT2MultiHeadConfig, GPT2LMMultiHeadModel, exist_ok=True)
+        ref_auto.CustomModelForCausalLM.register(GPT2MultiHeadMixingConfig, GPT2LMMultiHeadModelMixing, exist_ok=True)
 
 
 def _rebind_everywhere(replaced: dict):

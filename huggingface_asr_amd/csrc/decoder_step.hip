@@ -26,6 +26,20 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const bf16_t* __restrict
     }
 }
 
+// multi-tap head (mi_decoder_step_taps): the LAST new position's residual stream of every sequence, rounded to bf16, into one column block of the head's input rows
+// x points at that position of sequence 0; sequences are ldx floats apart, head input rows ldo elements
+__global__ __launch_bounds__(256) void tap_rows_kernel(const float* __restrict__ x, long ldx, bf16_t* __restrict__ out, long ldo, int B, int d) {
+    const int d8 = d >> 3;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= B * d8) return;
+    const int b = i / d8, c = i - b * d8;
+    const float* src = x + (long)b * ldx + c * 8;
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = f2bf(src[j]);
+    *reinterpret_cast<bf16x8*>(out + (long)b * ldo + c * 8) = o;
+}
+
 // ---- skinny fused linear for the token step (M <= 8 rows, e.g. 1 utterance x 5 beams): y = act(LN?(x) · W^T + b) (+ resid)
 // A 128x128 MFMA tile is 96 % padding at M = 5 and every separate LayerNorm / residual launch costs more than its work, so this
 // kernel does it GEMV-style: the block normalises the M rows into LDS (bf16-rounded, like the LN kernel's output), then every wave
@@ -289,7 +303,8 @@ namespace {
 constexpr int ROWS_MAXM = 64;
 bool step_streams(const mi_gpt2_config& c, int M, int U) { return c.step_form == 2 && U == 1 && M <= ROWS_MAXM; }
 struct StepWs { float* x; bf16_t *a, *qkv, *ctx, *qq, *m, *hid; float* fws; float* part; size_t part_floats; size_t bytes; };
-StepWs carve(const mi_gpt2_config& c, int M, int B, int U, void* base) {
+constexpr int MAX_TAPS = 8;
+StepWs carve(const mi_gpt2_config& c, int M, int B, int U, void* base, int nt = 1, bool taps = false) {      // nt: column blocks of the head's input row (1: the plain head); taps: a multi-tap call, which never takes the fused form
     Carver k{(char*)base, 0};
     StepWs w;
     w.x = (float*)k.take((size_t)M * c.d * 4);
@@ -298,11 +313,11 @@ StepWs carve(const mi_gpt2_config& c, int M, int B, int U, void* base) {
     w.ctx = (bf16_t*)k.take((size_t)M * c.d * 2);
     w.qq = (bf16_t*)k.take((size_t)M * c.d * 2);
     w.m = (bf16_t*)k.take((size_t)M * 4 * c.d * 2);
-    w.hid = (bf16_t*)k.take((size_t)B * c.d * 2);
-    w.fws = gpt2_step_fused_ok(c, B, U) ? (float*)k.take(gpt2_step_fused_floats(c, M) * sizeof(float)) : nullptr;
+    w.hid = (bf16_t*)k.take((size_t)B * nt * c.d * 2);
+    w.fws = (!taps && gpt2_step_fused_ok(c, B, U)) ? (float*)k.take(gpt2_step_fused_floats(c, M) * sizeof(float)) : nullptr;
     w.part = nullptr; w.part_floats = 0;
     if (step_streams(c, M, U)) {                                       // the K-split partials of the largest linear of the step
-        const int shapes[5][2] = {{3 * c.d, c.d}, {c.d, c.d}, {4 * c.d, c.d}, {c.d, 4 * c.d}, {c.V, c.d}};
+        const int shapes[5][2] = {{3 * c.d, c.d}, {c.d, c.d}, {4 * c.d, c.d}, {c.d, 4 * c.d}, {c.V, nt * c.d}};
         for (auto& s : shapes) { const size_t f = linear_rows_workspace_floats(M, s[0], s[1]); w.part_floats = f > w.part_floats ? f : w.part_floats; }
         w.part = (float*)k.take(w.part_floats * sizeof(float));
     }
@@ -327,9 +342,12 @@ extern "C" size_t mi_gpt2_step_workspace_bytes(const mi_gpt2_config* cfg, int B,
 // cross_kv is (B / beams * T_enc, 2d) per layer and enc_len (B / beams).  One new token per row; the step runs one launch per op whatever the row count (the fused, GEMV
 // and streaming forms index the cross tables by row), and its cross-attention is the teacher-forced forward's call: B / beams batches of `beams` queries, so an utterance's
 // K / V tiles are fetched once for all its hypotheses instead of once per hypothesis.  Everything else — self-attention over the per-row cache included — is per row.
-extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
-                                     void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
-                                     float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
+// taps == NULL: the plain head on ln_f of the last new position (mi_gpt2_step, mi_decoder_step, mi_decoder_step_beams: their launches, one for one).
+// taps != NULL (mi_decoder_step_taps): weights[4] is the folded head (V, n_taps * d) and column block h of its input row is the stream after taps[h] blocks.
+static int step_impl(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                     void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                     float emb_scale, const float* head_bias, const int* taps, int n_taps, void* workspace, size_t workspace_bytes, float* logits, long ld_logits,
+                     hipStream_t st) {
     MI_ENTER();
     const mi_gpt2_config& c = *cfg;
     if (c.act < 0 || c.act > 1 || c.step_form < 0 || c.step_form > 2) return MI_ERR_ARG;
@@ -340,16 +358,36 @@ extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* cons
     const int hd = c.d / c.H;
     if (hd != 64 && hd != 128) return MI_ERR_UNSUPPORTED;
     const int M = B * U, d = c.d;
-    StepWs w = carve(c, M, B, U, workspace);
+    const int nt = taps ? n_taps : 1;
+    if (taps) {
+        if (n_taps < 1 || n_taps > MAX_TAPS) return MI_ERR_ARG;
+        for (int h = 0; h < n_taps; ++h) if (taps[h] < 0 || taps[h] > c.L) return MI_ERR_ARG;
+    }
+    const int hk = nt * d;                                            // K of the head
+    StepWs w = carve(c, M, B, U, workspace, nt, taps != nullptr);
     if (w.bytes > workspace_bytes) return MI_ERR_ARG;
     const float scale = 1.0f / sqrtf((float)hd);
     auto Gf = [&](int i) { return (const float*)weights[i]; };
     auto Lw = [&](int l, int i) { return weights[5 + l * 18 + i]; };
     auto Lf = [&](int l, int i) { return (const float*)weights[5 + l * 18 + i]; };
-    auto ln = [&](const float* x, long ldx, const float* g, const float* b, bf16_t* out, int rows) {
-        return mi_layernorm_chain(x, ldx, nullptr, 1, nullptr, nullptr, 0.f, nullptr, 0, g, b, c.eps, out, d, nullptr, 0, nullptr, nullptr, nullptr, 0, rows, d, st);
+    auto ln_to = [&](const float* x, long ldx, const float* g, const float* b, bf16_t* out, long ldo, int rows) {
+        return mi_layernorm_chain(x, ldx, nullptr, 1, nullptr, nullptr, 0.f, nullptr, 0, g, b, c.eps, out, ldo, nullptr, 0, nullptr, nullptr, nullptr, 0, rows, d, st);
     };
-    if (!shared && c.step_form == 0 && c.act == 0 && w.fws) {
+    auto ln = [&](const float* x, long ldx, const float* g, const float* b, bf16_t* out, int rows) { return ln_to(x, ldx, g, b, out, d, rows); };
+    // multi-tap head: the blocks of the head's input row that read the stream after `loc` blocks (loc < L: the raw stream; loc == L: ln_f, written by head_input)
+    auto tap = [&](int loc) {
+        for (int h = 0; h < n_taps && taps; ++h)
+            if (taps[h] == loc)
+                hipLaunchKernelGGL(tap_rows_kernel, dim3(cdiv(B * (d / 8), 256)), dim3(256), 0, st, w.x + (size_t)(U - 1) * d, (long)U * d, w.hid + (size_t)h * d, (long)hk, B,
+                                   d);
+    };
+    auto head_input = [&]() {                                         // ln_f of the last new position of every sequence (rows b*U + U-1: a strided view) -> its block(s)
+        if (!taps) return ln(w.x + (size_t)(U - 1) * d, (long)U * d, Gf(2), Gf(3), w.hid, B);
+        for (int h = 0; h < n_taps; ++h)
+            if (taps[h] == c.L) RUN(ln_to(w.x + (size_t)(U - 1) * d, (long)U * d, Gf(2), Gf(3), w.hid + (size_t)h * d, hk, B));
+        return MI_OK;
+    };
+    if (!taps && !shared && c.step_form == 0 && c.act == 0 && w.fws) {
         // ---- fused token step (decoder_fused.hip): three launches per layer (two without cross-attention), every cross-workgroup reduction folded into the next launch's
         // prologue (the embedding too)
         RUN(gpt2_step_fused(c, weights, ids_new, emb_scale, M, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, w.fws, w.hid, st));
@@ -360,6 +398,7 @@ extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* cons
         return MI_OK;
     }
     RUN(mi_embed_tokens(ids_new, Gf(0), emb_scale, Gf(1), past, U, d, M, c.V, w.x, st));
+    tap(0);
     if (!shared && step_streams(c, M, U)) {
         // ---- streaming token step (linear_rows.hip): up to 64 rows, one new token each; every linear reads its weights once, spread over the chip by N and K
         auto lin = [&](const bf16_t* in, int K, const void* W, const float* bias, int N, int act, float* o32, long ldo32, int accumulate, bf16_t* o16, bf16_t* kc, bf16_t* vc) {
@@ -382,13 +421,14 @@ extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* cons
             RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
             RUN(lin(w.a, d, Lw(l, 14), Lf(l, 15), 4 * d, mlp_act, nullptr, 0, 0, w.m, nullptr, nullptr));
             RUN(lin(w.m, 4 * d, Lw(l, 16), Lf(l, 17), d, 0, w.x, d, 1, nullptr, nullptr, nullptr));
+            if (l + 1 < c.L) tap(l + 1);
         }
-        RUN(ln(w.x, d, Gf(2), Gf(3), w.hid, B));
-        RUN(lin(w.hid, d, weights[4], head_bias, c.V, 0, logits, ld_logits, 0, nullptr, nullptr, nullptr));
+        RUN(head_input());                                            // (U == 1: every row is its sequence's last position)
+        RUN(lin(w.hid, hk, weights[4], head_bias, c.V, 0, logits, ld_logits, 0, nullptr, nullptr, nullptr));
         MI_CHECK_LAUNCH();
         return MI_OK;
     }
-    if (!shared && c.act == 0 && M <= SK_MAXM && (d % 8) == 0 && 4 * d <= 2048) {
+    if (!shared && c.act == 0 && M <= SK_MAXM && (d % 8) == 0 && 4 * d <= 2048 && hk <= 2048) {      // (a head input wider than the GEMV kernel's K: one launch per op, below)
         // ---- skinny token step: LayerNorms, biases, activations and residual adds fused into GEMV-style linears (8 launches per layer)
         auto lin_ln = [&](const float* g, const float* b, const void* W, const float* bias, int N, bf16_t* out, int act) {
             SkArgs a{}; a.x32 = w.x; a.ldx = d; a.ln_g = g; a.ln_b = b; a.eps = c.eps; a.W = (const bf16_t*)W; a.ldw = d; a.bias = bias;
@@ -419,6 +459,15 @@ extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* cons
             }
             RUN(lin_ln(Lf(l, 12), Lf(l, 13), Lw(l, 14), Lf(l, 15), 4 * d, w.m, 2));
             RUN(lin_res(w.m, 4 * d, Lw(l, 16), Lf(l, 17)));
+            if (l + 1 < c.L) tap(l + 1);
+        }
+        if (taps) {                                                   // ln_f into its column block, then the head over the whole row (K = n_taps d)
+            RUN(head_input());
+            SkArgs a{}; a.x16 = w.hid; a.ldx16 = hk; a.W = (const bf16_t*)weights[4]; a.ldw = hk; a.bias = head_bias; a.out32 = logits; a.ldo32 = ld_logits;
+            a.M = B; a.N = c.V; a.K = hk; a.act = 0;
+            RUN(skinny(a, st));
+            MI_CHECK_LAUNCH();
+            return MI_OK;
         }
         // ln_f on the last new position of every sequence + lm head -> fp32 logits
         SkArgs a{}; a.x32 = w.x + (size_t)(U - 1) * d; a.ldx = (long)U * d; a.ln_g = Gf(2); a.ln_b = Gf(3); a.eps = c.eps; a.W = (const bf16_t*)weights[4];
@@ -450,12 +499,37 @@ extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* cons
         RUN(ln(w.x, d, Lf(l, 12), Lf(l, 13), w.a, M));
         RUN(mi_gemm_bf16(w.a, d, Lw(l, 14), d, Lf(l, 15), 1, w.m, 4 * d, 0, nullptr, 0, 1.f, mlp_act, M, 4 * d, d, 0, 0, st));
         RUN(mi_gemm_bf16(w.m, 4 * d, Lw(l, 16), 4 * d, Lf(l, 17), 1, w.x, d, 1, w.x, d, 1.f, 0, M, d, 4 * d, 0, 0, st));
+        if (l + 1 < c.L) tap(l + 1);
     }
     // ln_f on the last new position of every sequence (rows b*U + U-1: a strided view), then the lm head
-    RUN(ln(w.x + (size_t)(U - 1) * d, (long)U * d, Gf(2), Gf(3), w.hid, B));
-    RUN(mi_gemm_bf16(w.hid, d, weights[4], d, head_bias, head_bias ? 1 : 0, logits, ld_logits, 1, nullptr, 0, 1.f, 0, B, c.V, d, 0, 0, st));
+    RUN(head_input());
+    RUN(mi_gemm_bf16(w.hid, hk, weights[4], hk, head_bias, head_bias ? 1 : 0, logits, ld_logits, 1, nullptr, 0, 1.f, 0, B, c.V, hk, 0, 0, st));
     MI_CHECK_LAUNCH();
     return MI_OK;
+}
+
+extern "C" int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                                     void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                                     float emb_scale, const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, hipStream_t st) {
+    return step_impl(cfg, weights, ids_new, B, beams, U, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, emb_scale, head_bias, nullptr, 0, workspace, workspace_bytes,
+                     logits, ld_logits, st);
+}
+
+// ---- the step with a multi-tap head (GPT2LMMultiHeadModelMixing in every mixing mode, `average_logits`: multi_head_gpt2_mixing.py:101-121, multi_head_gpt2.py:129-136):
+// logits = sum_h A_h hidden[taps[h]] (+ head_bias) as ONE head GEMM with K = n_taps d over the row [stream after taps[0] blocks | ... | stream after taps[n_taps - 1] blocks].
+// weights[4] is the folded head (V, n_taps d) bf16; taps (host memory): 0 = the embedding output, l = the stream after l blocks (no LayerNorm), L = ln_f of the last
+// block's output.  Each tapped stream is rounded to bf16 into its column block when its layer completes (one small launch per tap: tap_rows_kernel).  Everything else is
+// mi_decoder_step_beams; the three-launch fused form has no place to expose a layer's stream, so at <= 8 rows the step runs its GEMV form (step_form 0 and 1 alike).
+extern "C" size_t mi_decoder_step_taps_workspace_bytes(const mi_gpt2_config* cfg, int B, int U, int n_taps) {
+    return carve(*cfg, B * U, B, U, nullptr, n_taps < 1 ? 1 : (n_taps > MAX_TAPS ? MAX_TAPS : n_taps), true).bytes;
+}
+extern "C" int mi_decoder_step_taps(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                                    void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len,
+                                    float emb_scale, const float* head_bias, const int* taps, int n_taps, void* workspace, size_t workspace_bytes, float* logits,
+                                    long ld_logits, hipStream_t st) {
+    if (!taps) return MI_ERR_ARG;
+    return step_impl(cfg, weights, ids_new, B, beams, U, past, Lmax, kcache, vcache, cross_kv, T_enc, enc_len, emb_scale, head_bias, taps, n_taps, workspace, workspace_bytes,
+                     logits, ld_logits, st);
 }
 
 extern "C" int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int U, int past, int Lmax,

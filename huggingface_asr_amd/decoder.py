@@ -19,7 +19,7 @@ import torch
 
 from . import _lib, ops
 from .engine import EBranchformerEngine
-from .packing import _dec_map, _lm_map, decoder_specs, lm_specs, mapped_fp32, packed
+from .packing import _dec_map, _lm_map, decoder_specs, head_fold, head_taps, lm_specs, mapped_fp32, mixes_heads, packed
 
 BF16 = torch.bfloat16
 
@@ -48,8 +48,9 @@ class GPT2DecoderEngine:
         c, dev = self.cfg, self.device
         d, L = c["n_embd"], c["n_layer"]
         m = _dec_map(c, False, prefix)
-        P = {s.name: (t.to(BF16) if s.mat and s.name != "wte" else t).contiguous()          # wte stays fp32: the embedding gather reads it
-             for s, t in packed(decoder_specs(c, d, False), m, mapped_fp32(m, sd, dev))}
+        specs = decoder_specs(c, d, False)
+        F = {s.name: t for s, t in packed(specs, m, mapped_fp32(m, sd, dev))}               # fp32 on the device: what the head fold reads
+        P = {s.name: (F[s.name].to(BF16) if s.mat and s.name != "wte" else F[s.name]).contiguous() for s in specs}      # wte stays fp32: the embedding gather reads it
         fixed = c.get("pos_emb_fixed", False)
         w = dict(wte=P["wte"], scale=float(d) ** 0.5 if fixed else 1.0, pos=_sinusoid_table(c.get("n_positions", 1024), d, dev) if fixed else P["wpe"],
                  lnf=(P["lnf_g"], P["lnf_b"]), heads=[P[f"head{k}"] for k in range(len(c.get("head_locations") or []))],
@@ -65,6 +66,18 @@ class GPT2DecoderEngine:
         self._wtable = (C.c_void_p * len(ptrs))(*[t.data_ptr() for t in ptrs])
         self._gcfg = _lib.Gpt2Config(d=d, H=c["n_head"], L=L, V=w["lm_head"].shape[0], eps=float(c.get("layer_norm_epsilon", 1e-5)))
         self._step_ws = None
+        # decode-time logits from several heads (every mixing mode of GPT2LMMultiHeadModelMixing, `average_logits`): ONE head over the row [tap_0 | ... | ln_f(x)], its
+        # matrix folded here in fp32 from the fp32 parameters and rounded to bf16 once (packing.head_fold); every load folds again
+        w["taps"] = None
+        if mixes_heads(c):
+            taps = head_taps(c)
+            heads = [F[f"head{k}"] for k in range(len(taps) - 1)] + [F["lm_head"] if "lm_head" in F else F["wte"]]
+            fold, bias = head_fold(c, heads, F)
+            w.update(taps=taps, head_fold=fold.to(BF16).contiguous(), head_bias=bias.contiguous() if bias is not None else None,
+                     mix={k: F[k] for k in ("mix", "mix_w", "mix_b") if k in F})
+            ptrs[4] = w["head_fold"]
+            self._wtable_taps = (C.c_void_p * len(ptrs))(*[t.data_ptr() for t in ptrs])      # mi_decoder_step_taps: the same table with the folded head in slot 4
+            self._taps = (C.c_int * len(taps))(*taps)
 
     def ensure_positions(self, n: int):
         """Positions [0, n) must have rows in the table the kernels read (they take row `past + u` unchecked).  Fixed sinusoidal positions exist for every position in
@@ -79,18 +92,41 @@ class GPT2DecoderEngine:
             torch.cuda.synchronize(self.device)        # (rare: once per longer cache) no queued step still reads the old table when it is released
         self.w["pos"] = _sinusoid_table(n, self.cfg["n_embd"], self.device)
         self._wtable[1] = self.w["pos"].data_ptr()
+        if self.w.get("taps"):
+            self._wtable_taps[1] = self.w["pos"].data_ptr()
 
     # ------------------------------------------------------------------ building blocks
     def cross_kv(self, enc_bf16: torch.Tensor):
         """Per-layer cross-attention keys/values of the encoder frames: list of (B*T', 2d) bf16 (computed once per utterance)."""
         return [ops.gemm(enc_bf16, lw["wkv"], lw["bkv"]) for lw in self.w["layers"]]
 
-    def _logits(self, hid_bf16, head_w):
+    def _logits(self, hid_bf16, head_w, bias=None):
         V = head_w.shape[0]
         Vp = (V + 7) // 8 * 8
         buf = torch.empty((hid_bf16.shape[0], Vp), device=self.device, dtype=torch.float32)
-        ops.gemm(hid_bf16, head_w, None, out=buf[:, :V])
+        ops.gemm(hid_bf16, head_w, bias, out=buf[:, :V])
         return buf[:, :V]
+
+    def _head_input(self, taps: dict, hid):
+        """the folded head's input rows [tap_0 | ... | ln_f(x)] (rows, H d) bf16: `taps` loc -> fp32 stream after loc blocks (loc < n_layer), `hid` bf16 ln_f output"""
+        locs, d = self.w["taps"], self.cfg["n_embd"]
+        cat = torch.empty((hid.shape[0], len(locs) * d), device=self.device, dtype=BF16)
+        for h, loc in enumerate(locs):
+            cat[:, h * d:(h + 1) * d] = ops.cast_bf16(taps[loc]) if loc in taps else hid
+        return cat
+
+    def _mixed_logits_fp32(self, per_head):
+        """the reference's mix of the H per-head fp32 logit matrices (rows, V) in fp32 — the loss path; decoding runs the folded head instead"""
+        c, mix = self.cfg, self.w["mix"]
+        V = per_head[0].shape[1]
+        buf = torch.empty((per_head[0].shape[0], (V + 7) // 8 * 8), device=self.device, dtype=torch.float32)
+        out = buf[:, :V]
+        if c["mixing_mode"] == "full":
+            out.copy_(torch.cat(per_head, 1) @ mix["mix_w"].t() + mix["mix_b"])
+        else:
+            m = mix["mix"] if c["mixing_mode"] == "linear" else mix["mix"][:, None]
+            out.copy_(sum(m[h] * per_head[h] for h in range(len(per_head))))
+        return out
 
     def _block(self, l, x, B, U, kv, T_enc, enc_len, self_k=None, self_v=None, past=0, Lmax=0):
         """One GPT-2 block on the fp32 stream x (B*U, d).  With a KV cache (self_k/self_v (B, Lmax, d)) U new tokens are
@@ -138,6 +174,15 @@ class GPT2DecoderEngine:
                 taps[l + 1] = x.clone()
         hid = torch.empty((B * U, d), device=self.device, dtype=BF16)
         ops.layernorm_chain(x, lna=w["lnf"], eps2=eps, outa=hid)
+        if labels is None and w.get("taps"):                   # mixing modes / average_logits (multi_head_gpt2.py:129-136): the folded multi-tap head
+            return dict(logits=self._logits(self._head_input(taps, hid), w["head_fold"], w["head_bias"]).view(B, U, -1), loss=None)
+        if labels is not None and c.get("mixing_mode") is not None:
+            # GPT2LMMultiHeadModelMixing with labels: the plain shifted cross-entropy of the mixed logits over every non-ignored position of the batch — the reference's
+            # formula where the reference is defined (multi_head_gpt2_mixing.py:125-131 indexes `lm_logits[-1]`, the last utterance: B = 1)
+            heads = list(w["heads"]) + [w["lm_head"]]
+            per_head = [self._logits(ops.cast_bf16(taps[loc]) if loc in taps else hid, heads[h]) for h, loc in enumerate(w["taps"])]
+            logits = self._mixed_logits_fp32(per_head).view(B, U, -1)
+            return dict(logits=logits, loss=ops.ce_label_smoothing(logits, labels, shift=1, eps=0.0))
         logits = self._logits(hid, w["lm_head"]).view(B, U, -1)
         loss = None
         if labels is not None:
@@ -189,7 +234,8 @@ class GPT2DecoderEngine:
         past, Lmax = cache["past"], cache["Lmax"]
         self.ensure_positions(past + U)
         L_ = _lib.lib()
-        nbytes = L_.mi_gpt2_step_workspace_bytes(C.byref(self._gcfg), B, U)
+        taps = w.get("taps")
+        nbytes = L_.mi_decoder_step_taps_workspace_bytes(C.byref(self._gcfg), B, U, len(taps)) if taps else L_.mi_gpt2_step_workspace_bytes(C.byref(self._gcfg), B, U)
         if self._step_ws is None or self._step_ws.numel() < nbytes:
             self._step_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         if cache.get("kv_id") != id(kvs):                              # pointer table of the per-layer encoder K/V
@@ -201,6 +247,15 @@ class GPT2DecoderEngine:
         if beams != 1:
             if beams < 1 or B % beams or U != 1 or kvs[0].shape[0] != B // beams * T_enc or (enc_len is not None and enc_len.numel() != B // beams):
                 raise ValueError(f"step(beams={beams}): {B} rows of {U} new tokens over cross tables of {kvs[0].shape[0]} rows (T_enc = {T_enc})")
+        if taps:                                                       # the multi-tap head (mixing modes, average_logits): the same step, taps written as their layers complete
+            hb = w["head_bias"]
+            _lib.check(L_.mi_decoder_step_taps(C.byref(self._gcfg), self._wtable_taps, ids_new.data_ptr(), B, beams, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc,
+                                               enc_len.data_ptr() if enc_len is not None else None, float(w["scale"]), hb.data_ptr() if hb is not None else None,
+                                               self._taps, len(taps), self._step_ws.data_ptr(), self._step_ws.numel(), buf.data_ptr(), Vp,
+                                               torch.cuda.current_stream().cuda_stream), "mi_decoder_step_taps")
+            cache["past"] = past + U
+            return buf[:, :V]
+        if beams != 1:
             _lib.check(L_.mi_decoder_step_beams(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, beams, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc,
                                                 enc_len.data_ptr() if enc_len is not None else None, float(w["scale"]), None, self._step_ws.data_ptr(),
                                                 self._step_ws.numel(), buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_decoder_step_beams")
@@ -220,12 +275,19 @@ class GPT2DecoderEngine:
         past, Lmax = cache["past"], cache["Lmax"]
         self.ensure_positions(past + U)
         x = ops.embed_tokens(ids_new, w["wte"], w["pos"], scale=w["scale"], pos_offset=past)
+        locs = w.get("taps") or []
+        last_of = lambda t: t.view(B, U, d)[:, -1].clone()             # a copy: the blocks update the stream in place
+        taps = {0: last_of(x)} if 0 in locs else {}
         for l in range(L):
             x = self._block(l, x, B, U, kvs[l], T_enc, enc_len, cache["k"][l], cache["v"][l], past, Lmax)
+            if (l + 1) in locs and l + 1 < L:
+                taps[l + 1] = last_of(x)
         cache["past"] = past + U
-        last = x.view(B, U, d)[:, -1].contiguous()
+        last = last_of(x)
         hid = torch.empty((B, d), device=self.device, dtype=BF16)
         ops.layernorm_chain(last, lna=w["lnf"], eps2=eps, outa=hid)
+        if locs:
+            return self._logits(self._head_input(taps, hid), w["head_fold"], w["head_bias"])
         return self._logits(hid, w["lm_head"])
 
 

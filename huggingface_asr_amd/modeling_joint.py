@@ -34,6 +34,19 @@ class GPT2MultiHeadConfig(GPT2Config):
         self.average_logits = average_logits
 
 
+class GPT2MultiHeadMixingConfig(GPT2Config):
+    """reference src/models/decoders/multi_head_gpt2_mixing.py:13-31 (keyword-only there as well)"""
+    model_type = "gpt2-multi-head-mixing"
+
+    def __init__(self, *args, head_locations=None, head_weights=None, tie_additional_weights=False, average_logits=False, mixing_mode="full", **kwargs):
+        super().__init__(*args, **kwargs)
+        self.head_locations = head_locations
+        self.head_weights = head_weights
+        self.tie_additional_weights = tie_additional_weights
+        self.average_logits = average_logits
+        self.mixing_mode = mixing_mode
+
+
 class JointCTCAttentionEncoderDecoderConfig(SpeechEncoderDecoderConfig):
     model_type = "joint_aed_ctc_speech-encoder-decoder"
     is_composition = True
@@ -157,7 +170,34 @@ class GPT2LMMultiHeadModel(PreTrainedModel):
                            "it has no stand-alone forward and no CPU fallback")
 
 
+class GPT2LMMultiHeadModelMixing(GPT2LMMultiHeadModel):
+    """Parameter holder of the reference's DeCRED decoder that forms its logits from ALL heads (`src/models/decoders/multi_head_gpt2_mixing.py:34-51`): the same keys
+    plus `lm_mixing` — (H,) for mode `scalar`, (H, V) for `linear`, both filled with 1 / H; `lm_mixing.weight` (V, H V) = eye(V) repeated H times * 0.5 and
+    `lm_mixing.bias` for `full`.  Inside `JointCTCAttentionEncoderDecoder` the engine folds the mix into one multi-tap head (packing.head_fold)."""
+    config_class = GPT2MultiHeadMixingConfig
+
+    def __init__(self, config):
+        super().__init__(config)
+        H, V = len(self.head_weights), config.vocab_size
+        mode = config.mixing_mode
+        if mode == "full":
+            self.lm_mixing = nn.Linear(H * V, V, bias=True)
+            self.lm_mixing.weight = nn.Parameter(torch.eye(V).repeat(1, H) * 0.5)
+            self.lm_mixing.bias.data.zero_()
+        elif mode == "linear":
+            self.lm_mixing = nn.Parameter(torch.full((H, V), 1 / H), requires_grad=True)
+        elif mode == "scalar":
+            self.lm_mixing = nn.Parameter(torch.full((H,), 1 / H), requires_grad=True)
+        else:
+            raise NotImplementedError(f"Mixing mode {mode} not implemented.")          # reference :123 (there at the first forward)
+
+
 _Decoder = GPT2LMMultiHeadModel
+
+
+def _decoder_class(cfg):
+    """the HIP parameter holder of a decoder configuration"""
+    return GPT2LMMultiHeadModelMixing if isinstance(cfg, GPT2MultiHeadMixingConfig) else GPT2LMMultiHeadModel
 
 
 def _dec_cfg_dict(c) -> dict:
@@ -165,7 +205,8 @@ def _dec_cfg_dict(c) -> dict:
                 n_positions=c.max_position_embeddings, head_locations=list(c.head_locations or []),
                 head_weights=list(c.head_weights or [1.0]), lsm_factor=getattr(c, "lsm_factor", 0.0),
                 layer_norm_epsilon=c.layer_norm_epsilon, pos_emb_fixed=bool(getattr(c, "pos_emb_fixed", False)),
-                activation_function=c.activation_function)
+                activation_function=c.activation_function, average_logits=bool(getattr(c, "average_logits", False)),
+                mixing_mode=c.mixing_mode if isinstance(c, GPT2MultiHeadMixingConfig) else None)
 
 
 class JointCTCAttentionEncoderDecoder(PreTrainedModel):
@@ -196,7 +237,7 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
         if decoder is not None and not isinstance(decoder, GPT2LMMultiHeadModel):
             raise TypeError(f"decoder must be the HIP GPT2LMMultiHeadModel, got {type(decoder)} (no PyTorch fallback)")
         self.encoder = encoder if encoder is not None else Wav2Vec2EBranchformerForCTC(config.encoder)
-        self.decoder = decoder if decoder is not None else GPT2LMMultiHeadModel(config.decoder)
+        self.decoder = decoder if decoder is not None else _decoder_class(config.decoder)(config.decoder)
         self.encoder.config = self.config.encoder
         self.decoder.config = self.config.decoder
         self.encoder_output_dim = getattr(config.encoder, "output_hidden_size", config.encoder.hidden_size)
@@ -221,6 +262,20 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
 
     def _init_weights(self, module):
         pass
+
+    def __setattr__(self, name, value):
+        """`model.decoder = new_decoder` (the reference's `instantiate_aed_model` swaps the mixing decoder in this way, model_utils.py:205-213): only a HIP decoder may
+        take the place, and the joint configuration follows it — so that the engine is built for the decoder that is there and a saved checkpoint loads as what it is"""
+        if name == "decoder" and isinstance(value, nn.Module) and "_modules" in self.__dict__ and "decoder" in self._modules:
+            if not isinstance(value, GPT2LMMultiHeadModel):
+                raise TypeError(f"decoder must be the HIP GPT2LMMultiHeadModel, got {type(value)} (no PyTorch fallback)")
+            super().__setattr__(name, value)
+            if value.config is not self.config.decoder:
+                self.config.decoder = value.config
+                if not hasattr(value.config, "lsm_factor"):
+                    value.config.lsm_factor = self.lsm_factor
+            return
+        super().__setattr__(name, value)
 
     @classmethod
     def from_encoder_decoder_pretrained(cls, encoder_pretrained_model_name_or_path=None, decoder_pretrained_model_name_or_path=None, *model_args, **kwargs):
@@ -254,9 +309,9 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
                 dec_cfg.is_decoder = True
                 dec_cfg.add_cross_attention = True
                 kw_dec["config"] = dec_cfg
-            if not isinstance(kw_dec["config"], GPT2MultiHeadConfig):
+            if not isinstance(kw_dec["config"], (GPT2MultiHeadConfig, GPT2MultiHeadMixingConfig)):
                 raise ValueError(f"decoder config {type(kw_dec['config'])} is not a GPT2MultiHeadConfig: only the multi-head GPT-2 decoder has a HIP implementation")
-            decoder = GPT2LMMultiHeadModel.from_pretrained(decoder_pretrained_model_name_or_path, **kw_dec)
+            decoder = _decoder_class(kw_dec["config"]).from_pretrained(decoder_pretrained_model_name_or_path, **kw_dec)
         config = JointCTCAttentionEncoderDecoderConfig.from_encoder_decoder_configs(encoder.config, decoder.config, **kwargs)
         config.tie_word_embeddings = False
         return cls(encoder=encoder, decoder=decoder, config=config)
@@ -271,10 +326,11 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
         self.encoder.freeze_feature_encoder()
 
     def _get_engine(self, device) -> JointAEDEngine:
-        if self._engine is None or self._engine.device != torch.device(device):
+        dc = _dec_cfg_dict(self.decoder.config)           # the decoder that is there NOW: the module may have been replaced after construction (`__setattr__`)
+        if self._engine is None or self._engine.device != torch.device(device) or self._engine.dec.cfg != dc:
             jc = dict(ctc_weight=self.config.ctc_weight, pad_token_id=self.config.pad_token_id,
                       decoder_start_token_id=self.config.decoder_start_token_id)
-            self._engine = JointAEDEngine(cfg_from_hf(self.config.encoder), _dec_cfg_dict(self.config.decoder), jc, device)
+            self._engine = JointAEDEngine(cfg_from_hf(self.config.encoder), dc, jc, device)
             self._engine_key = None
         from .autograd_bridge import bridge_generation
         key = (sum(p._version for p in self.parameters()), bridge_generation(self), tuple(p.data_ptr() for p in self.parameters()))
@@ -285,10 +341,11 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
 
     def _get_trainer(self, device):
         from .train_aed import JointAEDTrainer
-        if getattr(self, "_trainer", None) is None or self._trainer.device != torch.device(device):
+        if getattr(self, "_trainer", None) is None or self._trainer.device != torch.device(device) or self.__dict__.get("_trainer_decoder") is not self.decoder:
+            object.__setattr__(self, "_trainer_decoder", self.decoder)          # (the decoder module may have been replaced after construction)
             jc = dict(ctc_weight=self.config.ctc_weight, pad_token_id=self.config.pad_token_id,
                       decoder_start_token_id=self.config.decoder_start_token_id)
-            dc = dict(_dec_cfg_dict(self.config.decoder), tie_word_embeddings=False,
+            dc = dict(_dec_cfg_dict(self.decoder.config), tie_word_embeddings=False,
                       resid_pdrop=getattr(self.config.decoder, "resid_pdrop", 0.0), embd_pdrop=getattr(self.config.decoder, "embd_pdrop", 0.0),
                       attn_pdrop=getattr(self.config.decoder, "attn_pdrop", 0.0))
             self._trainer = JointAEDTrainer(cfg_from_hf(self.config.encoder), dc, jc, device, with_proj=hasattr(self, "enc_to_dec_proj"), dp_sync=False, seed=_dropout_seed())
@@ -308,6 +365,8 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
                 past_key_values=None, decoder_inputs_embeds=None, labels=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, input_values=None, input_features=None, return_dict=None, **kwargs):
         training = self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if training and isinstance(self.decoder, GPT2LMMultiHeadModelMixing):
+            return self._forward_mixing_finetune(self._pick_inputs(inputs, input_values, input_features), attention_mask, labels)
         if labels is None or decoder_input_ids is not None or encoder_outputs is not None or decoder_inputs_embeds is not None:
             raise NotImplementedError("HIP joint forward implements the teacher-forced path driven by `labels` (reference :303-304); "
                                       "use generate() for decoding")
@@ -341,6 +400,41 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
             out = self._get_engine(inputs.device).forward(inputs, fl, labels.to(inputs.device))
         B, T2 = out["encoder_logits"].shape[:2]
         return Seq2SeqLMOutputLosses(loss=out["loss"], enc_loss=out["enc_loss"], dec_loss=out["dec_loss"], logits=out["logits"],
+                                     encoder_last_hidden_state=out["encoder_hidden"].view(B, T2, -1), encoder_logits=out["encoder_logits"])
+
+    def _forward_mixing_finetune(self, inputs, attention_mask, labels):
+        """Training-mode forward of a mixing decoder (`--finetune_mixing_mechanism`, model_utils.py:205-217: every parameter frozen except `lm_mixing`): the frozen body
+        runs the trainer's forward stages only (train_aed.forward_heads, under the configuration's dropouts), the loss of the mixed logits and `d lm_mixing` come from
+        mi_mix_ce behind a small autograd.Function — torch's optimizer in HF `Trainer` then steps `lm_mixing` as any parameter."""
+        mode = self.decoder.config.mixing_mode
+        extra = [n for n, p in self.named_parameters() if p.requires_grad and "lm_mixing" not in n]
+        if extra:
+            raise NotImplementedError(f"JointCTCAttentionEncoderDecoder (HIP): mixing fine-tuning trains `lm_mixing` alone, as model_utils.py:214-217 freezes every other "
+                                      f"parameter; {len(extra)} others require grad (first: {extra[0]})")
+        if mode == "full":
+            raise NotImplementedError("JointCTCAttentionEncoderDecoder (HIP): training the `full` mixing mode (a (V, H V) weight gradient) is not implemented; no recipe "
+                                      "uses it — `linear` and `scalar` train")
+        if labels is None:
+            raise NotImplementedError("HIP joint forward implements the teacher-forced path driven by `labels`")
+        if not inputs.is_cuda:
+            raise RuntimeError("JointCTCAttentionEncoderDecoder (HIP): inputs must be on the GPU; there is no CPU fallback")
+        if labels.max() >= self.config.encoder.vocab_size:
+            raise ValueError(f"Label values must be <= vocab_size: {self.config.encoder.vocab_size}")
+        from .ops_train import MixCE
+        dev = inputs.device
+        tr = self._get_trainer(dev)
+        frozen = [(n, p) for n, p in self.named_parameters() if "lm_mixing" not in n]
+        key = tuple((p.data_ptr(), p._version) for _, p in frozen)
+        if getattr(self, "_mix_trainer_key", None) != key:         # the frozen body is loaded once; `lm_mixing` itself goes to the kernel as the live parameter
+            tr.load_state_dict(dict(self.state_dict()))
+            object.__setattr__(self, "_mix_trainer_key", key)
+        fl = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        labels = labels.to(dev)
+        out = tr.forward_heads(inputs, fl, labels)
+        dec_loss = MixCE.apply(self.decoder.lm_mixing, out["head_logits"], labels, int(self.decoder.config.vocab_size))
+        w = self.config.ctc_weight
+        B, T2 = out["encoder_logits"].shape[:2]
+        return Seq2SeqLMOutputLosses(loss=w * out["enc_loss"] + (1 - w) * dec_loss, enc_loss=out["enc_loss"], dec_loss=dec_loss, logits=None,
                                      encoder_last_hidden_state=out["encoder_hidden"].view(B, T2, -1), encoder_logits=out["encoder_logits"])
 
     # generation options that change the decoding and that the HIP loop does not implement: name -> the values that leave them off

@@ -903,3 +903,48 @@ def linear_bwd(dy, x, wT, *, dw=None, db=None, dx_out=None, dx_dtype=BF16, need_
     elif db is not None:
         colsum_(db, dy)
     return dx
+
+
+# ---------------------------------------------------------------------------------------------------------------- mixing fine-tuning (csrc/mix_loss.hip)
+def mix_ce_fwd(head_logits, mix, labels, V):
+    """head_logits (H, B, U, ld) fp32: the H per-head logit matrices (columns [V, ld) padding); mix (H,) fp32 (mode scalar) or (H, V) (mode linear); labels (B, U) int64
+    (shift 1, ignore < 0) -> (acc [sum of the valid rows' losses, their count], lse (B*U)) of the cross-entropy of the mixed logits sum_h mix[h, v] L_h (mi_mix_ce_fwd)."""
+    _req(head_logits, torch.float32); _req(mix, torch.float32); _req(labels, torch.int64)
+    H, B, U, ld = head_logits.shape
+    if not head_logits.is_contiguous() or not mix.is_contiguous() or tuple(mix.shape) not in ((H,), (H, V)):
+        raise ValueError(f"mix_ce: contiguous head logits (H, B, U, ld) and a contiguous mixing parameter (H,) or (H, V); got {tuple(head_logits.shape)}, {tuple(mix.shape)}")
+    labels = labels.contiguous()
+    dev = head_logits.device
+    lse, rows, acc = (torch.empty(n, device=dev, dtype=torch.float32) for n in (B * U, B * U, 2))
+    _lib.check(_L().mi_mix_ce_fwd(head_logits.data_ptr(), ld, head_logits.stride(0), H, mix.data_ptr(), int(mix.dim() == 2), labels.data_ptr(), B, U, V,
+                                  lse.data_ptr(), rows.data_ptr(), acc.data_ptr(), _stream()), "mi_mix_ce_fwd")
+    return acc, lse
+
+
+def mix_ce_bwd(head_logits, mix, labels, V, acc, lse):
+    """d (acc[0] / acc[1]) / d mix, in mix's shape, from what `mix_ce_fwd` left (mi_mix_ce_bwd: rows in fixed chunks, partials in chunk order — bit-reproducible)"""
+    H, B, U, ld = head_logits.shape
+    labels = labels.contiguous()
+    n = _L().mi_mix_ce_bwd_workspace_floats(B * U, H, V)
+    ws = torch.empty(n, device=head_logits.device, dtype=torch.float32)
+    dmix = torch.empty_like(mix)
+    _lib.check(_L().mi_mix_ce_bwd(head_logits.data_ptr(), ld, head_logits.stride(0), H, mix.data_ptr(), int(mix.dim() == 2), labels.data_ptr(), B, U, V,
+                                  lse.data_ptr(), acc.data_ptr(), ws.data_ptr(), n, dmix.data_ptr(), _stream()), "mi_mix_ce_bwd")
+    return dmix
+
+
+class MixCE(torch.autograd.Function):
+    """loss = mean cross-entropy of the mixed logits; the only differentiable input is the mixing parameter (the per-head logits come from the frozen body)"""
+
+    @staticmethod
+    def forward(ctx, mix, head_logits, labels, V):
+        m = mix.detach().contiguous()
+        acc, lse = mix_ce_fwd(head_logits, m, labels, V)
+        ctx.save_for_backward(m, head_logits, labels, acc, lse)
+        ctx.V = V
+        return acc[0] / acc[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        m, head_logits, labels, acc, lse = ctx.saved_tensors
+        return mix_ce_bwd(head_logits, m, labels, ctx.V, acc, lse) * g, None, None, None

@@ -216,6 +216,16 @@ def decoder_specs(c: dict, enc_dim: int, with_proj: bool) -> list[Spec]:
         mat("lm_head", V, d)
     for k in range(len(c.get("head_locations") or [])):
         mat(f"head{k}", V, d)
+    H = len(c.get("head_locations") or []) + 1
+    mode = c.get("mixing_mode")                            # GPT2LMMultiHeadModelMixing (multi_head_gpt2_mixing.py:39-51): fp32, folded into the head by `head_fold`
+    if mode == "scalar":
+        vec("mix", H, decay=True)
+    elif mode == "linear":
+        vec("mix", H, V, decay=True)
+    elif mode == "full":
+        vec("mix_w", V, H * V, decay=True); vec("mix_b", V)
+    elif mode is not None:
+        raise NotImplementedError(f"Mixing mode {mode} not implemented.")
     return S
 
 
@@ -249,7 +259,48 @@ def _dec_map(c: dict, with_proj: bool, prefix="decoder."):
         one("lm_head", prefix + "lm_head.weight")
     for k in range(len(c.get("head_locations") or [])):
         one(f"head{k}", f"{prefix}additional_lm_heads.{k}.weight")
+    if c.get("mixing_mode") in ("scalar", "linear"):
+        one("mix", prefix + "lm_mixing")
+    elif c.get("mixing_mode") == "full":
+        one("mix_w", prefix + "lm_mixing.weight"); one("mix_b", prefix + "lm_mixing.bias")
     return m
+
+
+def head_taps(c: dict) -> list:
+    """where the heads of a multi-head decoder read the stream, additional heads first, `lm_head` last — transformers' `hidden_states` index: 0 the embedding output,
+    l the residual stream after l blocks (no LayerNorm), n_layer ln_f of the last block's output (multi_head_gpt2.py:143-148)"""
+    L = c["n_layer"]
+    locs = [int(l) for l in (c.get("head_locations") or [])]
+    bad = [l for l in locs if not 0 <= l <= L]
+    if bad:
+        raise ValueError(f"head_locations {bad} outside [0, n_layer = {L}]")
+    return locs + [L]
+
+
+def mixes_heads(c: dict) -> bool:
+    """does decoding read more than `lm_head`?  Every mixing mode, and `average_logits` with additional heads (multi_head_gpt2.py:129-136)"""
+    return c.get("mixing_mode") is not None or (bool(c.get("average_logits", False)) and bool(c.get("head_locations")))
+
+
+def head_fold(c: dict, heads: list, mix: dict):
+    """Every way the reference forms decode-time logits from several heads is  logits = sum_h A_h hidden[loc_h] (+ b):  -> (the folded head [A_0 | ... | A_{H-1}] of shape
+    (V, H d), b (V) or None), in the precision of its inputs (the engine passes fp32 and rounds the result to bf16 once).  `heads`: the H head matrices (V, d) in
+    `head_taps` order; `mix`: "mix" (scalar (H,) / linear (H, V)) or "mix_w" (V, H V) + "mix_b" (V) of GPT2LMMultiHeadModelMixing:
+      scalar / linear  logits = sum_h mix[h, v] head_h(.)            -> A_h = rows of W_h scaled by mix[h, v]          (multi_head_gpt2_mixing.py:111-121)
+      full             logits = W_mix [head_0(.) | ...] + b_mix      -> A_h = W_mix[:, hV:(h+1)V] W_h, b = b_mix      (:101-110)
+      average_logits   logits = sum_h head_weights[h] head_h(.)      -> A_h = head_weights[h] W_h                     (multi_head_gpt2.py:129-136)"""
+    H, V = len(heads), heads[0].shape[0]
+    mode = c.get("mixing_mode")
+    if mode == "scalar":
+        return torch.cat([mix["mix"][h] * heads[h] for h in range(H)], 1), None
+    if mode == "linear":
+        return torch.cat([mix["mix"][h][:, None] * heads[h] for h in range(H)], 1), None
+    if mode == "full":
+        return torch.cat([mix["mix_w"][:, h * V:(h + 1) * V] @ heads[h] for h in range(H)], 1), mix["mix_b"]
+    if mode is not None:
+        raise NotImplementedError(f"Mixing mode {mode} not implemented.")
+    hw = list(c.get("head_weights") or [1.0])
+    return torch.cat([float(hw[h]) * heads[h] for h in range(H)], 1), None
 
 
 # ====================================================================================================== GPT-2 language model parameters (shallow fusion)

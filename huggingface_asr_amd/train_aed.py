@@ -263,6 +263,31 @@ class JointAEDTrainer(ZeroCopyTrainer):
         self.sync.launch(0, self.store.n)
         return dh
 
+    # ------------------------------------------------------------------ mixing fine-tuning: the frozen body, forward stages only
+    def forward_heads(self, feats, feat_lengths, labels):
+        """The forward stages alone, in training mode (the dropouts of the configuration), no backward: what the mixing fine-tuning of the DeCRED decoder needs of the
+        frozen model (model_utils.py:214-217 freezes everything but `lm_mixing`).  -> dict(enc_loss, encoder_logits, encoder_hidden, head_logits (H, B, U, Vp) f32: the
+        logits of every head in `packing.head_taps` order, columns [V, Vp) padding)"""
+        with ops.pinned_stream():
+            labels = labels.contiguous()
+            B = feats.shape[0]
+            eo = self.enc._forward_backward(feats, feat_lengths, labels, backward=False, train_mode=True, keep_hidden=True)
+            T2 = eo["last_hidden"].shape[1]
+            key_len = torch.clamp(eo["outer_len"], max=T2) if feat_lengths is not None else None
+            x, sp = self._embed_fwd(eo["last_hidden"].reshape(B * T2, -1), B, T2, key_len, labels, 1.0)
+            taps = {0: x} if 0 in self.locs else {}
+            for l in range(self.L):
+                x, _ = self._layer_fwd(x, l, sp)
+                if (l + 1) in self.locs and l + 1 < self.L:
+                    taps[l + 1] = x
+            hid = self._e16(sp.M, self.d)
+            ops.layernorm_chain(x, lna=(self.store.p("lnf_g"), self.store.p("lnf_b")), eps2=self.eps, outa=hid)
+            names = [f"head{k}" for k in range(len(self.locs))] + [self.lm_name]
+            buf = torch.empty((len(names), sp.B, sp.U, self.Vp), device=self.device, dtype=F32)
+            for h, (loc, name) in enumerate(zip(self.locs + [self.L], names)):
+                ops.gemm(ops.cast_bf16(taps[loc]) if loc in taps else hid, self.store.bf(name), None, out=buf[h].view(sp.M, self.Vp))
+            return dict(enc_loss=eo["loss"], encoder_logits=eo["logits"], encoder_hidden=sp.enc_bf, head_logits=buf)
+
     # ------------------------------------------------------------------ step
     def forward_backward(self, feats, feat_lengths, labels):
         with ops.pinned_stream():

@@ -523,6 +523,16 @@ int mi_ctc_loss_bwd_nll(const void* logits, long ld_b, long ld_t, int dtype, con
 int mi_ctc_reduce(const float* nll, const int* tgt_len, int B, int reduction, int zero_infinity, float* loss, mi_stream_t stream);
 int mi_ce_label_smoothing_bwd(const float* logits, long ld, const long* labels, int B, int U, int shift, int V, float eps,
                               float weight, const float* acc, void* dlogits, long ldo, mi_stream_t stream);
+/* ---- mixing fine-tuning of the DeCRED decoder (csrc/mix_loss.hip; multi_head_gpt2_mixing.py:111-131, modes scalar / linear): the mean unsmoothed cross-entropy of
+ * z[r, v] = sum_h mix[h, v] L_h[r, v] against labels shifted by one (ignore < 0), and d mix, from the H per-head fp32 logit matrices (head h, row r, column v at
+ * logits[h * head_stride + r * ld + v]; columns [V, ld) are never read).  mix: (H, V) when mix_per_col, else (H); 1 <= H <= 8.  Neither z nor its gradient is
+ * materialised.  fwd: lse (M), row_loss (M) workspace, acc[0] = sum of the valid rows' losses, acc[1] = their count.  bwd: d mix of acc[0] / acc[1] from fwd's lse / acc;
+ * rows reduced in fixed chunks, partials added in chunk order — no float atomics, bit-reproducible. */
+int mi_mix_ce_fwd(const float* logits, long ld, long head_stride, int H, const float* mix, int mix_per_col, const long* labels, int B, int U, int V,
+                  float* lse, float* row_loss, float* acc, mi_stream_t stream);
+size_t mi_mix_ce_bwd_workspace_floats(int M, int H, int V);
+int mi_mix_ce_bwd(const float* logits, long ld, long head_stride, int H, const float* mix, int mix_per_col, const long* labels, int B, int U, int V,
+                  const float* lse, const float* acc, float* workspace, size_t workspace_floats, float* dmix, mi_stream_t stream);
 /* as gathers (a block per 16 vocabulary entries / per position adds its rows in order: no atomics).  heavy_id: an entry expected on a large share of the rows (the padding
  * token of the shifted decoder input) is summed as a masked column sum instead, or -1; workspace: mi_embed_tokens_bwd_workspace_bytes(M, d, V) bytes; d <= 1024 */
 size_t mi_embed_tokens_bwd_workspace_bytes(int M, int d, int V);
@@ -575,6 +585,16 @@ int mi_decoder_step(const mi_gpt2_config* cfg, const void* const* weights, const
 int mi_decoder_step_beams(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
                           void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
                           const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
+/* mi_decoder_step_beams with a multi-tap head: logits = sum_h A_h hidden[taps[h]] (+ head_bias) as one head GEMM with K = n_taps * d.  Serves the reference's
+ * GPT2LMMultiHeadModelMixing (multi_head_gpt2_mixing.py:101-121, all three mixing modes) and `average_logits` of GPT2LMMultiHeadModel (multi_head_gpt2.py:129-136), whose
+ * mixing parameters the engine folds into the head at load time.  weights[4] is the folded head (V, n_taps * d) bf16; taps (n_taps ints in HOST memory, 1 <= n_taps <= 8):
+ * 0 = the embedding output, l = the residual stream after l blocks (no LayerNorm), L = ln_f of the last block's output — transformers' `hidden_states[l]`.  Column block h
+ * of the head's input row is the bf16-rounded stream of tap h at the last new position.  Workspace: mi_decoder_step_taps_workspace_bytes.  At <= 8 rows the step runs
+ * its GEMV form (while n_taps * d <= 2048, the GEMV kernel's K; beyond it one launch per op) whatever step_form says (the fused form keeps a layer's stream inside its launches); beams as in mi_decoder_step_beams. */
+size_t mi_decoder_step_taps_workspace_bytes(const mi_gpt2_config* cfg, int B, int U, int n_taps);
+int mi_decoder_step_taps(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                         void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
+                         const float* head_bias, const int* taps, int n_taps, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
 /* Rows-streaming linear (csrc/linear_rows.hip): y = act(x W^T + b) for 1 <= M <= 64 rows, any N, K % 8 == 0; x (M, K) and W (N, K) bf16, 16-B aligned, ldx % 8 == ldw % 8 == 0.
  * act 0 none / 1 erf-GELU / 2 gelu_new.  Exactly one of out32 / out16: out32 (M, ldo32) fp32 = y, or out32 += y when accumulate (the in-place residual add); out16 (M, ldo16)
  * bf16, and with kcache != NULL (N == 3 dkv, M % U == 0) columns [dkv, 2 dkv) / [2 dkv, 3 dkv) of row m = b U + u also go to kcache / vcache (.., Lmax, dkv) at row
