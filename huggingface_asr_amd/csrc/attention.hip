@@ -1371,6 +1371,7 @@ extern "C" int mi_attention_qkv_bf16(const void* q, long ldq, const void* k, lon
     MI_ENTER();
     if (B <= 0 || T <= 0 || H <= 0 || Tk < 0) return MI_ERR_ARG;
     if (pos && Tk != 0 && Tk != T) return MI_ERR_ARG;                    // the relative term needs a square score matrix
+    if (causal && Tk != 0 && Tk < T) return MI_ERR_ARG;                  // the first T - Tk queries would see no key at all: their rows are 0 / 0
     if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;                 // 16-B row stores
     if (ldq >= (1l << 30)) return MI_ERR_ARG;
     if (ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldp >= (1l << 30)) return MI_ERR_ARG;      // the kernel keeps row strides as 32-bit byte counts
@@ -1395,6 +1396,7 @@ extern "C" int mi_attention_qkv_bf16_v(const void* q, long ldq, const void* k, l
     MI_ENTER();
     if (B <= 0 || T <= 0 || H <= 0 || Tk < 0 || variant < 0 || variant > 2) return MI_ERR_ARG;
     if (pos && Tk != 0 && Tk != T) return MI_ERR_ARG;
+    if (causal && Tk != 0 && Tk < T) return MI_ERR_ARG;
     if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;
     if (ldq >= (1l << 30)) return MI_ERR_ARG;
     if (ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldp >= (1l << 30)) return MI_ERR_ARG;
@@ -1514,6 +1516,7 @@ extern "C" int mi_attention_x_lse_bf16(const void* q, long ldq, const void* k, l
                                        int B, int Tq, int Tk, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
     MI_ENTER();
     if (B <= 0 || Tq <= 0 || Tk <= 0 || H <= 0 || !lse || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
+    if (causal && Tk < Tq) return MI_ERR_ARG;                            // queries without a visible key (see mi_attention_qkv_bf16)
     if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;
     if (ldq >= (1l << 30) || ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30)) return MI_ERR_ARG;
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15)) return MI_ERR_ARG;
@@ -1530,6 +1533,7 @@ extern "C" int mi_attention_x_bwd_probs(const void* q, long ldq, const void* k, 
                                         int B, int Tq, int Tk, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
     MI_ENTER();
     if (B <= 0 || Tq <= 0 || Tk <= 0 || H <= 0 || !lse || !ctx || !dctx || !prob || !ds || !dq || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
+    if (causal && Tk < Tq) return MI_ERR_ARG;
     if ((lddq % 8) || lddq >= (1l << 30) || ((uintptr_t)dq & 15)) return MI_ERR_ARG;
     if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || (ldd % 8)) return MI_ERR_ARG;
     if (ldq >= (1l << 30) || ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldo >= (1l << 30) || ldd >= (1l << 30)) return MI_ERR_ARG;

@@ -250,13 +250,20 @@ def attention_qkv(qkv, B, T, H, *, pos=None, bias_u=None, bias_v=None, lengths=N
     return out
 
 
-def attention_general(q, k, v, B, Tq, Tk, H, *, lengths=None, causal=False, out=None, kv_bstride=0):
+def attention_general(q, k, v, B, Tq, Tk, H, *, lengths=None, causal=False, out=None, kv_bstride=0, variant=0):
     """q (B*Tq, .) / k, v (B*Tk, .) bf16 row views with head h at columns [h*hd, (h+1)*hd) -> context (B*Tq, d) bf16.
-    Cross-attention (Tk = encoder frames, `lengths` = valid keys) and KV-cache steps (causal offset Tk - Tq)."""
+    Cross-attention (Tk = encoder frames, `lengths` = valid keys) and KV-cache steps (causal offset Tk - Tq).
+    variant: as in `attention_qkv` (1 = the four-wave kernel, 2 = the eight-wave form; tests and measurements only)."""
     d = q.shape[1]
     hd = d // H
     if out is None:
         out = torch.empty((B * Tq, d), device=q.device, dtype=BF16)
+    if variant:
+        rc = _lib.lib().mi_attention_qkv_bf16_v(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                                0, 0, 0, 0, _p(lengths), out.data_ptr(), out.stride(0), B, Tq, Tk, kv_bstride, H, hd,
+                                                1.0 / math.sqrt(hd), int(causal), int(variant), _stream())
+        _lib.check(rc, "mi_attention_qkv_bf16_v")
+        return out
     rc = _lib.lib().mi_attention_qkv_bf16(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
                                           0, 0, 0, 0, _p(lengths), out.data_ptr(), out.stride(0), B, Tq, Tk, kv_bstride, H, hd,
                                           1.0 / math.sqrt(hd), int(causal), _stream())

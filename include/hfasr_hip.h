@@ -149,14 +149,15 @@ int mi_attention_qkv_bf16(const void* q, long ldq, const void* k, long ldk, cons
                           const int* lengths, void* out, long ldo, int B, int T, int Tk, long kv_bstride, int H, int hd,
                           float scale, int causal, mi_stream_t stream);
 /* A/B form of mi_attention_qkv_bf16: variant 0 = the library's choice (the eight-wave kernel: two waves per SIMD, the wave pair of a query group splits the keys),
- * except with relative positions at head size 64), 1 = the four-wave kernel of rounds 1-3, 2 = the eight-wave kernel.  Measurement only (tools/attn_ab.py); no product call
- * site passes a non-zero variant. */
+ * except with relative positions at head size 64), 1 = the four-wave kernel of rounds 1-3, 2 = the eight-wave kernel.  Measurement (tools/attn_ab.py) and tests (tests/test_gpu_attention_probes.py) only; no product
+ * call site passes a non-zero variant. */
 int mi_attention_qkv_bf16_v(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
                             const void* pos, long ldp, const float* bias_u, const float* bias_v,
                             const int* lengths, void* out, long ldo, int B, int T, int Tk, long kv_bstride, int H, int hd,
                             float scale, int causal, int variant, mi_stream_t stream);
 /* (kv_bstride = elements between batches of k/v, 0 = Tk*ld (KV caches are (B, Lmax, d)); T = queries per batch, Tk = keys per batch, 0 = T: cross-attention over encoder frames and KV-cache decoding use Tk != T;
- *  with causal != 0 query i sees keys <= i + (Tk - T).) */
+ *  with causal != 0 query i sees keys <= i + (Tk - T); causal with 0 < Tk < T leaves the first queries without a key and is MI_ERR_ARG, here and in the
+ *  mi_attention_x_* entries below.) */
 
 /* Training form of the above (self-attention only, Tk = T): also leaves each row's log-sum-exp of the scaled scores (log2 domain) in lse (B, H, T) fp32,
  * which mi_attention_qkv_bwd_probs needs.  replaces: the forward half of Wav2Vec2EBranchformerSelfAttention under autograd, e_branchformer.py:105-138. */
