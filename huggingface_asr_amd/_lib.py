@@ -63,11 +63,7 @@ SIGNATURES = {
     "mi_attention_x_bwd_probs": [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, f32, i32, f32, C.c_uint, C.c_uint, vp],
     "mi_attention_qkv_lse_bf16": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i32, i32, i32, i32, f32, i32, f32, C.c_uint, C.c_uint, vp],
     "mi_attention_qkv_bwd_probs": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i32,
-                                   vp, i64, vp, vp, i32, i32, i32, i32, f32, i32, f32, C.c_uint, C.c_uint, vp],
-    "mi_attention_qkv_bwd_probs_qb": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i32,
-                                      vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, f32, C.c_uint, C.c_uint, vp],
-    "mi_attention_qkv_bwd_probs_f": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, i64, vp, vp, vp, i64, vp, i64, i32,
-                                     vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, f32, C.c_uint, C.c_uint, i32, vp],
+                                   vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, f32, C.c_uint, C.c_uint, i32, vp],
     "mi_attention_qkv_bwd_fused": [vp, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, i64, vp, sz, i32, i32, i32, i32, f32, vp],
     "mi_row_stats_bf16": [vp, i64, i32, f32, vp, i32, vp],
     "mi_csgu_bf16": [vp, i64, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, vp],
@@ -92,7 +88,6 @@ SIGNATURES = {
     "mi_ctc_loss_fwd": [vp, i64, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp],
     "mi_ctc_prefix_prepare": [vp, i64, i64, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
     "mi_ctc_prefix_score": [vp, i32, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, vp, vp],
-    "mi_ctc_prefix_select": [vp, i32, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp],
     "mi_embed_tokens": [vp, vp, f32, vp, i32, i32, i32, i32, i32, vp, vp],
     "mi_ce_label_smoothing": [vp, i64, vp, i32, i32, i32, i32, f32, vp, vp, vp],
     "mi_whisper_logmel": [vp, i64, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp],
@@ -111,7 +106,6 @@ SIGNATURES = {
     "mi_layernorm_bwd_dual_partial": [vp, i64, i32, f32, vp, vp, i64, i32, vp, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, vp, i64, f32, f32, C.c_uint, C.c_uint, i32, i32, vp],
     "mi_layernorm_bwd_partial_cast": [vp, i64, i32, vp, f32, vp, i64, i32, vp, i64, i32, i32, vp, vp, vp, i64, f32, f32, C.c_uint, C.c_uint, i32, i32, vp],
     "mi_ln_partial_reduce_many": [vp, i32, vp],
-    "mi_ln_apply_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, i32, vp],
     "mi_axpy_f32": [vp, vp, i64, f32, vp],
     "mi_scale_f32": [vp, i64, f32, vp],
     "mi_scale_dev_f32": [vp, i64, vp, vp],
@@ -120,7 +114,6 @@ SIGNATURES = {
     "mi_colsum2_acc_f32": [vp, vp, i64, i32, i32, vp, vp, vp],
     "mi_colsum_cast_bf16": [vp, i64, i32, i32, vp, vp],
     "mi_add_rowvec2_bf16": [vp, i64, vp, vp, vp, vp, i64, i32, i32, vp],
-    "mi_gate_bwd_bf16": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, vp],
     "mi_subsampled_lengths_i32": [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp],
     "mi_mask_rows_f32": [vp, i64, vp, i32, i32, i32, vp],
     "mi_spec_mask_apply": [vp, i64, vp, vp, vp, i32, i32, i32, vp],

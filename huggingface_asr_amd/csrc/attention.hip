@@ -1339,6 +1339,64 @@ int launch_hd(const AttnArgs& a, bool rel, hipStream_t stream) {
     return MI_OK;
 }
 
+// ---- host side of the C entries below: AttnArgs is filled by name, the argument checks and the head-size dispatch are written once ----
+
+// The operands every forward has (the LDS-staged kernels take V row-major in the `vt` slot).  Tk = 0: as many keys as queries; kv_bstride = 0: Tk * ld.
+AttnArgs forward_args(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* pos, long ldp, const float* bias_u, const float* bias_v,
+                      const int* lengths, void* out, long ldo, int B, int T, int Tk, long kv_bstride, int H, float scale, int causal) {
+    AttnArgs a{};
+    a.q = (const bf16_t*)q; a.ldq = ldq;
+    a.k = (const bf16_t*)k; a.ldk = ldk;
+    a.vt = (const bf16_t*)v; a.ldvt = ldv;
+    a.pos = (const bf16_t*)pos; a.ldp = ldp;
+    a.bias_u = bias_u; a.bias_v = bias_v;
+    a.lengths = lengths;
+    a.out = (bf16_t*)out; a.ldo = ldo;
+    a.B = B; a.T = T; a.H = H;
+    a.scale = scale; a.causal = causal;
+    a.Tk = Tk; a.kv_bstride = kv_bstride;
+    return a;
+}
+
+void set_dropout(AttnArgs& a, float drop_p, unsigned seed, unsigned stream_id) {
+    a.drop_p = drop_p;
+    a.drop_key = ((unsigned long long)stream_id << 32) ^ (unsigned long long)seed;
+}
+
+// Adds the backward walk's operands to `a`, whose `out` is the forward's context (read).
+void add_backward_args(AttnArgs& a, const void* dctx, long ldd, const float* lse, void* prob, void* ds, long ldsr, void* dq, long lddq) {
+    a.lse = const_cast<float*>(lse);
+    a.dctx = (const bf16_t*)dctx; a.ldd = ldd;
+    a.prob = (bf16_t*)prob; a.ds = (bf16_t*)ds; a.ldsr = ldsr;
+    a.dq = (bf16_t*)dq; a.lddq = lddq;
+}
+
+inline bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+constexpr long LD_END = 1l << 30;     // the kernels keep row strides as 32-bit byte counts
+
+// What every LDS-staged entry requires of the forward operands (16-B row loads and stores).  ldq and ldo may be <= 0, and ldp is bounded without positions too: as the
+// entries always had it.
+bool forward_args_ok(const AttnArgs& a) {
+    if (a.B <= 0 || a.T <= 0 || a.H <= 0 || a.Tk < 0) return false;
+    if (a.pos && a.Tk != 0 && a.Tk != a.T) return false;                 // the relative term needs a square score matrix
+    if (a.causal && a.Tk != 0 && a.Tk < a.T) return false;               // the first T - Tk queries would see no key at all: their rows are 0 / 0
+    if ((a.ldq % 8) || (a.ldk % 8) || (a.ldvt % 8) || (a.ldo % 8) || (a.kv_bstride % 8)) return false;
+    if (misaligned16(a.q) || misaligned16(a.k) || misaligned16(a.vt) || misaligned16(a.out)) return false;
+    if (a.ldq >= LD_END || a.ldk <= 0 || a.ldvt <= 0 || a.ldk >= LD_END || a.ldvt >= LD_END || a.ldp >= LD_END) return false;
+    if (a.pos && ((a.ldp % 8) || misaligned16(a.pos) || !a.bias_u || !a.bias_v)) return false;
+    return true;
+}
+
+// ... and of the backward operands both walks share (dbd is null without relative positions); ldsr covers the keys rounded up to 32.
+bool backward_args_ok(const AttnArgs& a) {
+    if (!forward_args_ok(a)) return false;
+    if (!a.out || !a.dctx || !a.prob || !a.ds || !a.dq) return false;
+    if ((a.ldd % 8) || (a.lddq % 8) || a.ldo >= LD_END || a.ldd >= LD_END || a.lddq >= LD_END) return false;
+    if (misaligned16(a.dctx) || misaligned16(a.prob) || misaligned16(a.ds) || misaligned16(a.dbd) || misaligned16(a.dq)) return false;
+    const int keys = a.Tk ? a.Tk : a.T;
+    return (a.ldsr % 32) == 0 && a.ldsr >= (keys + 31) / 32 * 32;
+}
+
 }  // namespace
 
 // q,k: (B*T, ld) bf16 ; vt: (H*hd, ldvt) bf16 with column b*Tp + t (Tp >= T rounded up to 32, zero padded);
@@ -1351,8 +1409,8 @@ extern "C" int mi_attention_bf16(const void* q, long ldq, const void* k, long ld
     if (B <= 0 || T <= 0 || H <= 0) return MI_ERR_ARG;
     if ((ldq % 8) || (ldk % 8) || (ldvt % 4) || (Tp % 32) || Tp < T || (ldo % 4)) return MI_ERR_ARG;
     if (pos && ((ldp % 8) || !bias_u || !bias_v)) return MI_ERR_ARG;
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)vt, ldvt, Tp, (const bf16_t*)pos, ldp,
-               bias_u, bias_v, lengths, (bf16_t*)out, ldo, B, T, H, scale, causal};
+    AttnArgs a = forward_args(q, ldq, k, ldk, vt, ldvt, pos, ldp, bias_u, bias_v, lengths, out, ldo, B, T, 0, 0, H, scale, causal);
+    a.Tp = Tp;
     const bool rel = pos != nullptr;
     switch (hd) {
         case 16: return launch_hd<16>(a, rel, stream);
@@ -1363,62 +1421,42 @@ extern "C" int mi_attention_bf16(const void* q, long ldq, const void* k, long ld
     }
 }
 
-// LDS-staged form: q, k, v are all (B*T, ld) bf16 row-major (columns of one fused QKV projection); hd in {64, 128}.
-extern "C" int mi_attention_qkv_bf16(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
-                                     const void* pos, long ldp, const float* bias_u, const float* bias_v,
-                                     const int* lengths, void* out, long ldo, int B, int T, int Tk, long kv_bstride, int H, int hd,
-                                     float scale, int causal, hipStream_t stream) {
-    MI_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || Tk < 0) return MI_ERR_ARG;
-    if (pos && Tk != 0 && Tk != T) return MI_ERR_ARG;                    // the relative term needs a square score matrix
-    if (causal && Tk != 0 && Tk < T) return MI_ERR_ARG;                  // the first T - Tk queries would see no key at all: their rows are 0 / 0
-    if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;                 // 16-B row stores
-    if (ldq >= (1l << 30)) return MI_ERR_ARG;
-    if (ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldp >= (1l << 30)) return MI_ERR_ARG;      // the kernel keeps row strides as 32-bit byte counts
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || (kv_bstride % 8)) return MI_ERR_ARG;
-    if (pos && ((ldp % 8) || ((uintptr_t)pos & 15) || !bias_u || !bias_v)) return MI_ERR_ARG;
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, (const bf16_t*)pos, ldp,
-               bias_u, bias_v, lengths, (bf16_t*)out, ldo, B, T, H, scale, causal, Tk, kv_bstride};
-    const bool rel = pos != nullptr;
-    switch (hd) {
-        case 64: return launch_lds<64>(a, rel, stream);
-        case 128: return launch_lds<128>(a, rel, stream);
-        default: return MI_ERR_UNSUPPORTED;
-    }
+// The head-size dispatch of every LDS-staged entry below: called after the argument checks, so that a bad argument AND an unsupported head size is MI_ERR_ARG.
+// (It follows the direct form's switch above so that the kernels are instantiated, and laid out in the code object, in the order they always were.)
+static int launch_staged(bool backward, int hd, const AttnArgs& a, hipStream_t stream) {
+    if (hd != 64 && hd != 128) return MI_ERR_UNSUPPORTED;
+    const bool rel = a.pos != nullptr;
+    if (!backward) return hd == 64 ? launch_lds<64>(a, rel, stream) : launch_lds<128>(a, rel, stream);
+    return hd == 64 ? launch_lds_bw<64>(a, rel, stream) : launch_lds_bw<128>(a, rel, stream);
 }
 
-// A/B form of the entry above: variant 0 = the product's kernel choice, 1 = the four-wave LDS-staged forward of rounds 1-3, 2 = the eight-wave form of round 4
-// (tools/attn_ab.py; no product call site passes a non-zero variant).
+// LDS-staged form: q, k, v are all (B*T, ld) bf16 row-major (columns of one fused QKV projection); hd in {64, 128}.
+// variant 0 = the product's kernel choice, 1 = the four-wave LDS-staged forward of rounds 1-3, 2 = the eight-wave form of round 4 (tools/attn_ab.py; no product call site
+// passes a non-zero variant).
 extern "C" int mi_attention_qkv_bf16_v(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
                                        const void* pos, long ldp, const float* bias_u, const float* bias_v,
                                        const int* lengths, void* out, long ldo, int B, int T, int Tk, long kv_bstride, int H, int hd,
                                        float scale, int causal, int variant, hipStream_t stream) {
     MI_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || Tk < 0 || variant < 0 || variant > 2) return MI_ERR_ARG;
-    if (pos && Tk != 0 && Tk != T) return MI_ERR_ARG;
-    if (causal && Tk != 0 && Tk < T) return MI_ERR_ARG;
-    if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;
-    if (ldq >= (1l << 30)) return MI_ERR_ARG;
-    if (ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldp >= (1l << 30)) return MI_ERR_ARG;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || (kv_bstride % 8)) return MI_ERR_ARG;
-    if (pos && ((ldp % 8) || ((uintptr_t)pos & 15) || !bias_u || !bias_v)) return MI_ERR_ARG;
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, (const bf16_t*)pos, ldp,
-               bias_u, bias_v, lengths, (bf16_t*)out, ldo, B, T, H, scale, causal, Tk, kv_bstride};
+    AttnArgs a = forward_args(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, out, ldo, B, T, Tk, kv_bstride, H, scale, causal);
     a.variant = variant;
-    switch (hd) {
-        case 64: return launch_lds<64>(a, pos != nullptr, stream);
-        case 128: return launch_lds<128>(a, pos != nullptr, stream);
-        default: return MI_ERR_UNSUPPORTED;
-    }
+    if (!forward_args_ok(a) || variant < 0 || variant > 2) return MI_ERR_ARG;
+    return launch_staged(false, hd, a, stream);
+}
+extern "C" int mi_attention_qkv_bf16(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
+                                     const void* pos, long ldp, const float* bias_u, const float* bias_v,
+                                     const int* lengths, void* out, long ldo, int B, int T, int Tk, long kv_bstride, int H, int hd,
+                                     float scale, int causal, hipStream_t stream) {
+    return mi_attention_qkv_bf16_v(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, out, ldo, B, T, Tk, kv_bstride, H, hd, scale, causal, 0, stream);
 }
 
 #ifdef ATTN_STAMPS
+// (instrumented build, tools/attn_stamps.py: no argument checks, and any hd other than 64 runs the hd-128 kernel)
 extern "C" int mi_attention_qkv_stamps(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const void* pos, long ldp, const float* bias_u, const float* bias_v,
                                        const int* lengths, void* out, long ldo, int B, int T, int H, int hd, float scale, int causal, unsigned long long* stamps, hipStream_t stream) {
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, (const bf16_t*)pos, ldp,
-               bias_u, bias_v, lengths, (bf16_t*)out, ldo, B, T, H, scale, causal, 0, 0};
+    AttnArgs a = forward_args(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, out, ldo, B, T, 0, 0, H, scale, causal);
     a.stamps = stamps;
-    return hd == 64 ? launch_lds<64>(a, pos != nullptr, stream) : launch_lds<128>(a, pos != nullptr, stream);
+    return launch_staged(false, hd == 64 ? 64 : 128, a, stream);
 }
 #endif
 
@@ -1428,123 +1466,67 @@ extern "C" int mi_attention_qkv_lse_bf16(const void* q, long ldq, const void* k,
                                          const int* lengths, void* out, long ldo, float* lse, int B, int T, int H, int hd,
                                          float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
     MI_ENTER();
-    if (B <= 0 || T <= 0 || H <= 0 || !lse || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
-    if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;
-    if (ldq >= (1l << 30) || ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldp >= (1l << 30)) return MI_ERR_ARG;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15)) return MI_ERR_ARG;
-    if (pos && ((ldp % 8) || ((uintptr_t)pos & 15) || !bias_u || !bias_v)) return MI_ERR_ARG;
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, (const bf16_t*)pos, ldp,
-               bias_u, bias_v, lengths, (bf16_t*)out, ldo, B, T, H, scale, causal, 0, 0, lse};
-    a.drop_p = drop_p; a.drop_key = ((unsigned long long)stream_id << 32) ^ (unsigned long long)seed;
-    switch (hd) {
-        case 64: return launch_lds<64>(a, pos != nullptr, stream);
-        case 128: return launch_lds<128>(a, pos != nullptr, stream);
-        default: return MI_ERR_UNSUPPORTED;
-    }
+    AttnArgs a = forward_args(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, out, ldo, B, T, 0, 0, H, scale, causal);
+    a.lse = lse;
+    set_dropout(a, drop_p, seed, stream_id);
+    if (!forward_args_ok(a) || !lse || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
+    return launch_staged(false, hd, a, stream);
 }
 
 // First half of the attention backward (self-attention, fused QKV operand; hd in {64, 128}): from q, k, v, the projected positions, the forward's context and row
 // log-sum-exp, and dctx -> prob, ds (H, B, T, ldsr) bf16 and dbd (H, B, T, ldbd) bf16 with dbd[i][T-1-i+j + pad] = ds[i][j]; and the query gradient itself,
 // dq (B*T, lddq) bf16 = dS K + dBD P, with the per-wave column sums of its two terms in dsum_u / dsum_v (B, 4 ceil(T/128), H*hd) fp32.  ldsr, ldbd multiples of 32,
 // ldsr >= T rounded up to 32, ldbd >= pad + 2T - 1, (T - 32 + pad) % 32 == 0: a wave's band of relative positions then starts on a 64-B boundary of its rows.
-// Every element of the three outputs is written (zeros where no key / relative position contributes).
+// Every element of the three outputs is written (zeros where no key / relative position contributes), unless flags says otherwise.
 // qu_out / qv_out (both or neither; with pos only): (B*T, ldqb) bf16 = q + pos_bias_u / q + pos_bias_v, written by the walk's prologue from its A fragments.
-// ... _f: the same with `flags`.  bit 0 (sparse writes): zeros nobody reads are not written — dbd must be a buffer the caller zero-filled once and that only this entry
-// writes (relative positions outside a row's maximal band stay zero from launch to launch), and columns of prob / ds from the key length rounded up to 128 on must never be
-// read (mi_bgemm_sparse_bf16 with m_valid = lengths does not).  At BASELINE config 3 (clips of 1-20 s padded to 20 s) that is 42 % of the walk's 800 MB of writes per launch.
-extern "C" int mi_attention_qkv_bwd_probs_f(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
-                                            const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
-                                            const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
-                                            void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                                            void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
-                                            int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, int flags, hipStream_t stream);
-extern "C" int mi_attention_qkv_bwd_probs_qb(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
-                                             const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
-                                             const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
-                                             void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                                             void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
-                                             int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
-    return mi_attention_qkv_bwd_probs_f(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, ctx, ldo, dctx, ldd, lse, prob, ds, ldsr, dbd, ldbd, pad, dq, lddq,
-                                        dsum_u, dsum_v, qu_out, qv_out, ldqb, B, T, H, hd, scale, causal, drop_p, seed, stream_id, 0, stream);
-}
-extern "C" int mi_attention_qkv_bwd_probs_f(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
-                                            const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
-                                            const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
-                                            void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                                            void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
-                                            int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, int flags, hipStream_t stream) {
-    MI_ENTER();
-    if (flags & ~1) return MI_ERR_ARG;
-    if ((qu_out != nullptr) != (qv_out != nullptr) || (qu_out && (!pos || (ldqb % 8) || ldqb < (long)H * hd || (((uintptr_t)qu_out | (uintptr_t)qv_out) & 15)))) return MI_ERR_ARG;
-    if (B <= 0 || T <= 0 || H <= 0 || !lse || !ctx || !dctx || !prob || !ds || !dq || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
-    if ((lddq % 8) || lddq >= (1l << 30) || ((uintptr_t)dq & 15) || (pos && (!dsum_u || !dsum_v))) return MI_ERR_ARG;
-    if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || (ldd % 8)) return MI_ERR_ARG;
-    if (ldq >= (1l << 30) || ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldp >= (1l << 30) || ldo >= (1l << 30) || ldd >= (1l << 30)) return MI_ERR_ARG;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)prob | (uintptr_t)ds | (uintptr_t)dbd) & 15)) return MI_ERR_ARG;
-    if ((ldsr % 32) || ldsr < (T + 31) / 32 * 32) return MI_ERR_ARG;
-    if (pos) {
-        if ((ldp % 8) || ((uintptr_t)pos & 15) || !bias_u || !bias_v || !dbd) return MI_ERR_ARG;
-        if ((ldbd % 32) || pad < 0 || pad >= 32 || ((T - 32 + pad) % 32) || ldbd < pad + 2 * T - 1 || ldbd >= (1l << 30)) return MI_ERR_ARG;
-    }
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, (const bf16_t*)pos, ldp,
-               bias_u, bias_v, lengths, (bf16_t*)const_cast<void*>(ctx), ldo, B, T, H, scale, causal, 0, 0, const_cast<float*>(lse),
-               (const bf16_t*)dctx, ldd, (bf16_t*)prob, (bf16_t*)ds, ldsr, (bf16_t*)dbd, pos ? ldbd : 0, pos ? pad : 0,
-               (bf16_t*)dq, lddq, dsum_u, dsum_v, drop_p, ((unsigned long long)stream_id << 32) ^ (unsigned long long)seed};
-    a.ldsum = (dsum_u && dsum_v == dsum_u + (long)H * hd) ? 2l * H * hd : 0;      // [u | v] rows of one (rows, 2 H hd) buffer: see the header
-    a.qu_out = (bf16_t*)qu_out; a.qv_out = (bf16_t*)qv_out; a.ldqb = ldqb;
-    a.sparse = flags & 1;
-    switch (hd) {
-        case 64: return launch_lds_bw<64>(a, pos != nullptr, stream);
-        case 128: return launch_lds_bw<128>(a, pos != nullptr, stream);
-        default: return MI_ERR_UNSUPPORTED;
-    }
-}
+// flags bit 0 (sparse writes): zeros nobody reads are not written — dbd must be a buffer the caller zero-filled once and that only this entry writes (relative positions
+// outside a row's maximal band stay zero from launch to launch), and columns of prob / ds from the key length rounded up to 128 on must never be read
+// (mi_bgemm_sparse_bf16 with m_valid = lengths does not).  At BASELINE config 3 (clips of 1-20 s padded to 20 s) that is 42 % of the walk's 800 MB of writes per launch.
 extern "C" int mi_attention_qkv_bwd_probs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
                                           const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
                                           const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
                                           void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                                          void* dq, long lddq, float* dsum_u, float* dsum_v,
-                                          int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
-    return mi_attention_qkv_bwd_probs_qb(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, ctx, ldo, dctx, ldd, lse, prob, ds, ldsr, dbd, ldbd, pad, dq, lddq,
-                                         dsum_u, dsum_v, nullptr, nullptr, 0, B, T, H, hd, scale, causal, drop_p, seed, stream_id, stream);
+                                          void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
+                                          int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, int flags, hipStream_t stream) {
+    MI_ENTER();
+    AttnArgs a = forward_args(q, ldq, k, ldk, v, ldv, pos, ldp, bias_u, bias_v, lengths, const_cast<void*>(ctx), ldo, B, T, 0, 0, H, scale, causal);
+    add_backward_args(a, dctx, ldd, lse, prob, ds, ldsr, dq, lddq);
+    set_dropout(a, drop_p, seed, stream_id);
+    a.dbd = (bf16_t*)dbd; a.ldbd = pos ? ldbd : 0; a.pad = pos ? pad : 0;
+    a.dsum_u = dsum_u; a.dsum_v = dsum_v;
+    a.ldsum = (dsum_u && dsum_v == dsum_u + (long)H * hd) ? 2l * H * hd : 0;      // [u | v] rows of one (rows, 2 H hd) buffer: see the header
+    a.qu_out = (bf16_t*)qu_out; a.qv_out = (bf16_t*)qv_out; a.ldqb = ldqb;
+    a.sparse = flags & 1;
+    if (!backward_args_ok(a) || !lse || drop_p < 0.f || drop_p >= 1.f || (flags & ~1)) return MI_ERR_ARG;
+    if ((qu_out != nullptr) != (qv_out != nullptr)) return MI_ERR_ARG;
+    if (qu_out && (!pos || (ldqb % 8) || ldqb < (long)H * hd || misaligned16(qu_out) || misaligned16(qv_out))) return MI_ERR_ARG;
+    if (pos) {
+        if (!dbd || !dsum_u || !dsum_v) return MI_ERR_ARG;
+        if ((ldbd % 32) || pad < 0 || pad >= 32 || ((T - 32 + pad) % 32) || ldbd < pad + 2 * T - 1 || ldbd >= LD_END) return MI_ERR_ARG;
+    }
+    return launch_staged(true, hd, a, stream);
 }
 
 // The two training entries above for Tq != Tk and separate q / k / v operands (no relative positions): the GPT-2 decoder's causal self-attention (Tq = Tk = U) and its
 // cross-attention over the encoder frames (Tq = U, Tk = T', `lengths` = valid keys), multi_head_gpt2.py:80-170 — which rounds 2-3 trained through materialised scores
 // (batched GEMM, soft-max, batched GEMM: three launches forward, seven backward).  lse (B, H, Tq); prob / ds (H, B, Tq, ldsr), ldsr a multiple of 32 >= Tk rounded up to 32.
+// Tk = 0 does not mean Tq here: it is refused.
 extern "C" int mi_attention_x_lse_bf16(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const int* lengths, void* out, long ldo, float* lse,
                                        int B, int Tq, int Tk, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
     MI_ENTER();
-    if (B <= 0 || Tq <= 0 || Tk <= 0 || H <= 0 || !lse || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
-    if (causal && Tk < Tq) return MI_ERR_ARG;                            // queries without a visible key (see mi_attention_qkv_bf16)
-    if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || ((uintptr_t)out & 15)) return MI_ERR_ARG;
-    if (ldq >= (1l << 30) || ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30)) return MI_ERR_ARG;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15)) return MI_ERR_ARG;
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, nullptr, 0, nullptr, nullptr, lengths, (bf16_t*)out, ldo, B, Tq, H, scale, causal, Tk, 0, lse};
-    a.drop_p = drop_p; a.drop_key = ((unsigned long long)stream_id << 32) ^ (unsigned long long)seed;
-    switch (hd) {
-        case 64: return launch_lds<64>(a, false, stream);
-        case 128: return launch_lds<128>(a, false, stream);
-        default: return MI_ERR_UNSUPPORTED;
-    }
+    AttnArgs a = forward_args(q, ldq, k, ldk, v, ldv, nullptr, 0, nullptr, nullptr, lengths, out, ldo, B, Tq, Tk, 0, H, scale, causal);
+    a.lse = lse;
+    set_dropout(a, drop_p, seed, stream_id);
+    if (!forward_args_ok(a) || Tk <= 0 || !lse || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
+    return launch_staged(false, hd, a, stream);
 }
 extern "C" int mi_attention_x_bwd_probs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, const int* lengths,
                                         const void* ctx, long ldo, const void* dctx, long ldd, const float* lse, void* prob, void* ds, long ldsr, void* dq, long lddq,
                                         int B, int Tq, int Tk, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, hipStream_t stream) {
     MI_ENTER();
-    if (B <= 0 || Tq <= 0 || Tk <= 0 || H <= 0 || !lse || !ctx || !dctx || !prob || !ds || !dq || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
-    if (causal && Tk < Tq) return MI_ERR_ARG;
-    if ((lddq % 8) || lddq >= (1l << 30) || ((uintptr_t)dq & 15)) return MI_ERR_ARG;
-    if ((ldq % 8) || (ldk % 8) || (ldv % 8) || (ldo % 8) || (ldd % 8)) return MI_ERR_ARG;
-    if (ldq >= (1l << 30) || ldk <= 0 || ldv <= 0 || ldk >= (1l << 30) || ldv >= (1l << 30) || ldo >= (1l << 30) || ldd >= (1l << 30)) return MI_ERR_ARG;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)ctx | (uintptr_t)dctx | (uintptr_t)prob | (uintptr_t)ds) & 15)) return MI_ERR_ARG;
-    if ((ldsr % 32) || ldsr < (Tk + 31) / 32 * 32) return MI_ERR_ARG;
-    AttnArgs a{(const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, 0, nullptr, 0, nullptr, nullptr, lengths, (bf16_t*)const_cast<void*>(ctx), ldo, B, Tq, H, scale, causal,
-               Tk, 0, const_cast<float*>(lse), (const bf16_t*)dctx, ldd, (bf16_t*)prob, (bf16_t*)ds, ldsr, nullptr, 0, 0, (bf16_t*)dq, lddq, nullptr, nullptr, drop_p,
-               ((unsigned long long)stream_id << 32) ^ (unsigned long long)seed};
-    switch (hd) {
-        case 64: return launch_lds_bw<64>(a, false, stream);
-        case 128: return launch_lds_bw<128>(a, false, stream);
-        default: return MI_ERR_UNSUPPORTED;
-    }
+    AttnArgs a = forward_args(q, ldq, k, ldk, v, ldv, nullptr, 0, nullptr, nullptr, lengths, const_cast<void*>(ctx), ldo, B, Tq, Tk, 0, H, scale, causal);
+    add_backward_args(a, dctx, ldd, lse, prob, ds, ldsr, dq, lddq);
+    set_dropout(a, drop_p, seed, stream_id);
+    if (!backward_args_ok(a) || Tk <= 0 || !lse || drop_p < 0.f || drop_p >= 1.f) return MI_ERR_ARG;
+    return launch_staged(true, hd, a, stream);
 }

@@ -175,20 +175,9 @@ extern "C" int mi_ctc_prefix_score(const float* x, int B, int T, int O, int blan
     return MI_OK;
 }
 
-// advance the state along the selected chains (hyp[k], tok[k]), k < K: r_out (T,2,K)
-extern "C" int mi_ctc_prefix_select(const float* x, int B, int T, int O, int blank, int W, const float* r_prev, const long* last_ids,
-                                    long ld_last, int out_len, const int* hyp, const long* tok, long ld_tok, int K, float* r_out,
-                                    hipStream_t stream) {
-    MI_ENTER();
-    if (B <= 0 || T <= 0 || O <= 0 || W <= 0 || K <= 0) return MI_ERR_ARG;
-    ChainArgs a{x, B, T, O, blank, W, r_prev, last_ids, ld_last, out_len, hyp, tok, ld_tok, K, r_out, nullptr, nullptr, nullptr, 0, nullptr, 0};
-    hipLaunchKernelGGL(prefix_chain_kernel, dim3(cdiv(K, 256)), dim3(256), 0, stream, a);
-    MI_CHECK_LAUNCH();
-    return MI_OK;
-}
-
-// One decoding step of the processor after the first (= mi_ctc_prefix_select along (beam 0 of every utterance, the token each hypothesis ended on) followed by
-// mi_ctc_prefix_score with s_prev gathered from the previous call's psi), without the index tensors in between: two launches from one call.
+// One decoding step of the processor after the first: the state advances along the chains (beam 0 of every utterance, the token each hypothesis ended on) into r_prev,
+// then every (hypothesis, token) pair is scored from there as in mi_ctc_prefix_score, with s_prev gathered from the previous call's psi — no index tensors in between,
+// two launches from one call.
 //   previous call: r_old (T,2,n_bh), last_old (its prefixes' last tokens), out_len_old, psi_old (n_bh, O);  this call: last, out_len
 //   out: r_prev (T,2,n_bh) = the state this call's chains start from (kept for the next call), psi (n_bh, O), scores (n_bh, O)
 extern "C" int mi_ctc_prefix_advance(const float* x, int B, int T, int O, int blank, int W, const float* r_old, const long* last_old, long ld_last_old, int out_len_old,
@@ -206,7 +195,7 @@ extern "C" int mi_ctc_prefix_advance(const float* x, int B, int T, int O, int bl
 
 // The same step in ONE launch when the chains of every (hypothesis, token) may be kept (T x 2 x n_bh x O floats: 50 MB at T' = 250, W = 5, V = 5001 — what the reference
 // materialises per token, ctc_scorer.py:58-178; here it is written once, coalesced over the tokens, by the scan that computes it anyway): the state a hypothesis continues from
-// is then a column of the previous call's `r_all`, and the re-run of the selected chains (mi_ctc_prefix_select: a second dependent 250-frame scan per token) disappears.
+// is then a column of the previous call's `r_all`, and the re-run of the selected chains (mi_ctc_prefix_advance's first launch: a second dependent 250-frame scan per token) disappears.
 //   r_prev: rp_full = 0 -> (T, 2, n_bh) of mi_ctc_prefix_prepare (first token, psi_old null);  rp_full = 1 -> the previous call's r_all, psi_old its psi.
 extern "C" int mi_ctc_prefix_score_full(const float* x, int B, int T, int O, int blank, int W, const float* r_prev, int rp_full, const float* psi_old, const long* last,
                                         long ld_last, int out_len, float* r_all, float* psi, float* scores, hipStream_t stream) {

@@ -372,17 +372,6 @@ __global__ __launch_bounds__(256) void ln_partial_reduce_many_kernel(LnRedMany p
     }
 }
 
-// y = LN(x) with precomputed (mean, rstd) per row: the CSGU gate normalisation re-materialised for the backward pass
-__global__ __launch_bounds__(256) void ln_apply_kernel(const bf16_t* __restrict__ x, long ldx, const float* __restrict__ stats,
-                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                        bf16_t* __restrict__ y, long ldy, int M, int N) {
-    const long total = (long)M * N;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int m = (int)(i / N), c = (int)(i % N);
-        y[(long)m * ldy + c] = f2bf((bf2f(x[(long)m * ldx + c]) - stats[2 * m]) * stats[2 * m + 1] * gamma[c] + beta[c]);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------ small element-wise ops
 __global__ __launch_bounds__(256) void add_f32_kernel(float* __restrict__ a, const float* __restrict__ b, long n, float alpha) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) a[i] += alpha * b[i];
@@ -453,18 +442,6 @@ __global__ __launch_bounds__(256) void add_rowvec2_vec8_kernel(const bf16_t* __r
         }
         *reinterpret_cast<bf16x8*>(ou + (long)m * ldo + c) = a;
         *reinterpret_cast<bf16x8*>(ov + (long)m * ldo + c) = b;
-    }
-}
-// gating backward of s = r * c:  dr = ds * c,  dc = ds * r
-__global__ __launch_bounds__(256) void gate_bwd_kernel(const bf16_t* __restrict__ ds, long ldds, const bf16_t* __restrict__ c, long ldc,
-                                                        const bf16_t* __restrict__ r, long ldr, bf16_t* __restrict__ dr, long lddr,
-                                                        bf16_t* __restrict__ dc, long lddc, int M, int N) {
-    const long total = (long)M * N;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int m = (int)(i / N), n = (int)(i % N);
-        const float g = bf2f(ds[(long)m * ldds + n]);
-        dr[(long)m * lddr + n] = f2bf(g * bf2f(c[(long)m * ldc + n]));
-        dc[(long)m * lddc + n] = f2bf(g * bf2f(r[(long)m * ldr + n]));
     }
 }
 // zero the rows of padded frames: row (b, t) with t >= lengths[b]
@@ -835,15 +812,6 @@ extern "C" int mi_ln_partial_reduce_many(const mi_lnred_desc* descs, int n, hipS
     return MI_OK;
 }
 
-extern "C" int mi_ln_apply_bf16(const void* x, long ldx, const float* stats, const float* gamma, const float* beta, void* y, long ldy,
-                                int M, int N, hipStream_t st) {
-    MI_ENTER();
-    if (M <= 0 || N <= 0) return MI_ERR_ARG;
-    hipLaunchKernelGGL(ln_apply_kernel, dim3(grid_for((long)M * N)), dim3(256), 0, st, (const bf16_t*)x, ldx, stats, gamma, beta, (bf16_t*)y, ldy, M, N);
-    MI_CHECK_LAUNCH();
-    return MI_OK;
-}
-
 extern "C" int mi_axpy_f32(float* a, const float* b, long n, float alpha, hipStream_t st) {
     MI_ENTER();
     if (n <= 0) return MI_ERR_ARG;
@@ -893,15 +861,6 @@ extern "C" int mi_add_rowvec2_bf16(const void* x, long ldx, const float* u, cons
         hipLaunchKernelGGL(add_rowvec_kernel, dim3(grid_for((long)M * N)), dim3(256), 0, st, (const bf16_t*)x, ldx, u, (bf16_t*)out_u, ldo, M, N);
         hipLaunchKernelGGL(add_rowvec_kernel, dim3(grid_for((long)M * N)), dim3(256), 0, st, (const bf16_t*)x, ldx, v, (bf16_t*)out_v, ldo, M, N);
     }
-    MI_CHECK_LAUNCH();
-    return MI_OK;
-}
-extern "C" int mi_gate_bwd_bf16(const void* ds, long ldds, const void* c, long ldc, const void* r, long ldr, void* dr, long lddr,
-                                void* dc, long lddc, int M, int N, hipStream_t st) {
-    MI_ENTER();
-    if (M <= 0 || N <= 0) return MI_ERR_ARG;
-    hipLaunchKernelGGL(gate_bwd_kernel, dim3(grid_for((long)M * N)), dim3(256), 0, st, (const bf16_t*)ds, ldds, (const bf16_t*)c, ldc,
-                       (const bf16_t*)r, ldr, (bf16_t*)dr, lddr, (bf16_t*)dc, lddc, M, N);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }

@@ -229,24 +229,17 @@ def attention_qkv(qkv, B, T, H, *, pos=None, bias_u=None, bias_v=None, lengths=N
     hd = d // H
     out = torch.empty((B * T, d), device=qkv.device, dtype=BF16)
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
+    operands = (q.data_ptr(), qkv.stride(0), k.data_ptr(), qkv.stride(0), v.data_ptr(), qkv.stride(0),
+               _p(pos), pos.stride(0) if pos is not None else 0, _p(bias_u), _p(bias_v), _p(lengths), out.data_ptr(), out.stride(0))
     if lse is not None:
         dp, dseed, dsid = drop if drop is not None else (0.0, 0, 0)
-        rc = _lib.lib().mi_attention_qkv_lse_bf16(q.data_ptr(), qkv.stride(0), k.data_ptr(), qkv.stride(0), v.data_ptr(), qkv.stride(0),
-                                                  _p(pos), pos.stride(0) if pos is not None else 0, _p(bias_u), _p(bias_v), _p(lengths),
-                                                  out.data_ptr(), out.stride(0), lse.data_ptr(), B, T, H, hd, 1.0 / math.sqrt(hd), int(causal),
+        rc = _lib.lib().mi_attention_qkv_lse_bf16(*operands, lse.data_ptr(), B, T, H, hd, 1.0 / math.sqrt(hd), int(causal),
                                                   float(dp), int(dseed) & 0xFFFFFFFF, int(dsid) & 0xFFFFFFFF, _stream())
         _lib.check(rc, "mi_attention_qkv_lse_bf16")
         return out
-    if variant:      # measurement only (tools/attn_ab.py): the four-wave kernel of rounds 1-3
-        rc = _lib.lib().mi_attention_qkv_bf16_v(q.data_ptr(), qkv.stride(0), k.data_ptr(), qkv.stride(0), v.data_ptr(), qkv.stride(0),
-                                                _p(pos), pos.stride(0) if pos is not None else 0, _p(bias_u), _p(bias_v), _p(lengths),
-                                                out.data_ptr(), out.stride(0), B, T, 0, 0, H, hd, 1.0 / math.sqrt(hd), int(causal), int(variant), _stream())
-        _lib.check(rc, "mi_attention_qkv_bf16_v")
-        return out
-    rc = _lib.lib().mi_attention_qkv_bf16(q.data_ptr(), qkv.stride(0), k.data_ptr(), qkv.stride(0), v.data_ptr(), qkv.stride(0),
-                                          _p(pos), pos.stride(0) if pos is not None else 0, _p(bias_u), _p(bias_v), _p(lengths),
-                                          out.data_ptr(), out.stride(0), B, T, 0, 0, H, hd, 1.0 / math.sqrt(hd), int(causal), _stream())
-    _lib.check(rc, "mi_attention_qkv_bf16")
+    # variant != 0: measurement only (tools/attn_ab.py): 1 = the four-wave kernel of rounds 1-3, 2 = the eight-wave form
+    rc = _lib.lib().mi_attention_qkv_bf16_v(*operands, B, T, 0, 0, H, hd, 1.0 / math.sqrt(hd), int(causal), int(variant), _stream())
+    _lib.check(rc, "mi_attention_qkv_bf16_v")
     return out
 
 
@@ -258,16 +251,10 @@ def attention_general(q, k, v, B, Tq, Tk, H, *, lengths=None, causal=False, out=
     hd = d // H
     if out is None:
         out = torch.empty((B * Tq, d), device=q.device, dtype=BF16)
-    if variant:
-        rc = _lib.lib().mi_attention_qkv_bf16_v(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-                                                0, 0, 0, 0, _p(lengths), out.data_ptr(), out.stride(0), B, Tq, Tk, kv_bstride, H, hd,
-                                                1.0 / math.sqrt(hd), int(causal), int(variant), _stream())
-        _lib.check(rc, "mi_attention_qkv_bf16_v")
-        return out
-    rc = _lib.lib().mi_attention_qkv_bf16(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
-                                          0, 0, 0, 0, _p(lengths), out.data_ptr(), out.stride(0), B, Tq, Tk, kv_bstride, H, hd,
-                                          1.0 / math.sqrt(hd), int(causal), _stream())
-    _lib.check(rc, "mi_attention_qkv_bf16")
+    rc = _lib.lib().mi_attention_qkv_bf16_v(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0),
+                                            0, 0, 0, 0, _p(lengths), out.data_ptr(), out.stride(0), B, Tq, Tk, kv_bstride, H, hd,
+                                            1.0 / math.sqrt(hd), int(causal), int(variant), _stream())
+    _lib.check(rc, "mi_attention_qkv_bf16_v")
     return out
 
 

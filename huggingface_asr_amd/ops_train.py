@@ -405,7 +405,7 @@ def attn_bwd_probs(qkv, B, T, H, ctx, dctx, lse, dq, *, pos=None, bias_u=None, b
     dq (B*T, d) bf16 row view receives the query gradient dS K + dBD P; with positions also -> (su, sv): (rows, d) fp32 whose column sums are the gradients
     of pos_bias_u / pos_bias_v.  drop = the (p, seed, stream_id) the forward used: prob is then the DROPPED probabilities (what multiplied V).
     qb (with positions): also -> (qu, qv) (B*T, d) bf16 = q + pos_bias_u, q + pos_bias_v as the kernel's own operands (what `add_rowvec2(q, u, v)` makes), appended to the result.
-    sparse: the zeros nobody reads are not written (mi_attention_qkv_bwd_probs_f, flag 1): dbd is then ONE zero-filled buffer per shape that every call re-uses (the caller
+    sparse: the zeros nobody reads are not written (mi_attention_qkv_bwd_probs, flags bit 0): dbd is then ONE zero-filled buffer per shape that every call re-uses (the caller
     consumes it before the next call on the same stream), and prob / ds hold garbage from the key length rounded up to 128 on — read them only through `bgemm(..., m_valid=lengths)`."""
     d = qkv.shape[1] // 3
     dp, dseed, dsid = drop if drop is not None else (0.0, 0, 0)
@@ -423,12 +423,12 @@ def attn_bwd_probs(qkv, B, T, H, ctx, dctx, lse, dq, *, pos=None, bias_u=None, b
     q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
     qu = torch.empty((B * T, d), device=dev, dtype=BF16) if (qb and rel) else None
     qv = torch.empty((B * T, d), device=dev, dtype=BF16) if (qb and rel) else None
-    _lib.check(_L().mi_attention_qkv_bwd_probs_f(q.data_ptr(), qkv.stride(0), k.data_ptr(), qkv.stride(0), v.data_ptr(), qkv.stride(0),
-                                                  _p(pos), pos.stride(0) if rel else 0, _p(bias_u), _p(bias_v), _p(lengths),
-                                                  ctx.data_ptr(), ctx.stride(0), dctx.data_ptr(), dctx.stride(0), lse.data_ptr(),
-                                                  prob.data_ptr(), ds.data_ptr(), Ts, _p(dbd), Ps, pad, dq.data_ptr(), dq.stride(0), _p(su), _p(sv), _p(qu), _p(qv), d,
-                                                  B, T, H, hd, 1.0 / math.sqrt(hd), int(causal), float(dp), int(dseed) & 0xFFFFFFFF, int(dsid) & 0xFFFFFFFF, int(bool(sparse)), _stream()),
-               "mi_attention_qkv_bwd_probs_f")
+    _lib.check(_L().mi_attention_qkv_bwd_probs(q.data_ptr(), qkv.stride(0), k.data_ptr(), qkv.stride(0), v.data_ptr(), qkv.stride(0),
+                                                _p(pos), pos.stride(0) if rel else 0, _p(bias_u), _p(bias_v), _p(lengths),
+                                                ctx.data_ptr(), ctx.stride(0), dctx.data_ptr(), dctx.stride(0), lse.data_ptr(),
+                                                prob.data_ptr(), ds.data_ptr(), Ts, _p(dbd), Ps, pad, dq.data_ptr(), dq.stride(0), _p(su), _p(sv), _p(qu), _p(qv), d,
+                                                B, T, H, hd, 1.0 / math.sqrt(hd), int(causal), float(dp), int(dseed) & 0xFFFFFFFF, int(dsid) & 0xFFFFFFFF, int(bool(sparse)), _stream()),
+               "mi_attention_qkv_bwd_probs")
     return (prob, ds, dbd, su, sv, qu, qv) if qb else (prob, ds, dbd, su, sv)
 
 

@@ -174,30 +174,19 @@ int mi_attention_qkv_lse_bf16(const void* q, long ldq, const void* k, long ldk, 
  * dsum_u / dsum_v (B, 4 ceil(T/128), H*hd) fp32 (summed over their first two axes: the pos_bias_u / pos_bias_v gradients; unused without pos).
  * dsum_v == dsum_u + H*hd selects the interleaved layout: ONE (B * 4 ceil(T/128), 2 H*hd) buffer whose rows are [u | v] — the shape mi_ln_partial_reduce_many sums
  * (desc kind 0 with d = H*hd, dgamma = the pos_bias_u gradient, dbeta = the pos_bias_v gradient), so the reduction can leave with a later launch.
- * ldsr, ldbd multiples of 32 with ldsr >= T rounded up to 32 and ldbd >= pad + 2T - 1; 0 <= pad < 32 with (T - 32 + pad) % 32 == 0.  Every element is written. */
+ * ldsr, ldbd multiples of 32 with ldsr >= T rounded up to 32 and ldbd >= pad + 2T - 1; 0 <= pad < 32 with (T - 32 + pad) % 32 == 0.  Every element is written
+ * (but see flags).
+ * qu_out / qv_out (both or neither, with pos only; else null): (B*T, ldqb) bf16 = q + pos_bias_u / q + pos_bias_v, the walk's own A fragments — the operands of the
+ * dK = dS^T (q + u) and d(positions) = dBD^T (q + v) products that follow, which a pass of their own used to make.
+ * flags bit 0, sparse writes: the zeros nobody reads are not written — `dbd` must be a buffer the caller zero-filled ONCE and that only this entry writes (a row's
+ * relative positions outside its maximal band are the same for every launch), and columns of prob / ds from the key length rounded up to 128 on must never be read
+ * (mi_bgemm_sparse_bf16 with m_valid = lengths does not read them).  Other bits must be 0. */
 int mi_attention_qkv_bwd_probs(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
                                const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
                                const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
                                void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                               void* dq, long lddq, float* dsum_u, float* dsum_v,
-                               int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, mi_stream_t stream);
-/* the same, also leaving qu_out / qv_out (B*T, ldqb) bf16 = q + pos_bias_u / q + pos_bias_v (both or neither, with pos only): the walk's own A fragments — the operands
- * of the dK = dS^T (q + u) and d(positions) = dBD^T (q + v) products that follow, which a pass of their own used to make */
-int mi_attention_qkv_bwd_probs_qb(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
-                                  const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
-                                  const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
-                                  void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                                  void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
-                                  int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, mi_stream_t stream);
-/* ... with flags.  bit 0, sparse writes: the zeros nobody reads are not written — `dbd` must be a buffer the caller zero-filled ONCE and that only this entry writes (a row's
- * relative positions outside its maximal band are the same for every launch), and columns of prob / ds from the key length rounded up to 128 on must never be read
- * (mi_bgemm_sparse_bf16 with m_valid = lengths does not read them). */
-int mi_attention_qkv_bwd_probs_f(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv,
-                                  const void* pos, long ldp, const float* bias_u, const float* bias_v, const int* lengths,
-                                  const void* ctx, long ldo, const void* dctx, long ldd, const float* lse,
-                                  void* prob, void* ds, long ldsr, void* dbd, long ldbd, int pad,
-                                  void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
-                                  int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, int flags, mi_stream_t stream);
+                               void* dq, long lddq, float* dsum_u, float* dsum_v, void* qu_out, void* qv_out, long ldqb,
+                               int B, int T, int H, int hd, float scale, int causal, float drop_p, unsigned seed, unsigned stream_id, int flags, mi_stream_t stream);
 /* Attention backward for the fused (B*T, 3d) projection with no (H, B, T, T) tensor in HBM (attn_bwd_fused.hip): no relative positions, no dropout, hd 64 / 128.
  * P and dS are recomputed from q, k and the forward's lse (mi_attention_qkv_lse_bf16); dq / dk / dv are row views of one (B*T, ldg) bf16 buffer, every row written.
  * workspace: >= B*T*H*4 bytes.  No atomics: the result is bitwise reproducible. */
@@ -314,9 +303,6 @@ int mi_ctc_prefix_prepare(const void* logits, long ld_b, long ld_t, int dtype, c
                           int blank, int W, float* lse_scratch, float* x_out, float* r0_out, mi_stream_t stream);
 int mi_ctc_prefix_score(const float* x, int B, int T, int O, int blank, int W, const float* r_prev, const long* last_ids,
                         long ld_last, int out_len, const float* s_prev, float* psi_out, float* scores_out, mi_stream_t stream);
-int mi_ctc_prefix_select(const float* x, int B, int T, int O, int blank, int W, const float* r_prev, const long* last_ids,
-                         long ld_last, int out_len, const int* hyp, const long* tok, long ld_tok, int K, float* r_out,
-                         mi_stream_t stream);
 /* one processor call after the first = select along (beam 0 of every utterance, last token of every hypothesis) + score with s_prev = psi_old[beam 0 row, last token],
    from one call (no index tensors in between; ctc_scorer.py:327-330 -> :58-207).  r_prev / psi are the state the next call passes as r_old / psi_old. */
 int mi_ctc_prefix_advance(const float* x, int B, int T, int O, int blank, int W, const float* r_old, const long* last_old, long ld_last_old, int out_len_old,
@@ -386,8 +372,6 @@ int mi_layernorm_bwd_dual_partial(const void* x, long ldx, int x_bf16, float eps
                                   float* partial, float* partial2, int* nblk, void* cast, long ldcast, float alpha, float drop_p, unsigned seed,
                                   unsigned stream_id, int M, int d, mi_stream_t stream);
 int mi_ln_partial_reduce_many(const mi_lnred_desc* descs, int n, mi_stream_t stream);
-int mi_ln_apply_bf16(const void* x, long ldx, const float* stats, const float* gamma, const float* beta, void* y, long ldy,
-                     int M, int N, mi_stream_t stream);
 int mi_axpy_f32(float* a, const float* b, long n, float alpha, mi_stream_t stream);
 int mi_scale_f32(float* a, long n, float alpha, mi_stream_t stream);
 /* a *= *alpha_dev (a device scalar; a 16-B aligned); a no-op launch when it is exactly 1: the autograd bridge's d(loss) factor (autograd_bridge.py) */
@@ -397,8 +381,6 @@ int mi_add2_cast_bf16(const float* a, long lda, const float* b, long ldb, void* 
 int mi_add_rowvec_bf16(const void* x, long ldx, const float* vec, void* out, long ldo, int M, int N, mi_stream_t stream);
 /* out_u = bf16(x + u), out_v = bf16(x + v) from one read of x (q + pos_bias_u / q + pos_bias_v: e_branchformer's relative-position attention, tf wav2vec2_conformer :466-470) */
 int mi_add_rowvec2_bf16(const void* x, long ldx, const float* u, const float* v, void* out_u, void* out_v, long ldo, int M, int N, mi_stream_t stream);
-int mi_gate_bwd_bf16(const void* ds, long ldds, const void* c, long ldc, const void* r, long ldr, void* dr, long lddr,
-                     void* dc, long lddc, int M, int N, mi_stream_t stream);
 /* valid frame counts behind `layers` Conv2d sub-sampling layers (kernel, stride, pad on the time axis) for B utterances: inner[b] = min(count with padding, tmax) — the
  * encoder's masks —, outer[b] = count without padding — the CTC loss's input lengths (reference: e_branchformer.py _get_feat_extract_output_lengths; floor division) */
 int mi_subsampled_lengths_i32(const int* lengths, int B, int kernel, int stride, int pad, int layers, int tmax, int* inner, int* outer, mi_stream_t stream);

@@ -301,3 +301,47 @@ def test_causal_with_fewer_keys_than_queries_is_refused_x_bwd_probs():
         OT.attn_x_bwd_probs(q, k, v, B, Tq, Tk, H, ctx, ctx, lse, dq, causal=True)
     torch.cuda.synchronize()
     assert bool(torch.isnan(dq).all())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------------------------
+def test_refusal_table_bases_are_valid_calls():
+    """The six base calls of tests/attention_arg_cases.py on real tensors of their dimensions and strides: each returns 0 and writes finite values everywhere, so the
+    one defect of each mutation (tests/test_attention_args_cpu.py) is what refuses it.  The backward bases read the context and log-sum-exp their forward bases leave."""
+    import attention_arg_cases as A
+    from huggingface_asr_amd import _lib
+    from huggingface_asr_amd import ops_train as OT
+    gen = torch.Generator().manual_seed(11)
+    dims = A.BASES["mi_attention_qkv_bwd_probs"]
+    B, T, H, hd, Tk = dims["B"], dims["T"], dims["H"], dims["hd"], A.BASES["mi_attention_x_bwd_probs"]["Tk"]
+    d = H * hd
+
+    def rnd(*shape, dtype=BF16):
+        return (0.5 * torch.randn(*shape, generator=gen)).to(DEV, dtype)
+
+    def poison(*shape, dtype=BF16):
+        return torch.full(shape, NAN, device=DEV, dtype=dtype)
+
+    qkv, xq, xkv = rnd(B * T, 3 * d), rnd(B * T, d), rnd(B * Tk, 2 * d).chunk(2, dim=1)
+    shared = dict(pos=rnd(2 * T - 1, d), bias_u=rnd(H, hd, dtype=torch.float32), bias_v=rnd(H, hd, dtype=torch.float32), dctx=rnd(B * T, d))
+    operands = {"qkv": dict(shared, q=qkv[:, :d], k=qkv[:, d:2 * d], v=qkv[:, 2 * d:], lengths=torch.tensor([T, 25], dtype=torch.int32, device=DEV)),
+                "x": dict(shared, q=xq, k=xkv[0].contiguous(), v=xkv[1].contiguous(), lengths=torch.tensor([Tk, 20], dtype=torch.int32, device=DEV))}
+    nw = 4 * ((T + 127) // 128)
+    for entry in ("mi_attention_qkv_bf16", "mi_attention_qkv_bf16_v", "mi_attention_qkv_lse_bf16", "mi_attention_qkv_bwd_probs", "mi_attention_x_lse_bf16", "mi_attention_x_bwd_probs"):
+        base, ops_ = A.BASES[entry], operands["x" if "_x_" in entry else "qkv"]
+        fwd = "bwd" not in entry
+        outs = dict(out=poison(B * T, d), lse=poison(B, H, T, dtype=torch.float32)) if fwd else \
+            dict(prob=poison(H, B, T, base["ldsr"]), ds=poison(H, B, T, base["ldsr"]), dq=poison(B * T, d), dbd=poison(H, B, T, base.get("ldbd", 32)),
+                 dsum_u=poison(B, nw, d, dtype=torch.float32), dsum_v=poison(B, nw, d, dtype=torch.float32), qu_out=poison(B * T, d), qv_out=poison(B * T, d))
+        outs = {n: t for n, t in outs.items() if base.get(n)}
+        tensors = dict(ops_, **outs)
+        for n, ld in (("q", "ldq"), ("k", "ldk"), ("v", "ldv"), ("pos", "ldp"), ("out", "ldo"), ("ctx", "ldo"), ("dctx", "ldd"), ("dq", "lddq"), ("qu_out", "ldqb")):
+            if base.get(n):
+                assert tensors[n].stride(0) == base[ld], (entry, n)
+        args = [tensors[n].data_ptr() if n in A.POINTERS and base[n] else base[n] for n in A.PARAMS[entry]]
+        rc = getattr(_lib.lib(), entry)(*args, OT._stream())
+        torch.cuda.synchronize()
+        assert rc == 0, entry
+        for n, t in outs.items():
+            assert bool(torch.isfinite(t.float()).all()), (entry, n)
+        if entry.endswith("_lse_bf16"):
+            operands["x" if "_x_" in entry else "qkv"].update(ctx=outs["out"], lse=outs["lse"])
