@@ -191,6 +191,18 @@ SIGNATURES = {
     "mi_ebf_forward_hs": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp],
     "mi_ebf_forward_lse": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp],
     "mi_ebf_forward_greedy": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp],
+    # precision = "fp32" inference mode (csrc/gemm_f32.hip, csrc/encoder_f32.hip)
+    "mi_gemm_f32": [vp, i64, vp, i64, vp, vp, i64, vp, i64, f32, i32, i32, i32, i32, vp],
+    "mi_layernorm_f32": [vp, i64, vp, i32, vp, i64, vp, vp, f32, vp, i64, i32, i32, vp],
+    "mi_rotary_f32": [vp, i64, vp, i64, vp, vp, i32, i32, i32, i32, vp],
+    "mi_dwconv_f32": [vp, i64, vp, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+    "mi_gate_act_mul_f32": [vp, i64, vp, i64, vp, i64, i32, i32, i32, vp],
+    "mi_conv2d_first_gelu_f32": [vp, vp, vp, vp] + [i32] * 10 + [vp],
+    "mi_conv2d_cl_f32": [vp, vp, vp, vp] + [i32] * 12 + [vp],
+    "mi_attention_f32_workspace_bytes": [i32, i32, i32, i32, i32],
+    "mi_attention_f32": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, vp, sz, vp],
+    "mi_ebf_f32_workspace_bytes": [C.POINTER(EbfConfig)],
+    "mi_ebf_forward_f32": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp],
 }
 
 _lib = None
@@ -218,7 +230,8 @@ def lib():
             fn.argtypes = args
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
-                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes") else i32
+                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes",
+                                          "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None
         h.mi_profile_reset.argtypes = []; h.mi_profile_reset.restype = None

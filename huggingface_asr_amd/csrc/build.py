@@ -17,7 +17,8 @@ PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, "libhfasr_hip.so")
 OBJ = os.path.join(HERE, "build")
 SOURCES = ["gemm_bf16.hip", "gemm_glds.hip", "gemm_8p.hip", "norm.hip", "conv.hip", "attention.hip", "fbank.hip", "ctc.hip", "ctc_decode.hip", "ctc_beam.hip", "ctc_prefix.hip", "decoder.hip", "decoder_step.hip", "decoder_fused.hip", "linear_rows.hip", "beam_step.hip", "beam_step_wide.hip", "whisper.hip", "encoder.hip",
-           "train_ops.hip", "gemm_tn.hip", "bgemm.hip", "attn_bwd.hip", "attn_bwd_fused.hip", "conv_bwd.hip", "loss_bwd.hip", "mix_loss.hip", "dropout.hip", "bestrq.hip", "specaug.hip", "speed.hip"]
+           "train_ops.hip", "gemm_tn.hip", "bgemm.hip", "attn_bwd.hip", "attn_bwd_fused.hip", "conv_bwd.hip", "loss_bwd.hip", "mix_loss.hip", "dropout.hip", "bestrq.hip", "specaug.hip", "speed.hip",
+           "gemm_f32.hip", "encoder_f32.hip"]      # precision = "fp32" inference mode
 # -packed-fp32-ops (device side only): no v_pk_{add,mul,fma}_f32 in any kernel.  A wave executing packed-f32 VALU ops next to the LDS-DMA GEMM's
 # waves on one CU (kernels from two streams) lost the low-half product on 16 lanes in ~3 % of launches (tools/dbg/README.md); without packed
 # ops the same pairing ran clean, and beside MFMAs they are slower than their scalar pairs anyway (MI355X_MICROARCH.md, fillers table).
@@ -34,7 +35,7 @@ def _stale(target, deps):
 
 def _compile(src):
     obj = os.path.join(OBJ, src.replace(".hip", ".o"))
-    deps = [os.path.join(HERE, src), os.path.join(HERE, "common.hpp"), os.path.join(HERE, "gemm_args.hpp"), os.path.join(HERE, "radix_select.hpp"), os.path.join(os.path.dirname(PKG), "include", "hfasr_hip.h"),
+    deps = [os.path.join(HERE, src), os.path.join(HERE, "common.hpp"), os.path.join(HERE, "gemm_args.hpp"), os.path.join(HERE, "radix_select.hpp"), os.path.join(HERE, "gemm_f32.hpp"), os.path.join(os.path.dirname(PKG), "include", "hfasr_hip.h"),
             os.path.abspath(__file__)]                                   # the flags live in this file
     if _stale(obj, deps):
         subprocess.run(["hipcc", *FLAGS, "-c", os.path.join(HERE, src), "-o", obj], check=True)

@@ -32,6 +32,7 @@ FOLDS = {"ff1_b1": ("FF1", "ff1_w1", "ff1_ln_g", "ff1_ln_b"), "att_bqkv": ("QKV"
          "mlp_b1": ("MLP", "mlp_w1", "mlp_ln_g", "mlp_ln_b"), "ff2_b1": ("FF2", "ff2_w1", "ff2_ln_g", "ff2_ln_b")}
 ACT = {"identity": 0, "gelu": 1, "relu": 2, "silu": 3, "swish": 3}
 POS = {None: 0, "none": 0, "relative": 1, "rotary": 2}
+PRECISIONS = ("bf16", "fp32")
 
 
 def cfg_from_hf(config) -> dict:
@@ -60,9 +61,17 @@ def cfg_from_hf(config) -> dict:
 
 
 class EBranchformerEngine:
-    """Forward engine for Wav2Vec2EBranchformerForCTC (eval-mode semantics of e_branchformer.py:422-496)."""
+    """Forward engine for Wav2Vec2EBranchformerForCTC (eval-mode semantics of e_branchformer.py:422-496).
 
-    def __init__(self, cfg: dict, device="cuda:0", logits_dtype=torch.float32):
+    precision "bf16" (default): bf16 operands and activations between kernels, fp32 accumulation — the reference's `--bf16` recipes.
+    precision "fp32": no value is rounded to bf16 anywhere between the features and the logits (mi_ebf_forward_f32: fp32 weights, f32-input MFMA GEMMs, fp32 attention
+    scores; DESIGN.md §4 'fp32 inference mode') — what the reference's decode recipes compute.  Plain encoder + CTC head only: the gated front ends, the BEST-RQ
+    fine-tuning head, want_all_hidden, ForwardPipeline lanes, HFASR_BRANCH_OVERLAP=1 and a forced ln_fold raise NotImplementedError, on the host."""
+
+    def __init__(self, cfg: dict, device="cuda:0", logits_dtype=torch.float32, precision="bf16"):
+        if precision not in PRECISIONS:
+            raise ValueError(f"EBranchformerEngine: precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
         self.cfg = dict(cfg)
         self.device = torch.device(device)
         self.logits_dtype = logits_dtype
@@ -100,16 +109,36 @@ class EBranchformerEngine:
         self._pos = {}
         self._posp = {}
         self.weights_version = 0
+        if precision == "fp32":
+            self._refuse_fp32_options(logits_dtype)
+
+    def _refuse_fp32_options(self, logits_dtype=torch.float32):
+        """what precision="fp32" does not cover, named and refused on the host before the device is touched"""
+        no = lambda what: NotImplementedError(f"precision='fp32' does not cover {what}: use the default precision='bf16'")
+        if self.ctx_mode:
+            raise no(f"the gated front ends (context_awareness_type={self.cfg.get('context_awareness_type')!r})")
+        if self.extra or self.mix:
+            raise no("the BEST-RQ fine-tuning head (finetune_with_additional_layer / finetune_with_layer_mixing)")
+        if self.branch_overlap:
+            raise no("HFASR_BRANCH_OVERLAP=1")
+        if self.ln_fold:
+            raise no("a forced ln_fold (HFASR_LN_FOLD=1 / engine.ln_fold = True)")
+        if self.wide_tiles:
+            raise no("wide_tiles (ForwardPipeline's throughput mode)")
+        if logits_dtype != torch.float32:
+            raise ValueError("precision='fp32' produces fp32 logits: logits_dtype must be torch.float32")
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd: dict):
         """sd: reference-named tensors (any device/dtype); packs them on `self.device`: every packed parameter of packing.encoder_specs into the slot of its
-        name (`l3.ff1_ln_g` -> layer 3, FF1_LN_G), matrices in bf16, the rest in fp32, plus the three things only the forward kernels want (below)."""
+        name (`l3.ff1_ln_g` -> layer 3, FF1_LN_G), matrices in bf16, the rest in fp32, plus the three things only the forward kernels want (below).
+        precision="fp32": the same slots, every one of them fp32 (matrices included), no fold tensors."""
         c, dev = self.cfg, self.device
         d, C2 = c["hidden_size"], c["conv_dim"][1]
         m = _enc_map(c)
         slots = [None] * (_lib.GLOBAL_SLOTS + (c["num_hidden_layers"] + self.extra) * _lib.LAYER_SLOTS)
-        fold = self._fold_shapes_ok()
+        f32 = self.precision == "fp32"
+        fold = self._fold_shapes_ok() and not f32
         layer = {}                                   # fp32 packed tensors of the layer being walked, by short name (ln_fold reads them)
         for s, t in packed(encoder_specs(c), m, mapped_fp32(m, sd, dev)):
             if s.name == "masked_spec_embed":        # SpecAugment's fill vector: training only
@@ -119,7 +148,7 @@ class EBranchformerEngine:
             if self.ctx_mode == 1 and n in ("conv2_w", "conv2_b"):
                 # packed: conv rows then gate rows; the one implicit GEMM's epilogue wants [conv blk ; gate blk] per 2*blk rows (gemm_8p.hip GATED / mi_gated_act_bf16)
                 t = t.reshape(2, C2 // self.gate_blk, self.gate_blk, -1).transpose(0, 1).reshape(s.shape)
-            w = t.to(torch.bfloat16).contiguous() if s.mat else t.contiguous()
+            w = t.to(torch.bfloat16).contiguous() if (s.mat and not f32) else t.contiguous()
             slots[base + names[SLOT_RENAME.get(n, n.upper())]] = w
             if n in ("att_wqkv", "att_bqkv"):        # the V-only GEMM reads row views of the packed [Wq; Wk; Wv]
                 slots[base + LS["ATT_WV" if s.mat else "ATT_BV"]] = w[2 * d:]
@@ -140,6 +169,8 @@ class EBranchformerEngine:
     def share_weights_from(self, other: "EBranchformerEngine") -> None:
         """Adopt `other`'s packed weight table (the same device tensors: bf16 weights, fold tensors, biases) instead of packing a state dict again — the lane engines of a
         `ForwardPipeline` differ in workspace and position cache only (four lanes held four copies of the weights and ran the load-time packing four times)."""
+        if self.precision == "fp32" or other.precision == "fp32":
+            raise NotImplementedError("precision='fp32' does not cover ForwardPipeline lanes (share_weights_from): use the default precision='bf16'")
         if other._table is None or other.device != self.device:
             raise ValueError("share_weights_from: the source engine must have its weights loaded on the same device")
         self._keep, self._slots, self._table = other._keep, other._slots, other._table
@@ -156,6 +187,9 @@ class EBranchformerEngine:
                 and c.get("position_embeddings_type", "relative") != "rotary" and not c.get("csgu_use_linear_after_conv", False))
 
     def _use_fold(self, B: int, T2: int) -> bool:
+        if self.precision == "fp32":
+            self._refuse_fp32_options()                   # ln_fold / wide_tiles / branch_overlap set after construction
+            return False
         if not self._fold_shapes_ok() or self.ln_fold is False or self.branch_overlap:
             return False
         return True if self.ln_fold else B * T2 >= 2048          # below that the 256x256 tiles cannot fill the chip: the small-problem kernels + LayerNorm kernels are faster
@@ -188,8 +222,8 @@ class EBranchformerEngine:
         if key in self._pos:
             return self._pos[key]
         d, H = c["hidden_size"], c["num_attention_heads"]
-        if ptype == "relative":
-            t = relative_position_table(T2, d).to(self.device).to(torch.bfloat16).contiguous()
+        if ptype == "relative":              # the sinusoid table in the precision of the GEMM that projects it
+            t = relative_position_table(T2, d).to(self.device).to(torch.float32 if self.precision == "fp32" else torch.bfloat16).contiguous()
         elif ptype == "rotary":   # one buffer: [cos.flat ; sin.flat]
             cos, sin = rotary_tables(T2, d // H, c.get("rotary_embedding_base", 10000))
             t = torch.cat([cos.reshape(-1), sin.reshape(-1)]).to(self.device).contiguous()
@@ -217,7 +251,7 @@ class EBranchformerEngine:
         if self._ws.get("key") != key:
             self._ws = {"key": key}                                                        # keep one shape resident
         if slot not in self._ws:
-            nbytes = _lib.lib().mi_ebf_workspace_bytes(C.byref(cs))
+            nbytes = (_lib.lib().mi_ebf_f32_workspace_bytes if self.precision == "fp32" else _lib.lib().mi_ebf_workspace_bytes)(C.byref(cs))
             self._ws[slot] = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         return self._ws[slot]
 
@@ -233,6 +267,8 @@ class EBranchformerEngine:
             raise RuntimeError("EBranchformerEngine: load_state_dict() first")
         if not feats.is_cuda:
             raise RuntimeError("EBranchformerEngine.forward needs device tensors (no CPU fallback)")
+        if self.precision == "fp32" and slot != 0:
+            raise NotImplementedError("precision='fp32' does not cover ForwardPipeline lanes (slot != 0): use the default precision='bf16'")
         feats = feats.to(torch.float32).contiguous()
         B, T, F = feats.shape
         c = self.cfg
@@ -248,7 +284,8 @@ class EBranchformerEngine:
         posp, compute = None, 0
         if cs.pos_type == 1:
             if T2 not in self._posp:
-                self._posp = {T2: torch.empty((c["num_hidden_layers"] + self.extra, 2 * T2 - 1, d), dtype=torch.bfloat16, device=self.device)}
+                self._posp = {T2: torch.empty((c["num_hidden_layers"] + self.extra, 2 * T2 - 1, d), dtype=torch.float32 if self.precision == "fp32" else torch.bfloat16,
+                                              device=self.device)}
                 self._posp_valid = {}
             posp = self._posp[T2]
             compute = 0 if self._posp_valid.get(T2) == self.weights_version else 1
@@ -266,7 +303,9 @@ class EBranchformerEngine:
         With `head_argmax` on (the default; and a head that fits the fused kernel) no logits tensor is allocated; `slot` as in forward().
         beams=W (1..64): the forward with fp32-or-`logits_dtype` logits, then ops.ctc_beam_decode over them with the same lengths (W hypotheses, the `token_topk` best
         classes per frame, None = min(W, V)): tokens / n_tokens[/ frames] are the best hypothesis' (tokens (B,T2)), and the dict gains nbest_tokens (B,nbest,T2),
-        nbest_n (B,nbest), scores (B,nbest) fp32[, nbest_frames (B,nbest,T2)]; no `best`."""
+        nbest_n (B,nbest), scores (B,nbest) fp32[, nbest_frames (B,nbest,T2)]; no `best`.
+        precision="fp32": the fp32 head GEMM writes its logits into a scratch, mi_row_argmax reads it and mi_ctc_collapse follows; `head_argmax` / `head_lse` are
+        ignored in this mode (there is no fused fp32 head).  beams=W runs ops.ctc_beam_decode over the fp32 logits as above."""
         if span not in ("valid", "all"):
             raise ValueError(f"transcribe: span must be 'valid' or 'all', got {span!r}")
         if beams is not None:
@@ -277,6 +316,14 @@ class EBranchformerEngine:
                        inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
             if return_frames:
                 out.update(frames=bo["frames"][:, 0], nbest_frames=bo["frames"])
+            if want_hidden:
+                out["last_hidden"] = fwd["last_hidden"]
+            return out
+        if self.precision == "fp32":
+            fwd = self.forward(feats, feat_lengths, want_hidden=want_hidden, want_logits=True, slot=slot)
+            best = ops.row_argmax(fwd["logits"].flatten(0, 1)).view(fwd["logits"].shape[:2])
+            out = ops.ctc_collapse(best, self.cfg["vocab_size"], pad_id, fwd["outer_len"] if span == "valid" else None, return_frames=return_frames, dtype=dtype)
+            out.update(best=best, inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
             if want_hidden:
                 out["last_hidden"] = fwd["last_hidden"]
             return out
@@ -310,7 +357,10 @@ class EBranchformerEngine:
         """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
         Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also
         hidden_states = the L+1 tensors HF returns for output_hidden_states (every layer's input, then the last hidden state).
-        `slot` selects a private workspace: calls issued on different streams must use different slots."""
+        `slot` selects a private workspace: calls issued on different streams must use different slots.
+        precision="fp32": the same dictionary out of mi_ebf_forward_f32 (logits fp32; `lse` None; want_all_hidden is not covered)."""
+        if self.precision == "fp32" and want_all_hidden:
+            raise NotImplementedError("precision='fp32' does not cover want_all_hidden (output_hidden_states): use the default precision='bf16'")
         feats, cs, T2, ws, pos, posp, compute = self._prepare(feats, slot)
         B, c = feats.shape[0], self.cfg
         d, V1 = c["hidden_size"], c["vocab_size"] + 1
@@ -323,6 +373,11 @@ class EBranchformerEngine:
         if feat_lengths is not None:
             feat_lengths = feat_lengths.to(device=self.device, dtype=torch.int32).contiguous()
         p = lambda t: None if t is None else t.data_ptr()
+        if self.precision == "fp32":
+            rc = _lib.lib().mi_ebf_forward_f32(C.byref(cs), self._table, feats.data_ptr(), p(feat_lengths), p(pos), p(posp), compute, ws.data_ptr(), ws.numel(),
+                                               p(hidden), p(lbuf), lens[0].data_ptr(), lens[1].data_ptr(), torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "mi_ebf_forward_f32")
+            return dict(logits=logits, last_hidden=hidden, inner_len=lens[0], outer_len=lens[1], lse=None)
         # fp32 logits come with their rows' log-sum-exp (B*T2) out of the head GEMM's epilogue: `ops.ctc_loss(..., lse=out["lse"])` then needs no pass of its own over them
         lse = lse_ws = None
         if want_logits and self.logits_dtype == torch.float32 and self.head_lse:

@@ -12,6 +12,7 @@ optimizer; dropout, LayerDrop, in-model SpecAugment (counter-based masks) and ca
 step does not cover raise NotImplementedError rather than silently falling back to PyTorch."""
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple, Union
 
 import torch
@@ -218,9 +219,14 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
     def _weights_version(self):
         return sum(p._version for p in self._param_list())
 
+    def _precision(self) -> str:
+        """numeric mode of the HIP inference engine: `config.hip_precision`, else the environment variable HFASR_PRECISION, else "bf16" ("fp32": engine.py)"""
+        return getattr(self.config, "hip_precision", None) or os.environ.get("HFASR_PRECISION") or "bf16"
+
     def _get_engine(self, device) -> EBranchformerEngine:
-        if self._engine is None or self._engine.device != torch.device(device):
-            self._engine = EBranchformerEngine(cfg_from_hf(self.config), device)
+        prec = self._precision()
+        if self._engine is None or self._engine.device != torch.device(device) or self._engine.precision != prec:
+            self._engine = EBranchformerEngine(cfg_from_hf(self.config), device, precision=prec)
             self._engine_key = None
         pl = self._param_list()
         from .autograd_bridge import bridge_generation
@@ -295,6 +301,8 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
         if not input_values.is_cuda:
             raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): inputs must be on the GPU; there is no CPU fallback")
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self._precision() == "fp32":
+                raise NotImplementedError("hip_precision='fp32' is an inference mode: the HIP trainer is bf16-only (call model.eval(), or train with the default precision)")
             return self._training_forward(input_values, attention_mask, labels, output_hidden_states, return_dict)
         eng = self._get_engine(input_values.device)
         feat_len = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None

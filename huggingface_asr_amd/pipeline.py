@@ -32,9 +32,11 @@ def reserve_hw_queues(lanes: int) -> int:
 
 
 class ForwardPipeline:
-    def __init__(self, cfg: dict, device, state_dict: dict, lanes: int = 2, wide_tiles: bool = False):
+    def __init__(self, cfg: dict, device, state_dict: dict, lanes: int = 2, wide_tiles: bool = False, precision: str = "bf16"):
         if lanes < 1:
             raise ValueError("lanes >= 1")
+        if precision != "bf16":      # the lanes share one bf16 weight table and run the folded / wide-tile kernels: the fp32 mode (engine.py) has neither
+            raise NotImplementedError(f"ForwardPipeline lanes run in precision='bf16' only, got {precision!r}")
         self.device = torch.device(device)
         if lanes > 3 and int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) < 8:
             import warnings

@@ -705,6 +705,46 @@ int mi_ebf_forward_greedy(const mi_ebf_config* cfg, const void* const* weights, 
                           const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
                           float* last_hidden, int* best, float* argmax_workspace, void* head_scratch, int* inner_len, int* outer_len, mi_stream_t stream);
 
+/* ---- precision = "fp32" inference mode (csrc/gemm_f32.hip, csrc/encoder_f32.hip): the encoder + CTC head with every operand, activation and weight in fp32 — what the
+ * reference's decode recipes (no --bf16) compute.  Opt-in; nothing above changes.  DESIGN.md §4 'fp32 inference mode'. */
+/* C (M,N) = resid + alpha * act(A (M,K) · W (N,K)^T + bias), all fp32, row-major with leading dimensions; act 0 none / 1 erf-GELU (exact erff); bias, resid nullable,
+ * resid may alias C.  f32-input MFMA (v_mfma_f32_32x32x2_f32), LDS-tiled; any M, N, K >= 1 (edges zero-filled / guarded).  An element is the k-ordered fmaf chain over
+ * its row of A and its row of W: no split-K, no atomics, run-to-run bit-identical. */
+int mi_gemm_f32(const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc, const float* resid, long ldr,
+                float alpha, int act, int M, int N, int K, mi_stream_t stream);
+/* y = LayerNorm(x) with fp32 statistics (two passes) and fp32 output; lengths (nullable): rows at t >= lengths[b] (row = b*T + t) are zeroed first, x_out (nullable, may
+ * alias x) receives the rows after that zeroing.  y may alias x. */
+int mi_layernorm_f32(const float* x, long ldx, const int* lengths, int T, float* x_out, long ldxo, const float* gamma, const float* beta, float eps,
+                     float* y, long ldy, int M, int d, mi_stream_t stream);
+int mi_rotary_f32(const float* x, long ldx, float* y, long ldy, const float* cos_t, const float* sin_t, int M, int T, int H, int hd, mi_stream_t stream);
+/* depthwise Conv1d over time on (B*T, C) rows, weight (C, K): v[t,c] = bias[c] + sum_k w[c,k] x[t - pad_left + k*dilation, c], zero outside [0, T).
+ * mode 0: y = v; 1: y = gate * act(v) (CSGU; act 0 identity, 1 gelu, 2 relu, 3 silu); 2: y = x + v (the merge's residual). */
+int mi_dwconv_f32(const float* x, long ldx, const float* w, const float* bias, const float* gate, long ldg, float* y, long ldy,
+                  int B, int T, int C, int K, int pad_left, int dilation, int act, int mode, mi_stream_t stream);
+int mi_gate_act_mul_f32(const float* r, long ldr, const float* g, long ldg, float* s, long lds, int M, int N, int act, mi_stream_t stream);
+/* the two Conv2d + GELU layers of the front end in fp32, same geometry arguments as mi_conv2d_first_gelu / mi_conv2d_cl_bf16; activations channels-last fp32.
+ * mi_conv2d_cl_f32 is an implicit GEMM: the (kh, kw, cin) window is gathered inside mi_gemm_f32's A load, no im2col buffer exists. */
+int mi_conv2d_first_gelu_f32(const float* x, const float* w, const float* bias, float* out_cl, int B, int T, int F, int C, int K, int stride,
+                             int pad_t, int pad_f, int T1, int F1, mi_stream_t stream);
+int mi_conv2d_cl_f32(const float* in, const float* weight, const float* bias, float* out, int B, int Tin, int Fin, int Cin, int Cout, int K, int stride,
+                     int pad_t, int pad_f, int Tout, int Fout, int act, mi_stream_t stream);
+/* fp32 attention (e_branchformer.py:74-141): fp32 scores materialised in workspace, fp32 softmax, fp32 P·V.  posp (2T-1, H*hd) / bias_u / bias_v: all three or none.
+ * A key >= lengths[b], or above the diagonal when causal, contributes exactly 0.  The workspace is walked in chunks of utterances (of query rows when one utterance
+ * alone does not fit): mi_attention_f32_workspace_bytes never exceeds MI_ATTENTION_F32_SCORES_BYTES (or one query row, if that is larger), whatever B and T. */
+#define MI_ATTENTION_F32_SCORES_BYTES (64L << 20)
+size_t mi_attention_f32_workspace_bytes(int B, int T, int H, int hd, int relative);
+int mi_attention_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const float* posp, long ldp, const float* bias_u,
+                     const float* bias_v, const int* lengths, float* out, long ldo, int B, int T, int H, int hd, float scale, int causal,
+                     void* workspace, size_t workspace_bytes, mi_stream_t stream);
+/* mi_ebf_forward in fp32: the same config struct and the same slot order, EVERY slot (matrices included) pointing at fp32; pos_table: the relative sinusoid table in
+ * fp32 (rotary: as above); posp (L, 2*T2-1, d) fp32; logits (B*T2, logits_ld or V+1) fp32.  Layer order and residual arithmetic are those of mi_ebf_forward's un-folded
+ * branch.  MI_ERR_UNSUPPORTED, before anything is launched, for context_mode != 0, layer_mixing, extra_layers, ln_fold, wide_tiles, branch_overlap
+ * (mi_ebf_f32_workspace_bytes returns 0 for those).  The workspace needs no initialisation. */
+size_t mi_ebf_f32_workspace_bytes(const mi_ebf_config* cfg);
+int mi_ebf_forward_f32(const mi_ebf_config* cfg, const void* const* weights, const float* feats, const int* feat_lengths,
+                       const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
+                       float* last_hidden, float* logits, int* inner_len, int* outer_len, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
