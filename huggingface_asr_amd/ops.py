@@ -372,6 +372,23 @@ def row_argmax(x):
     return out
 
 
+def whisper_timestamp_argmax(logits, ids, *, begin_index, cur_len, no_timestamps_token_id, eos_token_id, max_initial_timestamp_index=None, detect_from_logprob=True):
+    """logits (B, V) fp32 (contiguous rows, any row stride), ids (B, Lmax) int64 -> (B) int32 = argmax(WhisperTimeStampLogitsProcessor(ids[:, :cur_len], logits)) of
+    transformers, with `row_argmax`'s rules; ids[:, begin_index:cur_len] are the sampled tokens (mi_whisper_timestamp_argmax: one pass over logits)."""
+    _req(logits, torch.float32); _req(ids, torch.long)
+    if logits.dim() != 2 or logits.stride(1) != 1 or ids.dim() != 2 or ids.stride(1) != 1 or ids.shape[0] != logits.shape[0]:
+        raise TypeError("whisper_timestamp_argmax: logits (B, V) fp32 and ids (B, Lmax) int64, both with contiguous rows")
+    B, V = logits.shape
+    if not 0 <= begin_index <= cur_len <= ids.shape[1]:
+        raise ValueError(f"whisper_timestamp_argmax: need 0 <= begin_index ({begin_index}) <= cur_len ({cur_len}) <= {ids.shape[1]}")
+    out = torch.empty((B,), device=logits.device, dtype=torch.int32)
+    rc = _lib.lib().mi_whisper_timestamp_argmax(logits.data_ptr(), logits.stride(0), V, ids.data_ptr(), ids.stride(0), int(begin_index), int(cur_len),
+                                                int(no_timestamps_token_id), int(eos_token_id), -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index),
+                                                1 if detect_from_logprob else 0, out.data_ptr(), B, _stream())
+    _lib.check(rc, "mi_whisper_timestamp_argmax")
+    return out
+
+
 def gemm_argmax(a, w, bias):
     """the CTC head without its logits: -> (M) int32 = argmax_n (a W^T + b)[m, n] out of the GEMM's epilogue (mi_gemm_argmax_bf16: no (M, N) tensor is written);
     shapes outside that kernel: the fp32 GEMM into a scratch followed by row_argmax."""

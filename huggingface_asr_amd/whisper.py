@@ -508,14 +508,45 @@ class WhisperDecoderEngine(GPT2DecoderEngine):
         return G
 
 
+def encode_for_decoding(enc_engine, dec_engine, input_features, Lmax):
+    """The state a token loop starts from: the encoder run ONCE, its frames as every layer's cross K/V, and an empty KV cache of Lmax positions ->
+    dict(kvs, T2, cache).  `detect_language` advances the cache by the start token; `greedy_decode(state=...)` goes on from there."""
+    if not input_features.is_cuda:
+        raise RuntimeError("encode_for_decoding needs device tensors (no CPU fallback)")
+    enc = enc_engine.forward(input_features=input_features)
+    B, T2, d = enc.shape
+    return dict(kvs=dec_engine.cross_kv(ops.cast_bf16(enc.reshape(B * T2, d))), T2=T2, cache=dec_engine.init_cache(B, Lmax))
+
+
+def detect_language(dec_engine, state, start_token_id, lang_ids):
+    """transformers' `WhisperGenerationMixin.detect_language` on the HIP path -> (B) int64 language token ids: one decoder step over [start_token_id] whose head bias is 0
+    on `lang_ids` and -inf elsewhere, then `mi_row_argmax`.  The step stays in `state`'s KV cache (past = 1), so the prompt's remaining positions follow it."""
+    cache = state["cache"]
+    if cache["past"] != 0:
+        raise ValueError("detect_language is the first step on a fresh cache")
+    V = dec_engine.cfg["vocab_size"]
+    lang_ids = sorted({int(i) for i in lang_ids})
+    if not lang_ids or lang_ids[0] < 0 or lang_ids[-1] >= V:
+        raise ValueError(f"language token ids outside the vocabulary [0, {V})")
+    B = cache["k"][0].shape[0]
+    bias = torch.full((V,), float("-inf"), dtype=torch.float32, device=dec_engine.device)
+    bias[torch.tensor(lang_ids, device=dec_engine.device)] = 0.0
+    start = torch.full((B, 1), int(start_token_id), dtype=torch.long, device=dec_engine.device)
+    return ops.row_argmax(dec_engine.step(start, cache, state["kvs"], state["T2"], bias)).to(torch.long)
+
+
 def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new_tokens, eos_token_id, pad_token_id, suppress_tokens=None, begin_suppress_tokens=None,
-                  run_ahead=2, stats=None):
+                  run_ahead=2, stats=None, timestamps=None, state=None):
     """Greedy transcription with the loop on the device -> (B, P + n) LongTensor: per row the prompt, the generated tokens, the first EOS (kept), then pad_token_id —
     `GenerationMixin`'s greedy layout, trimmed to the longest row.  Per token: the decoder step with the suppression vector as the head's bias (the begin-suppress ids in
     the first generated token's only), `mi_row_argmax`, and one kernel that appends the token (pad for a finished row), hands it to the next step and sets the row's done
     flag at EOS, writing the flags into pinned memory.  The host only enqueues, at most `run_ahead` steps in front of the flags it has seen, and stops once every row is
-    done; nothing is copied per token.  The prompt (B, P) is consumed by one step of P positions.  `stats` receives the number of steps enqueued."""
-    if not input_features.is_cuda or not prompt_ids.is_cuda:
+    done; nothing is copied per token.  The prompt (B, P) is consumed by one step of P positions.  `stats` receives the number of steps enqueued.
+    `timestamps` = dict(no_timestamps_token_id, max_initial_timestamp_index (None = no limit), detect_from_logprob): every token is chosen under transformers'
+    `WhisperTimeStampLogitsProcessor` with begin_index = P — `mi_whisper_timestamp_argmax` over the step's logits and the device-resident ids in place of `mi_row_argmax`.
+    `state` (from `encode_for_decoding`; input_features is then not read): the encoder output / cross K/V to decode on and a KV cache that already holds the first
+    `cache["past"]` prompt positions (the start token after `detect_language`); the first step consumes the rest of the prompt."""
+    if (state is None and not input_features.is_cuda) or not prompt_ids.is_cuda:
         raise RuntimeError("greedy_decode needs device tensors (no CPU fallback)")
     dev = dec_engine.device
     B, P = prompt_ids.shape
@@ -527,16 +558,27 @@ def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new
         if not 0 <= int(t) < V:
             raise ValueError(f"{name} {t} outside the vocabulary [0, {V})")
     every, first = suppression_vectors(V, suppress_tokens, begin_suppress_tokens, dev)
-    enc = enc_engine.forward(input_features=input_features)
-    T2, d = enc.shape[1], enc.shape[2]
-    kvs = dec_engine.cross_kv(ops.cast_bf16(enc.reshape(B * T2, d)))
     Lmax = P + max_new_tokens
-    cache = dec_engine.init_cache(B, Lmax)
+    if timestamps is not None:
+        ts = dict(no_timestamps_token_id=int(timestamps["no_timestamps_token_id"]), eos_token_id=int(eos_token_id),
+                  max_initial_timestamp_index=timestamps.get("max_initial_timestamp_index"), detect_from_logprob=bool(timestamps.get("detect_from_logprob", True)))
+        if not 0 <= ts["no_timestamps_token_id"] < V:
+            raise ValueError(f"no_timestamps_token_id {ts['no_timestamps_token_id']} outside the vocabulary [0, {V})")
+    if state is None:
+        enc = enc_engine.forward(input_features=input_features)
+        T2, d = enc.shape[1], enc.shape[2]
+        kvs = dec_engine.cross_kv(ops.cast_bf16(enc.reshape(B * T2, d)))
+        cache = dec_engine.init_cache(B, Lmax)
+    else:
+        kvs, T2, cache = state["kvs"], state["T2"], state["cache"]
+        if cache["k"][0].shape[0] != B or cache["Lmax"] < Lmax or not 0 <= cache["past"] < P:
+            raise ValueError(f"state does not fit: its cache holds {cache['k'][0].shape[0]} rows x {cache['Lmax']} positions with {cache['past']} consumed; "
+                             f"decoding needs {B} rows x {Lmax} positions and a prompt of {P} > consumed")
     ids = torch.full((B, Lmax), int(pad_token_id), dtype=torch.long, device=dev)
     ids[:, :P] = prompt_ids
     done = torch.zeros((B,), dtype=torch.int32, device=dev)
     done_host = torch.zeros((max_new_tokens, B), dtype=torch.int32).pin_memory()
-    new_tok = prompt_ids.to(torch.long).contiguous()
+    new_tok = prompt_ids[:, cache["past"]:].to(torch.long).contiguous()
     L_ = _lib.lib()
     main = torch.cuda.current_stream()
     flags, steps = [], 0
@@ -546,7 +588,7 @@ def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new
             if bool(done_host[steps - run_ahead].all()):
                 break
         logits = dec_engine.step(new_tok, cache, kvs, T2, first if steps == 0 else every)
-        best = ops.row_argmax(logits)
+        best = ops.row_argmax(logits) if timestamps is None else ops.whisper_timestamp_argmax(logits, ids, begin_index=P, cur_len=P + steps, **ts)
         new_tok = torch.empty((B, 1), dtype=torch.long, device=dev)
         _lib.check(L_.mi_greedy_advance(best.data_ptr(), ids.data_ptr(), Lmax, P + steps, int(eos_token_id), int(pad_token_id), done.data_ptr(), new_tok.data_ptr(),
                                         done_host[steps].data_ptr(), B, main.cuda_stream), "mi_greedy_advance")
@@ -566,8 +608,125 @@ def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new
     return ids[:, :P + n]
 
 
-_GENERATE_REFUSED = ("logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "assistant_model", "streamer", "prompt_ids", "language", "task", "is_multilingual",
-                     "negative_prompt_ids", "forced_decoder_ids")
+_GENERATE_REFUSED = ("logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "assistant_model", "streamer", "prompt_ids", "negative_prompt_ids")
+
+
+LANGUAGE_TO_DETECT = -1          # stands in the language slot of `prompt_template`'s rows where the language has to be detected
+
+
+def build_prompt(generation_config, config, batch_size, *, language=None, task=None, is_multilingual=None, return_timestamps=False, detect_language=None):
+    """The decoder prompt of one segment -> `batch_size` equal-length lists of token ids: transformers' `WhisperGenerationMixin._set_language_and_task` followed by
+    `_retrieve_init_tokens` (models/whisper/generation_whisper.py), restated without a model and without touching `generation_config`: decoder_start_token_id (the model
+    config's when the generation config has none); `forced_decoder_ids` of the (generation) config only when neither task nor language is set; the language — a name, a code
+    or a `<|xx|>` token, one string or one per row, mapped through `lang_to_id` — or, when none is given, the config has `lang_to_id` and the language slot is still open,
+    what `detect_language()` (-> batch_size ids) finds; the task (`transcribe` when only a language is given); `no_timestamps_token_id` appended unless `return_timestamps`,
+    and dropped where it is last and `return_timestamps` is set.  `language` / `task` None fall back to the attributes of `generation_config`.  Raises the ValueError /
+    TypeError transformers raises at the same inputs.  Pure host code: the only device work is inside the injected `detect_language`."""
+    rows, detect = prompt_template(generation_config, config, batch_size, language=language, task=task, is_multilingual=is_multilingual, return_timestamps=return_timestamps)
+    if detect:
+        if detect_language is None:
+            raise ValueError("the language has to be detected and no `detect_language` was given")
+        for r, lid in zip(rows, detect_language()):
+            r[1] = int(lid)
+    return rows
+
+
+def prompt_template(generation_config, config, batch_size, *, language=None, task=None, is_multilingual=None, return_timestamps=False):
+    """`build_prompt` up to the detection -> (rows, detect): with `detect` the language slot (index 1) of every row holds LANGUAGE_TO_DETECT for the caller to fill — the
+    prompt's length and every other token do not depend on WHICH language is found, so one call sizes the KV cache before the detection step runs."""
+    from transformers.models.whisper.tokenization_whisper import TASK_IDS, TO_LANGUAGE_CODE
+    gc = generation_config
+    issue = "https://github.com/huggingface/transformers/issues/25084#issuecomment-1664398224"
+    outdated = "The generation config is outdated and is thus not compatible with the `{}` argument to `generate`. Please update the generation config as per the instructions " + issue
+    multilingual = getattr(gc, "is_multilingual", None)
+    if is_multilingual is not None:
+        if not hasattr(gc, "is_multilingual"):
+            raise ValueError(outdated.format("is_multilingual"))
+        multilingual = is_multilingual
+    if (hasattr(gc, "is_multilingual") or is_multilingual is not None) and not multilingual and (task is not None or language is not None):
+        raise ValueError("Cannot specify `task` or `language` for an English-only model. If the model is intended to be multilingual, pass `is_multilingual=True` to generate, "
+                         "or update the generation config.")
+    if language is not None and not hasattr(gc, "lang_to_id"):
+        raise ValueError(outdated.format("language"))
+    if task is not None and not hasattr(gc, "task_to_id"):
+        raise ValueError(outdated.format("task"))
+    language = language if language is not None else getattr(gc, "language", None)
+    task = task if task is not None else getattr(gc, "task", None)
+
+    def language_to_id(lang):
+        lang = lang.lower()
+        if lang in gc.lang_to_id:
+            token = lang
+        elif lang in TO_LANGUAGE_CODE:
+            token = f"<|{TO_LANGUAGE_CODE[lang]}|>"
+        elif lang in TO_LANGUAGE_CODE.values():
+            token = f"<|{lang}|>"
+        else:
+            raise ValueError(f"Unsupported language: {lang}. Language should be one of: {list(TO_LANGUAGE_CODE.values()) if len(lang) == 2 else list(TO_LANGUAGE_CODE.keys())}.")
+        if token not in gc.lang_to_id:
+            raise ValueError(f"{token} is not supported by this specific model as it is not in the `generation_config.lang_to_id`. (You should just add it to the generation config)")
+        return gc.lang_to_id[token]
+
+    start = gc.decoder_start_token_id if getattr(gc, "decoder_start_token_id", None) is not None else getattr(config, "decoder_start_token_id", None)
+    if start is None:
+        raise ValueError("neither the generation config nor the model config has a decoder_start_token_id")
+    init = [start]
+    if task is None and language is None:
+        forced = getattr(gc, "forced_decoder_ids", None)
+        if forced is None and getattr(config, "forced_decoder_ids", None) is not None:
+            forced = config.forced_decoder_ids
+        if forced is not None and forced[0][0] == 1:
+            i = 1
+            while len(forced) > 0 and forced[0][0] == i:
+                init.append(forced[0][1])
+                forced = forced[1:]
+                i += 1
+            if len(forced) > 0:
+                raise ValueError(f"You are using token ids in `forced_decoder_ids` that do not seem to correctly follow the prompt pattern of Whisper. Make sure that {forced} "
+                                 f"has an entry for all indices >= 1 and < {forced[0][0]}.")
+    lang_slot_open = len(init) <= 1 or init[1] is None
+    if isinstance(language, (list, tuple)):
+        if any(l is None for l in language):
+            raise TypeError("Expected `language` to be `None`, a single string (e.g. `'en'`), or a list of strings with length equal to the batch size (e.g. `('en', 'fr')` for "
+                            "a batch size of 2). Got a list containing `None`.")
+        if len(language) != batch_size:
+            raise ValueError(f"When passing a list of languages, the length of the list must match the batch size. Expected length of {batch_size}, but got {len(language)} languages.")
+        languages = list(language)
+    elif language is None:
+        languages = [None] * batch_size
+    else:
+        languages = [language]                           # one row now, every row below
+    rows = [list(init) for _ in languages]
+    lang_ids, detect = None, False
+    if language is not None:
+        lang_ids = [language_to_id(l) for l in languages]
+    elif hasattr(gc, "lang_to_id") and lang_slot_open:
+        lang_ids, detect = [LANGUAGE_TO_DETECT] * len(rows), True
+    if lang_ids is not None:
+        for r, lid in zip(rows, lang_ids):
+            if len(r) > 1:
+                r[1] = lid
+            else:
+                r.append(lid)
+    out = []
+    for r in rows:
+        if task is not None:
+            if task not in TASK_IDS:
+                raise ValueError(f"The `{task}` task is not supported. The task should be one of `{TASK_IDS}`")
+            r.append(gc.task_to_id[task])                # (transformers appends; its replace_or_add after that changes nothing)
+        elif language is not None and hasattr(gc, "task_to_id"):
+            if not any(t in r for t in gc.task_to_id.values()):
+                r.append(gc.task_to_id["transcribe"])
+        if not return_timestamps and hasattr(gc, "no_timestamps_token_id") and r[-1] != gc.no_timestamps_token_id:
+            r.append(gc.no_timestamps_token_id)
+        elif return_timestamps and r[-1] == gc.no_timestamps_token_id:
+            r = r[:-1]
+        out.append([t for t in r if t is not None])
+    if len(out) == 1 and batch_size != 1:
+        out = [list(out[0]) for _ in range(batch_size)]
+    if any(len(r) != len(out[0]) for r in out) or len(out) != batch_size:
+        raise ValueError("the prompts of a batch must have one length")           # (torch.as_tensor over ragged rows, in transformers)
+    return out, detect
 
 
 def _decoder_engine_for(dec) -> WhisperDecoderEngine:
@@ -586,19 +745,68 @@ def _decoder_engine_for(dec) -> WhisperDecoderEngine:
     return eng
 
 
+def _token_rules(gc, cfg) -> dict:
+    """eos / pad / suppression ids of a generation config, as `greedy_decode` takes them"""
+    eos = gc.eos_token_id if gc.eos_token_id is not None else cfg.eos_token_id
+    if isinstance(eos, (list, tuple)):
+        if len(eos) != 1:
+            raise NotImplementedError("hip_generate takes one eos_token_id")
+        eos = eos[0]
+    pad = gc.pad_token_id if gc.pad_token_id is not None else cfg.pad_token_id
+    if eos is None or pad is None:
+        raise ValueError("generation_config needs eos_token_id and pad_token_id")
+    return dict(eos_token_id=int(eos), pad_token_id=int(pad), suppress_tokens=getattr(gc, "suppress_tokens", None), begin_suppress_tokens=getattr(gc, "begin_suppress_tokens", None))
+
+
+def _timestamp_rules(gc):
+    """`greedy_decode`'s `timestamps` of a generation config: what `WhisperTimeStampLogitsProcessor.__init__` reads"""
+    return dict(no_timestamps_token_id=gc.no_timestamps_token_id, max_initial_timestamp_index=getattr(gc, "max_initial_timestamp_index", None),
+                detect_from_logprob=getattr(gc, "_detect_timestamp_from_logprob", True))
+
+
+def _detected_prompt(model, gc, input_features, rows, detect, Lmax):
+    """-> (prompt (B, P) on the device, state or None) of `prompt_template`'s (rows, detect): where the language has to be detected the encoder runs here, once — the
+    detection step and the token loop share `state` (`encode_for_decoding` with a KV cache of Lmax positions)"""
+    state = None
+    if detect:
+        dec_eng = _decoder_engine_for(model.model.decoder)
+        dec_eng.ensure_positions(Lmax)
+        state = encode_for_decoding(_engine_for(model.model.encoder), dec_eng, input_features, Lmax)
+        for r, lid in zip(rows, detect_language(dec_eng, state, rows[0][0], gc.lang_to_id.values()).tolist()):
+            r[1] = lid
+    return torch.tensor(rows, dtype=torch.long, device=input_features.device), state
+
+
 def hip_generate(model, input_features, decoder_input_ids=None, max_new_tokens=None, max_length=None, **kw):
-    """Greedy transcription of a transformers `WhisperForConditionalGeneration` on the HIP path: the bound encoder, `WhisperDecoderEngine` and `greedy_decode`
-    (the recipes' case: `--num_beams=1 --predict_with_generate`).  eos / pad / suppress_tokens / begin_suppress_tokens come from `model.generation_config`; the prompt is
-    `decoder_input_ids`, or `[[decoder_start_token_id]]`.  Returns (B, P + n) ids in `GenerationMixin`'s greedy layout.  What it does not do is refused with
-    NotImplementedError before the device is touched — beams, sampling, timestamps, language / task prompts, custom processors or stopping criteria —: those stay
-    `model.generate`, which is transformers' own and not rerouted.  CPU tensors raise RuntimeError (no fallback)."""
+    """Greedy transcription of one 30 s segment of a transformers `WhisperForConditionalGeneration` on the HIP path: the bound encoder, `WhisperDecoderEngine` and
+    `greedy_decode` (the recipes' case: `--num_beams=1 --predict_with_generate`).  eos / pad / suppress_tokens / begin_suppress_tokens come from `model.generation_config`;
+    the prompt is `decoder_input_ids`, or what transformers' `generate` builds (`build_prompt`): decoder_start_token_id, then — as far as the generation config defines them
+    — the language (`language=`, one string or one per row; detected on the device when the model is multilingual and none is given), the task (`task=`), the
+    `forced_decoder_ids` of the (generation) config when neither is set, and `<|notimestamps|>` unless `return_timestamps=True`, which decodes under the timestamp rules
+    (`mi_whisper_timestamp_argmax`).  Returns (B, P + n) ids in `GenerationMixin`'s greedy layout, prompt included.  What it does not do is refused with
+    NotImplementedError before the device is touched — beams, sampling, custom processors or stopping criteria, prompt_ids, and language / task / timestamps on a
+    generation config that lacks their tables —: those stay `model.generate`.  CPU tensors raise RuntimeError (no fallback)."""
     gc, cfg = model.generation_config, model.config
     if kw.pop("num_beams", None) not in (None, 1) or (getattr(gc, "num_beams", 1) or 1) > 1:
         raise NotImplementedError("hip_generate is greedy: num_beams > 1 stays model.generate")
     if kw.pop("do_sample", None) or getattr(gc, "do_sample", False):
         raise NotImplementedError("hip_generate is greedy: do_sample stays model.generate")
-    if kw.pop("return_timestamps", None) or getattr(gc, "return_timestamps", False):
-        raise NotImplementedError("hip_generate does not apply the timestamp rules: return_timestamps stays model.generate")
+    return_timestamps = kw.pop("return_timestamps", None)
+    if return_timestamps is None:
+        return_timestamps = getattr(gc, "return_timestamps", None)
+    if return_timestamps not in (None, False, True):
+        raise NotImplementedError("hip_generate takes return_timestamps as a bool")
+    if return_timestamps and not hasattr(gc, "no_timestamps_token_id"):
+        raise NotImplementedError("hip_generate cannot apply the timestamp rules: the generation config has no no_timestamps_token_id (it stays model.generate)")
+    language, task, is_multilingual = kw.pop("language", None), kw.pop("task", None), kw.pop("is_multilingual", None)
+    for name, val, table in (("language", language, "lang_to_id"), ("task", task, "task_to_id"), ("is_multilingual", is_multilingual, "is_multilingual")):
+        if val is not None and not hasattr(gc, table):
+            raise NotImplementedError(f"hip_generate does not take {name}= on a generation config without {table}: it stays model.generate")
+    forced = kw.pop("forced_decoder_ids", None)
+    if forced is not None:
+        import copy
+        gc = copy.copy(gc)
+        gc.forced_decoder_ids = forced
     for k in _GENERATE_REFUSED:
         if kw.get(k) is not None:
             raise NotImplementedError(f"hip_generate does not take {k}=: it stays model.generate")
@@ -611,32 +819,28 @@ def hip_generate(model, input_features, decoder_input_ids=None, max_new_tokens=N
     frames = 2 * cfg.max_source_positions
     if input_features.dim() != 3 or input_features.shape[-1] != frames:
         raise NotImplementedError(f"hip_generate takes (B, mel, {frames}) input features (long-form and shorter inputs stay model.generate), got {tuple(input_features.shape)}")
+
+    def new_tokens_for(P):
+        n = max_new_tokens
+        if n is None:
+            n = (max_length if max_length is not None else (getattr(gc, "max_length", None) or cfg.max_target_positions)) - P
+        if n < 1:
+            raise ValueError(f"nothing to generate: max_new_tokens = {n}")
+        if P + n > cfg.max_target_positions:
+            raise ValueError(f"prompt ({P}) + max_new_tokens ({n}) exceeds max_target_positions = {cfg.max_target_positions}")
+        return n
     B = input_features.shape[0]
-    if decoder_input_ids is None:
-        start = gc.decoder_start_token_id if getattr(gc, "decoder_start_token_id", None) is not None else cfg.decoder_start_token_id
-        decoder_input_ids = torch.full((B, 1), int(start), dtype=torch.long, device=input_features.device)
-    P = decoder_input_ids.shape[1]
-    if max_new_tokens is None:
-        max_new_tokens = (max_length if max_length is not None else (getattr(gc, "max_length", None) or cfg.max_target_positions)) - P
-    if max_new_tokens < 1:
-        raise ValueError(f"nothing to generate: max_new_tokens = {max_new_tokens}")
-    if P + max_new_tokens > cfg.max_target_positions:
-        raise ValueError(f"prompt ({P}) + max_new_tokens ({max_new_tokens}) exceeds max_target_positions = {cfg.max_target_positions}")
-    eos = gc.eos_token_id if gc.eos_token_id is not None else cfg.eos_token_id
-    if isinstance(eos, (list, tuple)):
-        if len(eos) != 1:
-            raise NotImplementedError("hip_generate takes one eos_token_id")
-        eos = eos[0]
-    pad = gc.pad_token_id if gc.pad_token_id is not None else cfg.pad_token_id
-    if eos is None or pad is None:
-        raise ValueError("generation_config needs eos_token_id and pad_token_id")
-    if not input_features.is_cuda or not decoder_input_ids.is_cuda or not next(model.parameters()).is_cuda:
+    prompt_kw = dict(language=language, task=task, is_multilingual=is_multilingual, return_timestamps=bool(return_timestamps))
+    rows, detect = prompt_template(gc, cfg, B, **prompt_kw)                                   # raises what transformers raises
+    P = decoder_input_ids.shape[1] if decoder_input_ids is not None else len(rows[0])
+    n_new = new_tokens_for(P)
+    rules = _token_rules(gc, cfg)
+    if not input_features.is_cuda or (decoder_input_ids is not None and not decoder_input_ids.is_cuda) or not next(model.parameters()).is_cuda:
         raise RuntimeError("hip_generate needs the model and its inputs on the GPU (no CPU fallback)")
-    enc_eng = _engine_for(model.model.encoder)
-    dec_eng = _decoder_engine_for(model.model.decoder)
     with torch.no_grad():
-        return greedy_decode(enc_eng, dec_eng, input_features, decoder_input_ids, max_new_tokens=max_new_tokens, eos_token_id=int(eos), pad_token_id=int(pad),
-                             suppress_tokens=getattr(gc, "suppress_tokens", None), begin_suppress_tokens=getattr(gc, "begin_suppress_tokens", None))
+        prompt, state = (decoder_input_ids, None) if decoder_input_ids is not None else _detected_prompt(model, gc, input_features, rows, detect, P + n_new)
+        return greedy_decode(_engine_for(model.model.encoder), _decoder_engine_for(model.model.decoder), input_features, prompt, max_new_tokens=n_new,
+                             timestamps=_timestamp_rules(gc) if return_timestamps else None, state=state, **rules)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
@@ -644,7 +848,8 @@ def hip_generate(model, input_features, decoder_input_ids=None, max_new_tokens=N
 # `recipes_v0.0.1/decred/out_of_domain/decode_whisper_lumi.sh:60-66` `--from_pretrained=openai/whisper-medium --predict_with_generate`) runs HuggingFace's
 # `WhisperForConditionalGeneration` as it is, and `src/trainers/train_enc_dec_asr.py:82-83` tests `isinstance(model, WhisperForConditionalGeneration)` — so the class has
 # to stay HuggingFace's.  The drop-in is therefore a replacement of `WhisperEncoder.forward`: the encoder (the whole cost of config 4) runs on the HIP engine above;
-# `generate`, the loss and the checkpoint format stay transformers' own.  Greedy transcription on the HIP path is the separate entry `hip_generate` above.
+# `generate`, the loss and the checkpoint format stay transformers' own.  Greedy transcription on the HIP path is the separate entry `hip_generate` above, and — opt-in,
+# `install_whisper(generate=True)` — `generate` itself for the recipes' short-form greedy calls (`hip_whisper_generate` below).
 def _encoder_cfg(enc) -> dict:
     c = enc.config
     return dict(d_model=c.d_model, encoder_layers=c.encoder_layers, encoder_attention_heads=c.encoder_attention_heads, encoder_ffn_dim=c.encoder_ffn_dim)
@@ -908,6 +1113,210 @@ def hip_whisper_lm_forward(self, input_features=None, attention_mask=None, decod
                            encoder_attentions=o.encoder_attentions)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------------
+# `WhisperForConditionalGeneration.generate` on the HIP path (opt-in: `install_whisper(generate=True)`, HFASR_WHISPER_GENERATE=1): what the reference's Whisper decoding
+# recipes call through `Seq2SeqTrainer.prediction_step` (`--predict_with_generate --num_beams=1 --max_length=448`).  `generate_route` decides per call; the HIP side is
+# short-form greedy decoding, everything else runs transformers' own `generate` (`_hfasr_reference_generate`).
+_GENERATE_TAKEN = ("input_features", "generation_config", "attention_mask", "max_length", "max_new_tokens", "num_beams", "do_sample", "decoder_input_ids", "language", "task",
+                   "is_multilingual", "return_timestamps", "return_dict_in_generate", "synced_gpus", "temperature",
+                   "labels")              # `Seq2SeqTrainer.prediction_step` leaves the collator's labels among generate's inputs; transformers' generate does not read them
+# keyword arguments of `generate` the HIP path hands over when they are set, and the reason it gives
+_GENERATE_HANDED_OVER = (("prompt_ids", "prompt_ids"), ("prompt_condition_type", "prompt_ids"), ("condition_on_prev_tokens", "condition_on_prev_tokens"),
+                         ("return_token_timestamps", "return_token_timestamps"), ("return_segments", "return_segments"),
+                         ("no_speech_threshold", "no_speech_threshold / logprob_threshold / compression_ratio_threshold"),
+                         ("logprob_threshold", "no_speech_threshold / logprob_threshold / compression_ratio_threshold"),
+                         ("compression_ratio_threshold", "no_speech_threshold / logprob_threshold / compression_ratio_threshold"),
+                         ("logits_processor", "custom logits processors / stopping criteria"), ("stopping_criteria", "custom logits processors / stopping criteria"),
+                         ("prefix_allowed_tokens_fn", "custom logits processors / stopping criteria"), ("streamer", "streamer"), ("assistant_model", "assistant model"),
+                         ("force_unique_generate_call", "force_unique_generate_call"), ("monitor_progress", "monitor_progress"), ("encoder_outputs", "encoder_outputs instead of input_features"))
+# generation-config attributes that make `GenerationMixin.generate` add a logits processor or a stopping rule the device loop does not run: they must be unset (or neutral)
+_GENERATION_CONFIG_NEUTRAL = dict(repetition_penalty=1.0, encoder_repetition_penalty=1.0, no_repeat_ngram_size=0, encoder_no_repeat_ngram_size=0, bad_words_ids=None,
+                                  min_length=0, min_new_tokens=None, forced_bos_token_id=None, forced_eos_token_id=None, exponential_decay_length_penalty=None,
+                                  sequence_bias=None, guidance_scale=None, watermarking_config=None, renormalize_logits=False, remove_invalid_values=False, stop_strings=None,
+                                  max_time=None, num_return_sequences=1, output_scores=False, output_logits=False, output_attentions=False, output_hidden_states=False,
+                                  num_beam_groups=1, penalty_alpha=None, prompt_lookup_num_tokens=None, cache_implementation=None)
+
+
+def generate_route(kwargs: dict, generation_config, config, input_shape) -> tuple[str, str | None]:
+    """Where a `WhisperForConditionalGeneration.generate(**kwargs)` call runs: ("hip", None) or ("stock", reason) — transformers' own generate, said once per reason;
+    HFASR_WHISPER_STRICT=1 raises.  `kwargs`: the call's keyword arguments; `generation_config`: the one the call decodes under (the model's with the call's overrides
+    applied, `GenerationMixin._prepare_generation_config`); `input_shape`: of input_features, or None.  Pure: tensors are only asked for `.is_cuda`.
+    HIP: greedy (num_beams 1 / None, no sampling), short-form input (B, mel, 2 max_source_positions) on the GPU, max_length / max_new_tokens, decoder_input_ids, language
+    (a string or one per row), task, is_multilingual, forced_decoder_ids of the (generation) config, return_timestamps as a bool, attention_mask (not read for short-form
+    input, as in transformers), return_dict_in_generate False, labels (`Seq2SeqTrainer.prediction_step` passes the collator's along; not read, as in transformers)."""
+    g, gc = kwargs.get, generation_config
+    for name, why in _GENERATE_HANDED_OVER:
+        if g(name) is not None and g(name) is not False:
+            return "stock", why
+    if (g("num_beams") or getattr(gc, "num_beams", 1) or 1) > 1:
+        return "stock", "num_beams > 1"
+    temperature = g("temperature")
+    if isinstance(temperature, (list, tuple)):
+        if len(temperature) != 1:
+            return "stock", "temperature fallback"
+        temperature = temperature[0]
+    if g("do_sample") or (g("do_sample") is None and getattr(gc, "do_sample", False)) or (temperature is not None and temperature > 0.0):
+        return "stock", "sampling"
+    if g("return_dict_in_generate") or (g("return_dict_in_generate") is None and getattr(gc, "return_dict_in_generate", False)):
+        return "stock", "return_dict_in_generate"
+    if g("synced_gpus"):
+        return "stock", "synced_gpus"
+    extra = sorted(k for k, v in kwargs.items() if k not in _GENERATE_TAKEN and k not in dict(_GENERATE_HANDED_OVER) and v is not None
+                   and not hasattr(gc, k))                  # (a parameter of the generation config is judged there, below)
+    if extra:
+        return "stock", f"keyword arguments {extra}"
+    for name in ("condition_on_prev_tokens", "no_speech_threshold", "logprob_threshold", "compression_ratio_threshold", "return_token_timestamps", "force_unique_generate_call"):
+        if getattr(gc, name, None):
+            return "stock", f"generation_config.{name}"
+    for name, neutral in _GENERATION_CONFIG_NEUTRAL.items():
+        val = getattr(gc, name, None)
+        if val is not None and val != neutral:
+            return "stock", f"generation_config.{name}"
+    if input_shape is None or len(input_shape) != 3 or input_shape[-1] != 2 * config.max_source_positions:
+        return "stock", "long-form input, or input features that are not (B, mel, 2 max_source_positions)"
+    rt = g("return_timestamps")
+    if rt is None:
+        rt = getattr(gc, "return_timestamps", None)
+    if rt not in (None, False, True):
+        return "stock", "return_timestamps that is not a bool"
+    if rt and not hasattr(gc, "no_timestamps_token_id"):
+        return "stock", "return_timestamps on a generation config without no_timestamps_token_id"
+    for name, table in (("language", "lang_to_id"), ("task", "task_to_id"), ("is_multilingual", "is_multilingual")):
+        if g(name) is not None and not hasattr(gc, table):
+            return "stock", f"{name} on a generation config without {table}"
+    eos = gc.eos_token_id if getattr(gc, "eos_token_id", None) is not None else getattr(config, "eos_token_id", None)
+    if eos is None or (isinstance(eos, (list, tuple)) and len(eos) != 1) or (getattr(gc, "pad_token_id", None) is None and getattr(config, "pad_token_id", None) is None):
+        return "stock", "not exactly one eos_token_id, or no pad_token_id"
+    if g("max_new_tokens") is None and g("max_length") is None and getattr(gc, "max_new_tokens", None) is None and getattr(gc, "max_length", None) is None:
+        return "stock", "neither max_length nor max_new_tokens"
+    if getattr(config, "scale_embedding", False):
+        return "stock", "scale_embedding"
+    for name in ("input_features", "decoder_input_ids"):
+        if g(name) is not None and not getattr(g(name), "is_cuda", False):
+            return "stock", "CPU tensors"
+    return "hip", None
+
+
+def _stock_generate(self, why, kwargs):
+    """`_stock_forward` for `generate`: transformers' own `WhisperForConditionalGeneration.generate`, said once per reason; HFASR_WHISPER_STRICT=1 raises"""
+    import os
+    import warnings
+    from transformers.models.whisper import modeling_whisper as MW
+    if os.environ.get("HFASR_WHISPER_STRICT") == "1":
+        raise NotImplementedError(f"huggingface_asr_amd: the HIP Whisper generate does not cover this call ({why}) and HFASR_WHISPER_STRICT=1 forbids transformers' own generate")
+    if why not in _stock_generate.said:
+        _stock_generate.said.add(why)
+        warnings.warn(f"huggingface_asr_amd: WhisperForConditionalGeneration.generate runs transformers' own implementation for this call ({why}); the HIP path covers "
+                      "short-form greedy decoding on GPU tensors (language / task prompts, language detection, return_timestamps)", stacklevel=3)
+    return MW.WhisperForConditionalGeneration._hfasr_reference_generate(self, **kwargs)
+
+
+_stock_generate.said = set()
+
+
+def generate_segments(gc, config, input_features, decode_segment, *, init_tokens, decoder_input_ids=None, device=None):
+    """What transformers' `WhisperGenerationMixin.generate` does around its calls of `GenerationMixin.generate`, for short-form input without temperature fallback or
+    conditioning on previous text -> the ids `generate` returns: (B, longest) int64 — per row the generated tokens of its segments without the prompt columns and without
+    EOS, padded on the right with pad_token_id.  Its loop: decode the 30 s window at `seek` (`decode_segment(segment_input, prompt, max_new_tokens, first)` -> (b, P + n) ids
+    in `GenerationMixin`'s greedy layout), strip pads and EOS, cut at consecutive timestamp tokens and move `seek` behind the last closed one (`_retrieve_segment`), until
+    every row's window is used up; rows that finish leave the batch.  The bookkeeping is transformers' own static helpers, so the layout is the installed version's.
+    `gc.max_length` grows by the prompt length per segment, as transformers' generation config does across its loop."""
+    from transformers.models.whisper import generation_whisper as GW
+    mixin = GW.WhisperGenerationMixin
+    B, total = input_features.shape[0], input_features.shape[-1]
+    stride = 2                                             # conv1.stride * conv2.stride of every Whisper encoder
+    nseg = stride * config.max_source_positions
+    timestamp_begin = gc.no_timestamps_token_id + 1 if hasattr(gc, "no_timestamps_token_id") else config.vocab_size + 1
+    max_frames, seek = torch.full((B,), total, dtype=torch.long), torch.zeros((B,), dtype=torch.long)
+    batch_idx_map, cur_bsz, feats = list(range(B)), B, input_features
+    segments = [[] for _ in range(B)]
+    max_length, max_new = getattr(gc, "max_length", None), getattr(gc, "max_new_tokens", None)
+    first = True
+    while bool((seek < max_frames).any()):
+        feats, cur_bsz, batch_idx_map = mixin._maybe_reduce_batch(feats, seek, max_frames, cur_bsz, batch_idx_map)
+        time_offset = seek.to(torch.float64) * 0.02 / stride
+        seek_num_frames = (max_frames - seek).clamp(max=nseg)
+        segment_input = mixin._get_input_segment(feats, seek, seek_num_frames, nseg, cur_bsz, batch_idx_map)
+        prompt = decoder_input_ids if decoder_input_ids is not None else init_tokens[batch_idx_map]
+        P = prompt.shape[-1]
+        if (max_new or 0) + P > config.max_target_positions:                # `_set_max_new_tokens_and_length`
+            raise ValueError(f"The length of `decoder_input_ids`, including special start tokens, prompt tokens, and previous tokens, is {P},  and `max_new_tokens` is "
+                             f"{max_new or 0}. Thus, the combined length of `decoder_input_ids` and `max_new_tokens` is: {(max_new or 0) + P}. This exceeds the "
+                             f"`max_target_positions` of the Whisper model: {config.max_target_positions}. You should either reduce the length of your prompt, or reduce the "
+                             f"value of `max_new_tokens`, so that their combined length is less than {config.max_target_positions}.")
+        if max_length is not None and max_new is None:
+            max_length = min(max_length + min(config.max_target_positions // 2 - 1, P), config.max_target_positions)
+        n_new = max_new if max_new is not None else max_length - P
+        if n_new < 1:
+            raise ValueError(f"Input length of decoder_input_ids is {P}, but `max_length` is set to {P + n_new}. This can lead to unexpected behavior. You should consider "
+                             "increasing `max_length` or, better yet, setting `max_new_tokens`.")
+        out = decode_segment(segment_input, prompt, n_new, first)
+        first = False
+        for i, seq in enumerate(out[:, P:]):
+            prev_i = batch_idx_map[i]
+            if seq[-1] == gc.pad_token_id:                                  # `generate_with_fallback`: every pad goes, EOS stays for now
+                n_pad = int((seq == gc.pad_token_id).sum())
+                if gc.pad_token_id == gc.eos_token_id:
+                    n_pad -= 1
+                if n_pad != 0:
+                    seq = seq[:-n_pad]
+            if seq[-1] == gc.eos_token_id:
+                seq = seq[:-1]
+            segs, offset = mixin._retrieve_segment(seek_sequence=seq, seek_outputs=out, time_offset=time_offset, timestamp_begin=timestamp_begin, seek_num_frames=seek_num_frames,
+                                                   time_precision=0.02, time_precision_features=0.01, input_stride=stride, prev_idx=prev_i, idx=i, return_token_timestamps=False,
+                                                   decoder_input_ids=prompt)
+            if int(offset) <= 0:                                            # two timestamps at <|0.00|>: transformers' loop would decode the same window for ever
+                raise RuntimeError("Whisper segment loop does not advance: the decoded segment closes at timestamp 0")
+            seek[prev_i] += offset
+            segments[prev_i] += segs
+    return GW._pad_to_max_length(current_segments=segments, pad_token_id=gc.pad_token_id, device=device if device is not None else input_features.device, padding_side="right",
+                                 return_token_timestamps=False, force_unique_generate_call=False)
+
+
+def resolved_generation_config(model, generation_config, kwargs: dict):
+    """the generation config a `generate(generation_config=..., **kwargs)` call decodes under: a copy of the model's (or the given one) with the call's generation
+    parameters applied — `GenerationMixin._prepare_generation_config` on the keyword arguments that are not parameters of Whisper's own `generate` (those never reach it
+    in transformers either)"""
+    import inspect
+    from transformers.models.whisper.generation_whisper import WhisperGenerationMixin
+    own = set(inspect.signature(WhisperGenerationMixin.generate).parameters)
+    return model._prepare_generation_config(generation_config, **{k: v for k, v in kwargs.items() if k not in own})[0]
+
+
+def hip_whisper_generate(self, input_features=None, generation_config=None, **kwargs):
+    """`WhisperForConditionalGeneration.generate`: short-form greedy calls — `generate_route` — on the HIP path (`build_prompt`, `detect_language`, `greedy_decode`, the
+    timestamp rules in `mi_whisper_timestamp_argmax`), returning what transformers' own generate returns for the call (`generate_segments`); every other call is
+    transformers' own generate."""
+    raw = dict(kwargs, input_features=input_features, generation_config=generation_config)
+    gc = resolved_generation_config(self, generation_config, kwargs)
+    route, why = generate_route(raw, gc, self.config, tuple(input_features.shape) if input_features is not None else None)
+    if route == "hip" and not next(self.parameters()).is_cuda:
+        route, why = "stock", "CPU tensors"
+    if route != "hip":
+        return _stock_generate(self, why, raw)
+    g = kwargs.get
+    rt = g("return_timestamps") if g("return_timestamps") is not None else getattr(gc, "return_timestamps", None)
+    prompt_kw = dict(language=g("language"), task=g("task"), is_multilingual=g("is_multilingual"), return_timestamps=bool(rt))
+    rules = _token_rules(gc, self.config)
+    gc.eos_token_id, gc.pad_token_id = rules["eos_token_id"], rules["pad_token_id"]
+    timestamps = _timestamp_rules(gc) if rt else None
+    cfg, B = self.config, input_features.shape[0]
+    enc_eng, dec_eng = _engine_for(self.model.encoder), _decoder_engine_for(self.model.decoder)
+    dec_in = g("decoder_input_ids")
+    with torch.no_grad():
+        rows, detect = prompt_template(gc, cfg, B, **prompt_kw)                                   # raises what transformers raises, also when decoder_input_ids is given
+        P, mtp = len(rows[0]), cfg.max_target_positions                                           # the first segment's positions, as `generate_segments` will count them
+        Lmax = min(P + gc.max_new_tokens, mtp) if getattr(gc, "max_new_tokens", None) is not None else min(gc.max_length + min(mtp // 2 - 1, P), mtp)
+        if dec_in is not None:                                                                    # (the prompt as given: nothing to detect for)
+            rows, detect = [[0 if t == LANGUAGE_TO_DETECT else t for t in r] for r in rows], False
+        init_tokens, state = _detected_prompt(self, gc, input_features, rows, detect, max(Lmax, P + 1))
+
+        def decode_segment(segment_input, prompt, n_new, first):
+            st = state if first and state is not None and state["cache"]["Lmax"] >= prompt.shape[1] + n_new else None       # the detection step's encoder output and cache
+            return greedy_decode(enc_eng, dec_eng, segment_input, prompt.contiguous(), max_new_tokens=n_new, timestamps=timestamps, state=st, **rules)
+        return generate_segments(gc, cfg, input_features, decode_segment, init_tokens=init_tokens, decoder_input_ids=dec_in, device=self.device)
+
+
 def _replace_forward(cls, ours):
     if getattr(cls.forward, "_hfasr_hip", False):
         return
@@ -916,14 +1325,20 @@ def _replace_forward(cls, ours):
     cls.forward = ours
 
 
-def install_whisper(decoder: bool = False, fused_loss: bool = False):
+def install_whisper(decoder: bool = False, fused_loss: bool = False, generate: bool = False):
     """Give transformers' `WhisperEncoder` the HIP forward (idempotent).  The original stays reachable as `WhisperEncoder._hfasr_reference_forward` (tests compare against it).
     Opt-in: decoder=True also replaces `WhisperDecoder.forward` (`hip_whisper_decoder_forward`: the teacher-forced training pass on the HIP engine), fused_loss=True
-    (implies decoder=True) wraps `WhisperForConditionalGeneration.forward` (`hip_whisper_lm_forward`: the training loss out of the tied head's GEMM, no logits); their
-    originals stay reachable under the same name.  With neither, both classes are left untouched."""
+    (implies decoder=True) wraps `WhisperForConditionalGeneration.forward` (`hip_whisper_lm_forward`: the training loss out of the tied head's GEMM, no logits),
+    generate=True replaces `WhisperForConditionalGeneration.generate` (`hip_whisper_generate`: short-form greedy decoding on the HIP path; the original stays reachable as
+    `WhisperForConditionalGeneration._hfasr_reference_generate`); the other originals stay reachable under `_hfasr_reference_forward`.  With none of them, the decoder and
+    `WhisperForConditionalGeneration` are left untouched."""
     from transformers.models.whisper import modeling_whisper as MW
     _replace_forward(MW.WhisperEncoder, hip_whisper_encoder_forward)
     if decoder or fused_loss:
         _replace_forward(MW.WhisperDecoder, hip_whisper_decoder_forward)
     if fused_loss:
         _replace_forward(MW.WhisperForConditionalGeneration, hip_whisper_lm_forward)
+    if generate and not getattr(MW.WhisperForConditionalGeneration.generate, "_hfasr_hip", False):
+        MW.WhisperForConditionalGeneration._hfasr_reference_generate = MW.WhisperForConditionalGeneration.generate
+        hip_whisper_generate._hfasr_hip = True
+        MW.WhisperForConditionalGeneration.generate = hip_whisper_generate

@@ -589,6 +589,13 @@ int mi_linear_rows(const void* x, long ldx, const void* W, long ldw, const float
 /* One step of greedy decoding between two token steps (transformers GenerationMixin greedy loop): tok = done[b] ? pad : best[b]; ids[b, col] = new_tok[b] = tok;
  * done[b] |= tok == eos; done_host (nullable; pinned, device-mapped memory) receives the flags. */
 int mi_greedy_advance(const int* best, long* ids, long ld_ids, int col, long eos, long pad, int* done, long* new_tok, int* done_host, int B, mi_stream_t stream);
+/* Whisper's timestamp rules + argmax for one greedy step (csrc/whisper_rules.hip): best[b] = argmax(WhisperTimeStampLogitsProcessor(ids[b, :cur_len], logits[b])) of
+ * transformers (generation/logits_process.py), mi_row_argmax's rules (lowest index among equal maxima; a row with nothing finite left gives 0).  logits (B, ld) fp32, the
+ * first V columns of a row (suppression already applied as -inf); ids (B, ld_ids) int64, of which [begin_index, cur_len) are the sampled tokens; timestamp_begin =
+ * no_timestamps_token_id + 1; max_initial_timestamp_index -1 = None; detect_from_logprob: the processor's _detect_timestamp_from_logprob.  One read of the row, no
+ * atomics: bit-reproducible. */
+int mi_whisper_timestamp_argmax(const float* logits, long ld, int V, const long* ids, long ld_ids, int begin_index, int cur_len, int no_timestamps_token_id,
+                                int eos_token_id, int max_initial_timestamp_index, int detect_from_logprob, int* best, int B, mi_stream_t stream);
 int mi_kv_cache_reorder(const void* const* src_k, const void* const* src_v, void* const* dst_k, void* const* dst_v, const long* beam_idx,
                         int L, int BW, int rows, int Lmax, int d, mi_stream_t stream);
 

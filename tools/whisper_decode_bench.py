@@ -2,13 +2,16 @@
 """ms per token of the Whisper decoder step: the streaming form (mi_gpt2_config.step_form = 2, csrc/linear_rows.hip), the launch-per-op form (1) and transformers' own
 decoder with its KV cache under bf16 autocast, alternated in ONE process on the same weights.
 
-    python tools/whisper_decode_bench.py [--steps 200] [--rounds 3] [--warmup 20] [--out FILE.txt]
+    python tools/whisper_decode_bench.py [--steps 200] [--rounds 3] [--warmup 20] [--out FILE.txt] [--timestamps]
 
 Shapes: whisper-small size (d 768, 12 layers, V 51865, 1500 encoder keys) at B = 1, 16, 64 and whisper-medium size (d 1024, 24 layers) at B = 16.  A round of a leg is
 `steps` consecutive token steps after a one-token prompt between two device events; the legs run 2 1 T 2 1 T ... for `rounds` rounds.  Reported per leg: the mean over
 the rounds and the spread (max - min of the per-round means) — form 2 has to beat form 1 by more than that spread to be what `WhisperDecoderEngine` selects.  Next to
 them the byte floor of a step (decoder weights + tied head + the cached encoder K/V of every row, each read once) at the 6.3 TB/s a streaming read achieves on this part,
-and the share of that rate form 2 reaches.  One JSON line per shape, then a table."""
+and the share of that rate form 2 reaches.  One JSON line per shape, then a table.
+
+--timestamps measures the token choice instead: the step followed by `mi_row_argmax` next to the step followed by `mi_whisper_timestamp_argmax` (the timestamp rules of
+`greedy_decode(timestamps=...)`; an open segment of 32 sampled tokens as history), alternated R A R A ... in the engine's own step form, same rounds and spread rule."""
 from __future__ import annotations
 
 import argparse
@@ -42,6 +45,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out")
+    ap.add_argument("--timestamps", action="store_true")
     a = ap.parse_args()
     assert 1 + a.steps <= LMAX and a.warmup + 1 <= LMAX
     from transformers import WhisperConfig
@@ -91,6 +95,46 @@ def main():
                 e1.synchronize()
                 return e0.elapsed_time(e1) / n
 
+        if a.timestamps:
+            from huggingface_asr_amd import ops
+            tb, P, n_hist = 50364, 4, 32
+            ids = torch.randint(0, tb - 1, (B, LMAX), device=DEV)
+            ids[:, P] = tb                                    # an open segment: one timestamp, then text
+            rules = dict(begin_index=P, cur_len=P + n_hist, no_timestamps_token_id=tb - 1, eos_token_id=50257, max_initial_timestamp_index=50)
+
+            def choice_leg(choose):
+                def run(n):
+                    eng.step_form = None
+                    cache["past"] = 0
+                    choose(eng.step(tok, cache, kvs, T_ENC))
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(n):
+                        choose(eng.step(tok, cache, kvs, T_ENC))
+                    e1.record()
+                    e1.synchronize()
+                    return e0.elapsed_time(e1) / n
+                return run
+            legs = {"rules": choice_leg(lambda lg: ops.whisper_timestamp_argmax(lg, ids, **rules)), "argmax": choice_leg(ops.row_argmax)}
+            for fn in legs.values():
+                fn(a.warmup)
+            per = {k: [] for k in legs}
+            for _ in range(a.rounds):
+                for k, fn in legs.items():
+                    per[k].append(fn(a.steps))
+            mean = {k: sum(v) / len(v) for k, v in per.items()}
+            spread = {k: max(v) - min(v) for k, v in per.items()}
+            res = dict(tool="whisper_decode_bench", case="timestamps", device=torch.cuda.get_device_name(0), size=name, d=d, layers=L, B=B, V=V, keys=T_ENC, steps=a.steps,
+                       rounds=a.rounds, form=eng.form_for(B), mean_ms={k: round(v, 4) for k, v in mean.items()}, spread_ms={k: round(v, 4) for k, v in spread.items()},
+                       rounds_ms={k: [round(t, 4) for t in v] for k, v in per.items()}, row_bytes=V * 4,
+                       rules_slower_than_argmax=bool(mean["rules"] - mean["argmax"] > max(spread.values())))
+            lines.append(json.dumps(res))
+            print(lines[-1], flush=True)
+            table.append(f"{name:7s} d {d:4d} L {L:2d} B {B:2d} | step + timestamp rules {mean['rules']:7.3f} ms (+-{spread['rules']:.3f}) | step + row argmax {mean['argmax']:7.3f} ms "
+                         f"(+-{spread['argmax']:.3f}) | difference {1e3 * (mean['rules'] - mean['argmax']):+6.1f} us")
+            del dec, eng, kvs, cache, enc
+            torch.cuda.empty_cache()
+            continue
         legs = {"form2": hip_leg(2), "form1": hip_leg(1), "transformers": hf_leg}
         for fn in legs.values():
             fn(a.warmup)
