@@ -23,7 +23,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 // failed hipPointerGetAttributes behind): clear it on entry, so that MI_CHECK_LAUNCH reports only our own launches.
 #define MI_ENTER() (void)hipGetLastError()
 
-extern "C" void mi_record_hip_error(int code, const char* file, int line);   // encoder.hip (diagnostics only)
+extern "C" void mi_record_hip_error(int code, const char* file, int line);   // diag.hip (diagnostics only)
 
 #define MI_CHECK_LAUNCH()                                            \
     do {                                                             \

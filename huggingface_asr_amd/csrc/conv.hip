@@ -9,6 +9,7 @@
 //      MERGE (e_branchformer.py:296-299): out = m + conv(m) + b
 //  * row_stats: per-row mean / rstd of the gate half for the CSGU LayerNorm (fp32).
 #include "common.hpp"
+#include "ebf_layout.hpp"      // conv1_gated_fused
 
 namespace {
 
@@ -539,8 +540,8 @@ extern "C" int mi_conv2d_first_gated_gelu(const float* x, const float* w, const 
                                           int B, int T, int F, int C, int K, int stride, int pad_t, int pad_f, int T1, int F1, hipStream_t stream) {
     MI_ENTER();
     if (B <= 0 || T <= 0 || F <= 0 || C <= 0 || T1 <= 0 || F1 <= 0) return MI_ERR_ARG;
+    if (!conv1_gated_fused(B, T1, F1, C, K)) return MI_ERR_UNSUPPORTED;
     const int cgs = C / 4;
-    if (K != 3 || (C % 4) != 0 || cgs > 256 || (long)B * T1 * F1 >= (1L << 31) - 256L * 8192) return MI_ERR_UNSUPPORTED;
     const long npos = (long)B * T1 * F1;
     const int ppb = 256 / cgs;
     const long nb = (npos + ppb - 1) / ppb;

@@ -10,7 +10,7 @@
 // act1 (B,T1,F1,C1) / act2 (B,T2,F2,C2) channels-last conv activations.
 #include "common.hpp"
 #include "gemm_f32.hpp"
-#include "../../include/hfasr_hip.h"
+#include "ebf_layout.hpp"
 
 namespace {
 
@@ -360,27 +360,8 @@ extern "C" int mi_attention_f32(const float* q, long ldq, const float* k, long l
 }
 
 // ================================================================================================ whole-encoder driver
+// Slot order and geometry: ebf_layout.hpp, shared with the bf16 driver; this mode reads the un-folded slots, all of them fp32.
 namespace {
-
-enum G { G_CONV1_W, G_CONV1_B, G_CONV2_W, G_CONV2_B, G_FEOUT_W, G_FEOUT_B, G_FP_LN_G, G_FP_LN_B, G_FP_W, G_FP_B,
-         G_ENC_LN_G, G_ENC_LN_B, G_HEAD_W, G_HEAD_B };
-// the slot order of mi_ebf_forward (encoder.hip / engine.py LS); this mode reads the un-folded ones, all fp32
-enum LS { FF1_LN_G, FF1_LN_B, FF1_W1, FF1_B1, FF1_W2, FF1_B2,
-          ATT_LN_G, ATT_LN_B, ATT_WQK, ATT_BQK, ATT_WV, ATT_BV, ATT_WO, ATT_BO, ATT_WPOS, ATT_U, ATT_V,
-          MLP_LN_G, MLP_LN_B, MLP_W1, MLP_B1, CSGU_LN_G, CSGU_LN_B, CSGU_W, CSGU_B, MLP_W2, MLP_B2,
-          MRG_DW_W, MRG_DW_B, MRG_W, MRG_B, FIN_LN_G, FIN_LN_B,
-          FF2_LN_G, FF2_LN_B, FF2_W1, FF2_B1, FF2_W2, FF2_B2, CSGU_LIN_W, CSGU_LIN_B };
-
-struct Dims { int T1, F1, T2, F2, M, hd; };
-int conv_out(int n, int k, int s, int pad_total) { return (n + pad_total - k) / s + 1; }
-Dims dims(const mi_ebf_config& c) {
-    Dims d;
-    const int pt = 2 * c.pad;                 // causal: the same total, all of it on the left (streaming_modules.py:31-55)
-    d.T1 = conv_out(c.T, c.K, c.stride, pt); d.F1 = conv_out(c.F, c.K, c.stride, pt);
-    d.T2 = conv_out(d.T1, c.K, c.stride, pt); d.F2 = conv_out(d.F1, c.K, c.stride, pt);
-    d.M = c.B * d.T2; d.hd = c.H > 0 ? c.d / c.H : 0;
-    return d;
-}
 
 struct Ws {
     float *act1, *act2, *feo, *x, *a0, *a1, *a2, *a1r, *h, *qkv, *ctx, *cat, *m2, *gn, *s, *cv, *lin, *hid;
@@ -388,13 +369,11 @@ struct Ws {
     void* attn; size_t attn_bytes;
     size_t bytes;
 };
-Ws carve(const mi_ebf_config& c, void* base) {
-    const Dims d = dims(c);
-    char* b = (char*)base;
-    size_t off = 0;
-    auto take = [&](size_t floats) { float* p = b ? (float*)(b + off) : nullptr; off += (floats * 4 + 255) / 256 * 256; return p; };
+Ws carve(const mi_ebf_config& c, const Dims& d, void* base) {
+    Carver k{(char*)base, 0};
+    auto take = [&](size_t floats) { return (float*)k.take(floats * 4); };
     Ws w;
-    const size_t M = (size_t)(d.M > 0 ? d.M : 0), dd = c.d, I = c.I;
+    const size_t M = d.M, dd = c.d, I = c.I;
     w.act1 = take((size_t)c.B * d.T1 * d.F1 * c.C1);
     w.act2 = take((size_t)c.B * d.T2 * d.F2 * c.C2);
     w.feo = take(M * dd); w.x = take(M * dd); w.a0 = take(M * dd); w.a1 = take(M * dd); w.a2 = take(M * dd); w.a1r = take(M * dd);
@@ -406,23 +385,8 @@ Ws carve(const mi_ebf_config& c, void* base) {
     w.lens = (int*)take((size_t)2 * c.B);
     w.attn_bytes = mi_attention_f32_workspace_bytes(c.B, d.T2, c.H, d.hd, c.pos_type == 1);
     w.attn = take((w.attn_bytes + 3) / 4);
-    w.bytes = off;
+    w.bytes = k.off;
     return w;
-}
-
-// lengths: inner = padded conv formula (extractors.py:133-162), outer = un-padded formula (Wav2Vec2ForCTC._get_feat_extract_output_lengths; SURVEY.md §8a row 8')
-__global__ void lengths_f32_kernel(const int* feat_len, int T, int B, int K, int stride, int pad, int causal, int nconv, int T2, int* inner, int* outer) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    int li = feat_len ? feat_len[b] : T, lo = li;
-    for (int i = 0; i < nconv; ++i) {
-        const int num_i = li + (causal ? K - 1 : 2 * pad) - K;
-        li = (num_i >= 0 ? num_i / stride : -((-num_i + stride - 1) / stride)) + 1;
-        const int num_o = lo - K;
-        lo = (num_o >= 0 ? num_o / stride : -((-num_o + stride - 1) / stride)) + 1;
-    }
-    inner[b] = li < T2 ? li : T2;
-    outer[b] = lo;
 }
 
 // what this mode does not cover (header: mi_ebf_forward_f32)
@@ -430,13 +394,116 @@ bool f32_unsupported(const mi_ebf_config& c) {
     return c.context_mode != 0 || c.layer_mixing || c.extra_layers || c.ln_fold || c.wide_tiles || c.branch_overlap;
 }
 
-#define RUN(expr) do { int rc__ = (expr); if (rc__ != MI_OK) return rc__; } while (0)
+constexpr float LEPS = 1e-5f;                  // nn.LayerNorm default: the layers use nn.LayerNorm(embed_dim) (e_branchformer.py:233-261)
+
+// One fp32 forward, in the stages of the bf16 driver's un-folded branch (encoder.hip): front end, layer, exit
+struct Fwd32 : Slots {
+    const mi_ebf_config& c; const Dims D; const Ws w; hipStream_t st;
+    const int* mask_len;                          // the inner lengths of a ragged batch, else null
+    const float* pos_table; float* posp;          // header: mi_ebf_forward_f32
+    const int M, d, I, T2, P;                     // P = 2*T2-1 relative positions
+    Fwd32(const mi_ebf_config& c_, const Dims& D_, const Ws& w_, const void* const* weights, hipStream_t st_, const int* mask, const void* pos_table_, void* posp_)
+        : Slots{weights}, c(c_), D(D_), w(w_), st(st_), mask_len(mask), pos_table((const float*)pos_table_), posp((float*)posp_), M(D_.M), d(c_.d), I(c_.I), T2(D_.T2),
+          P(2 * D_.T2 - 1) {}
+    int ln(const float* x, const int* mask, float* xo, const float* g, const float* b, float eps, float* y) const {
+        return mi_layernorm_f32(x, d, mask, T2, xo, d, g, b, eps, y, d, M, d, st);
+    }
+    int first_norms(int l, const int* mask, float* xo) const;
+    int front_end(const float* feats, int compute_posp) const;
+    int layer(int l) const;
+    int exit(int l, float* last_hidden, float* logits) const;
+};
+
+// the LayerNorm(s) in front of layer l: ff1's with macaron FFNs, else the two branch norms; mask / xo: as mi_layernorm_f32's, for the first of them
+int Fwd32::first_norms(int l, const int* mask, float* xo) const {
+    if (c.use_macaron) return ln(w.x, mask, xo, Lf(l, FF1_LN_G), Lf(l, FF1_LN_B), LEPS, w.a0);
+    RUN(ln(w.x, mask, xo, Lf(l, ATT_LN_G), Lf(l, ATT_LN_B), LEPS, w.a1));
+    return ln(w.x, nullptr, nullptr, Lf(l, MLP_LN_G), Lf(l, MLP_LN_B), LEPS, w.a2);
+}
+
+int Fwd32::front_end(const float* feats, int compute_posp) const {
+    // --- Conv2d sub-sampling (extractors.py:110-113); causal: all padding on the left (CausalConv2d, streaming_modules.py:31-55)
+    const int pl = c.is_causal ? 2 * c.pad : c.pad;
+    RUN(mi_conv2d_first_gelu_f32(feats, Gf(G_CONV1_W), Gf(G_CONV1_B), w.act1, c.B, c.T, c.F, c.C1, c.K, c.stride, pl, pl, D.T1, D.F1, st));
+    RUN(mi_conv2d_cl_f32(w.act1, Gf(G_CONV2_W), Gf(G_CONV2_B), w.act2, c.B, D.T1, D.F1, c.C1, c.C2, c.K, c.stride, pl, pl, D.T2, D.F2, 1, st));
+    // (B,C,T',F') -> transpose -> flatten -> Linear: act2 is already (B*T', F'*C) with the weight columns permuted to match
+    RUN(gemm(w.act2, (long)D.F2 * c.C2, Gf(G_FEOUT_W), (long)D.F2 * c.C2, Gf(G_FEOUT_B), w.feo, d, nullptr, 0, 1.f, 0, M, d, D.F2 * c.C2, st));
+    // --- feature projection: LN -> Linear (extractors.py:130-131; tf:328-333)
+    RUN(ln(w.feo, nullptr, nullptr, Gf(G_FP_LN_G), Gf(G_FP_LN_B), c.ln_eps, w.a0));
+    RUN(gemm(w.a0, d, Gf(G_FP_W), d, Gf(G_FP_B), w.x, d, nullptr, 0, 1.f, 0, M, d, d, st));
+    // --- zero padded frames once (tf:662-665) + first LayerNorm(s) of layer 0
+    RUN(first_norms(0, mask_len, w.x));
+    // --- relative positions: p_l = linear_pos_l(table) for every layer (batch independent; tf:531-536)
+    if (c.pos_type == 1 && compute_posp)
+        for (int l = 0; l < c.L; ++l)
+            RUN(gemm(pos_table, d, Lf(l, ATT_WPOS), d, nullptr, posp + (size_t)l * P * d, d, nullptr, 0, 1.f, 0, P, d, d, st));
+    return MI_OK;
+}
+
+// one layer, from its first LayerNorm's output to the residual stream in front of final_layer_norm
+int Fwd32::layer(int l) const {
+    const int kc = c.csgu_kernel, km = c.merge_kernel;
+    if (c.use_macaron) {   // x += 0.5 * FFN(LN(x))   e_branchformer.py:271-273
+        RUN(gemm(w.a0, d, Lf(l, FF1_W1), d, Lf(l, FF1_B1), w.h, I, nullptr, 0, 1.f, 1, M, I, d, st));
+        RUN(gemm(w.h, I, Lf(l, FF1_W2), I, Lf(l, FF1_B2), w.x, d, w.x, d, 0.5f, 0, M, d, I, st));
+        RUN(ln(w.x, nullptr, nullptr, Lf(l, ATT_LN_G), Lf(l, ATT_LN_B), LEPS, w.a1));
+        RUN(ln(w.x, nullptr, nullptr, Lf(l, MLP_LN_G), Lf(l, MLP_LN_B), LEPS, w.a2));
+    }
+    // global branch (e_branchformer.py:281-288): [Q|K|V] projection (weights are packed [Wq;Wk;Wv]); rotary feeds Q,K from the rotated input only
+    if (c.pos_type == 2) {
+        RUN(mi_rotary_f32(w.a1, d, w.a1r, d, pos_table, pos_table ? pos_table + (size_t)T2 * D.hd : nullptr, M, T2, c.H, D.hd, st));      // [cos (T2, hd) | sin (T2, hd)]
+        RUN(gemm(w.a1r, d, Lf(l, ATT_WQK), d, Lf(l, ATT_BQK), w.qkv, 3 * d, nullptr, 0, 1.f, 0, M, 2 * d, d, st));
+        RUN(gemm(w.a1, d, Lf(l, ATT_WV), d, Lf(l, ATT_BV), w.qkv + 2 * d, 3 * d, nullptr, 0, 1.f, 0, M, d, d, st));
+    } else {
+        RUN(gemm(w.a1, d, Lf(l, ATT_WQK), d, Lf(l, ATT_BQK), w.qkv, 3 * d, nullptr, 0, 1.f, 0, M, 3 * d, d, st));
+    }
+    const bool rel = c.pos_type == 1;
+    RUN(mi_attention_f32(w.qkv, 3 * d, w.qkv + d, 3 * d, w.qkv + 2 * d, 3 * d, rel ? posp + (size_t)l * P * d : nullptr, d,
+                         rel ? Lf(l, ATT_U) : nullptr, rel ? Lf(l, ATT_V) : nullptr, mask_len, w.ctx, d,
+                         c.B, T2, c.H, D.hd, 1.0f / sqrtf((float)D.hd), c.is_causal, w.attn, w.attn_bytes, st));
+    RUN(gemm(w.ctx, d, Lf(l, ATT_WO), d, Lf(l, ATT_BO), w.cat, 2 * d, nullptr, 0, 1.f, 0, M, d, d, st));
+    // local branch: cgMLP (e_branchformer.py:291-292, 184-222)
+    RUN(gemm(w.a2, d, Lf(l, MLP_W1), d, Lf(l, MLP_B1), w.h, I, nullptr, 0, 1.f, 1, M, I, d, st));
+    RUN(mi_layernorm_f32(w.h + I / 2, I, nullptr, T2, nullptr, 0, Lf(l, CSGU_LN_G), Lf(l, CSGU_LN_B), LEPS, w.gn, I / 2, M, I / 2, st));
+    // quirk: the causal CSGU conv is dilated by (K-1)/2 (e_branchformer.py:153-160 passes it in the dilation slot)
+    const int dil = c.is_causal ? (kc - 1) / 2 : 1;
+    const int cpad = c.is_causal ? (kc - 1) * dil : (kc - 1) / 2;
+    if (c.csgu_linear) {   // conv -> Linear -> act -> gate (e_branchformer.py:196-201)
+        RUN(mi_dwconv_f32(w.gn, I / 2, Lf(l, CSGU_W), Lf(l, CSGU_B), nullptr, 0, w.cv, I / 2, c.B, T2, I / 2, kc, cpad, dil, 0, 0, st));
+        RUN(gemm(w.cv, I / 2, Lf(l, CSGU_LIN_W), I / 2, Lf(l, CSGU_LIN_B), w.lin, I / 2, nullptr, 0, 1.f, 0, M, I / 2, I / 2, st));
+        RUN(mi_gate_act_mul_f32(w.h, I, w.lin, I / 2, w.s, I / 2, M, I / 2, c.csgu_act, st));
+    } else
+        RUN(mi_dwconv_f32(w.gn, I / 2, Lf(l, CSGU_W), Lf(l, CSGU_B), w.h, I, w.s, I / 2, c.B, T2, I / 2, kc, cpad, dil, c.csgu_act, 1, st));
+    RUN(gemm(w.s, I / 2, Lf(l, MLP_W2), I / 2, Lf(l, MLP_B2), w.cat + d, 2 * d, nullptr, 0, 1.f, 0, M, d, I / 2, st));
+    // merge (e_branchformer.py:296-304)
+    RUN(mi_dwconv_f32(w.cat, 2 * d, Lf(l, MRG_DW_W), Lf(l, MRG_DW_B), nullptr, 0, w.m2, 2 * d, c.B, T2, 2 * d, km, (km - 1) / 2, 1, 0, 2, st));
+    RUN(gemm(w.m2, 2 * d, Lf(l, MRG_W), 2 * d, Lf(l, MRG_B), w.x, d, w.x, d, 1.0f, 0, M, d, 2 * d, st));
+    if (c.use_macaron) {   // e_branchformer.py:307-309
+        RUN(ln(w.x, nullptr, nullptr, Lf(l, FF2_LN_G), Lf(l, FF2_LN_B), LEPS, w.a0));
+        RUN(gemm(w.a0, d, Lf(l, FF2_W1), d, Lf(l, FF2_B1), w.h, I, nullptr, 0, 1.f, 1, M, I, d, st));
+        RUN(gemm(w.h, I, Lf(l, FF2_W2), I, Lf(l, FF2_B2), w.x, d, w.x, d, 0.5f, 0, M, d, I, st));
+    }
+    return MI_OK;
+}
+
+// final_layer_norm (:312), then the next consumer: layer l+1's first LayerNorm(s), or after the last layer encoder.layer_norm (tf:707) and the CTC head
+int Fwd32::exit(int l, float* last_hidden, float* logits) const {
+    if (l + 1 < c.L) {
+        RUN(ln(w.x, nullptr, nullptr, Lf(l, FIN_LN_G), Lf(l, FIN_LN_B), LEPS, w.x));
+        return first_norms(l + 1, nullptr, nullptr);
+    }
+    RUN(ln(w.x, nullptr, nullptr, Lf(l, FIN_LN_G), Lf(l, FIN_LN_B), LEPS, w.a0));
+    float* lh = last_hidden ? last_hidden : w.hid;
+    RUN(ln(w.a0, nullptr, nullptr, Gf(G_ENC_LN_G), Gf(G_ENC_LN_B), c.ln_eps, lh));
+    if (!logits) return MI_OK;
+    // CTC head: lm_head ⊕ blank_projection, blank LAST (e_branchformer.py:456-457)
+    return gemm(lh, d, Gf(G_HEAD_W), d, Gf(G_HEAD_B), logits, c.logits_ld > 0 ? c.logits_ld : c.V + 1, nullptr, 0, 1.f, 0, M, c.V + 1, d, st);
+}
 
 }  // namespace
 
 extern "C" size_t mi_ebf_f32_workspace_bytes(const mi_ebf_config* cfg) {
-    if (!cfg || f32_unsupported(*cfg) || cfg->B <= 0 || cfg->H <= 0 || dims(*cfg).T2 <= 0) return 0;
-    return carve(*cfg, nullptr).bytes;
+    return sizable(cfg) && !f32_unsupported(*cfg) ? carve(*cfg, dims(*cfg), nullptr).bytes : 0;
 }
 
 // pos_table: relative: (2*T2-1, d) FP32 sinusoid table; rotary: fp32 [cos (T2,hd) | sin (T2,hd)].  posp: (L, 2*T2-1, d) FP32.
@@ -453,105 +520,16 @@ extern "C" int mi_ebf_forward_f32(const mi_ebf_config* cfg, const void* const* w
     if (c.pos_type == 1 && !posp) return MI_ERR_ARG;
     const Dims D = dims(c);
     if (D.T2 <= 0) return MI_ERR_ARG;
-    Ws w = carve(c, workspace);
+    const Ws w = carve(c, D, workspace);
     if (w.bytes > workspace_bytes) return MI_ERR_ARG;
-    auto Gf = [&](int s) { return (const float*)weights[s]; };
-    auto Lf = [&](int l, int s) { return (const float*)weights[MI_EBF_GLOBAL_SLOTS + l * MI_EBF_LAYER_SLOTS + s]; };
-    const int M = D.M, d = c.d, I = c.I, T2 = D.T2;
-    const float leps = 1e-5f;                  // nn.LayerNorm default: the layers use nn.LayerNorm(embed_dim) (e_branchformer.py:233-261)
     int* inner = inner_len ? inner_len : w.lens;
     int* outer = outer_len ? outer_len : w.lens + c.B;
-    auto ln = [&](const float* x, const int* mask, float* xo, const float* g, const float* b, float eps, float* y) {
-        return mi_layernorm_f32(x, d, mask, T2, xo, d, g, b, eps, y, d, M, d, st);
-    };
-
-    hipLaunchKernelGGL(lengths_f32_kernel, dim3(cdiv(c.B, 64)), dim3(64), 0, st, feat_lengths, c.T, c.B, c.K, c.stride, c.pad, c.is_causal, 2, T2, inner, outer);
-    const int* mask_len = feat_lengths ? inner : nullptr;
-
-    // --- Conv2d sub-sampling (extractors.py:110-113); causal: all padding on the left (CausalConv2d, streaming_modules.py:31-55)
-    const int pl = c.is_causal ? 2 * c.pad : c.pad;
-    RUN(mi_conv2d_first_gelu_f32(feats, Gf(G_CONV1_W), Gf(G_CONV1_B), w.act1, c.B, c.T, c.F, c.C1, c.K, c.stride, pl, pl, D.T1, D.F1, st));
-    RUN(mi_conv2d_cl_f32(w.act1, Gf(G_CONV2_W), Gf(G_CONV2_B), w.act2, c.B, D.T1, D.F1, c.C1, c.C2, c.K, c.stride, pl, pl, D.T2, D.F2, 1, st));
-    // (B,C,T',F') -> transpose -> flatten -> Linear: act2 is already (B*T', F'*C) with the weight columns permuted to match
-    RUN(gemm(w.act2, (long)D.F2 * c.C2, Gf(G_FEOUT_W), (long)D.F2 * c.C2, Gf(G_FEOUT_B), w.feo, d, nullptr, 0, 1.f, 0, M, d, D.F2 * c.C2, st));
-    // --- feature projection: LN -> Linear (extractors.py:130-131; tf:328-333)
-    RUN(ln(w.feo, nullptr, nullptr, Gf(G_FP_LN_G), Gf(G_FP_LN_B), c.ln_eps, w.a0));
-    RUN(gemm(w.a0, d, Gf(G_FP_W), d, Gf(G_FP_B), w.x, d, nullptr, 0, 1.f, 0, M, d, d, st));
-    // --- zero padded frames once (tf:662-665) + first LayerNorm(s) of layer 0
-    if (c.use_macaron) RUN(ln(w.x, mask_len, w.x, Lf(0, FF1_LN_G), Lf(0, FF1_LN_B), leps, w.a0));
-    else {
-        RUN(ln(w.x, mask_len, w.x, Lf(0, ATT_LN_G), Lf(0, ATT_LN_B), leps, w.a1));
-        RUN(ln(w.x, nullptr, nullptr, Lf(0, MLP_LN_G), Lf(0, MLP_LN_B), leps, w.a2));
-    }
-    // --- relative positions: p_l = linear_pos_l(table) for every layer (batch independent; tf:531-536)
-    const int P = 2 * T2 - 1;
-    float* pp = (float*)posp;
-    if (c.pos_type == 1 && compute_posp)
-        for (int l = 0; l < c.L; ++l)
-            RUN(gemm((const float*)pos_table, d, Lf(l, ATT_WPOS), d, nullptr, pp + (size_t)l * P * d, d, nullptr, 0, 1.f, 0, P, d, d, st));
-    const float* rot_cos = (const float*)pos_table;
-    const float* rot_sin = rot_cos ? rot_cos + (size_t)T2 * D.hd : nullptr;
-    const float scale = 1.0f / sqrtf((float)D.hd);
-    const int kc = c.csgu_kernel, km = c.merge_kernel;
-
+    launch_subsampled_lengths(feat_lengths, c.T, c.B, c.K, c.stride, c.is_causal ? c.K - 1 : 2 * c.pad, 2, D.T2, inner, outer, st);
+    const Fwd32 f(c, D, w, weights, st, feat_lengths ? inner : nullptr, pos_table, posp);
+    RUN(f.front_end(feats, compute_posp));
     for (int l = 0; l < c.L; ++l) {
-        if (c.use_macaron) {   // x += 0.5 * FFN(LN(x))   e_branchformer.py:271-273
-            RUN(gemm(w.a0, d, Lf(l, FF1_W1), d, Lf(l, FF1_B1), w.h, I, nullptr, 0, 1.f, 1, M, I, d, st));
-            RUN(gemm(w.h, I, Lf(l, FF1_W2), I, Lf(l, FF1_B2), w.x, d, w.x, d, 0.5f, 0, M, d, I, st));
-            RUN(ln(w.x, nullptr, nullptr, Lf(l, ATT_LN_G), Lf(l, ATT_LN_B), leps, w.a1));
-            RUN(ln(w.x, nullptr, nullptr, Lf(l, MLP_LN_G), Lf(l, MLP_LN_B), leps, w.a2));
-        }
-        // global branch (e_branchformer.py:281-288): [Q|K|V] projection (weights are packed [Wq;Wk;Wv]); rotary feeds Q,K from the rotated input only
-        if (c.pos_type == 2) {
-            RUN(mi_rotary_f32(w.a1, d, w.a1r, d, rot_cos, rot_sin, M, T2, c.H, D.hd, st));
-            RUN(gemm(w.a1r, d, Lf(l, ATT_WQK), d, Lf(l, ATT_BQK), w.qkv, 3 * d, nullptr, 0, 1.f, 0, M, 2 * d, d, st));
-            RUN(gemm(w.a1, d, Lf(l, ATT_WV), d, Lf(l, ATT_BV), w.qkv + 2 * d, 3 * d, nullptr, 0, 1.f, 0, M, d, d, st));
-        } else {
-            RUN(gemm(w.a1, d, Lf(l, ATT_WQK), d, Lf(l, ATT_BQK), w.qkv, 3 * d, nullptr, 0, 1.f, 0, M, 3 * d, d, st));
-        }
-        RUN(mi_attention_f32(w.qkv, 3 * d, w.qkv + d, 3 * d, w.qkv + 2 * d, 3 * d, c.pos_type == 1 ? pp + (size_t)l * P * d : nullptr, d,
-                             c.pos_type == 1 ? Lf(l, ATT_U) : nullptr, c.pos_type == 1 ? Lf(l, ATT_V) : nullptr, mask_len, w.ctx, d,
-                             c.B, T2, c.H, D.hd, scale, c.is_causal, w.attn, w.attn_bytes, st));
-        RUN(gemm(w.ctx, d, Lf(l, ATT_WO), d, Lf(l, ATT_BO), w.cat, 2 * d, nullptr, 0, 1.f, 0, M, d, d, st));
-        // local branch: cgMLP (e_branchformer.py:291-292, 184-222)
-        RUN(gemm(w.a2, d, Lf(l, MLP_W1), d, Lf(l, MLP_B1), w.h, I, nullptr, 0, 1.f, 1, M, I, d, st));
-        RUN(mi_layernorm_f32(w.h + I / 2, I, nullptr, T2, nullptr, 0, Lf(l, CSGU_LN_G), Lf(l, CSGU_LN_B), leps, w.gn, I / 2, M, I / 2, st));
-        // quirk: the causal CSGU conv is dilated by (K-1)/2 (e_branchformer.py:153-160 passes it in the dilation slot)
-        const int dil = c.is_causal ? (kc - 1) / 2 : 1;
-        const int cpad = c.is_causal ? (kc - 1) * dil : (kc - 1) / 2;
-        if (c.csgu_linear) {   // conv -> Linear -> act -> gate (e_branchformer.py:196-201)
-            RUN(mi_dwconv_f32(w.gn, I / 2, Lf(l, CSGU_W), Lf(l, CSGU_B), nullptr, 0, w.cv, I / 2, c.B, T2, I / 2, kc, cpad, dil, 0, 0, st));
-            RUN(gemm(w.cv, I / 2, Lf(l, CSGU_LIN_W), I / 2, Lf(l, CSGU_LIN_B), w.lin, I / 2, nullptr, 0, 1.f, 0, M, I / 2, I / 2, st));
-            RUN(mi_gate_act_mul_f32(w.h, I, w.lin, I / 2, w.s, I / 2, M, I / 2, c.csgu_act, st));
-        } else
-            RUN(mi_dwconv_f32(w.gn, I / 2, Lf(l, CSGU_W), Lf(l, CSGU_B), w.h, I, w.s, I / 2, c.B, T2, I / 2, kc, cpad, dil, c.csgu_act, 1, st));
-        RUN(gemm(w.s, I / 2, Lf(l, MLP_W2), I / 2, Lf(l, MLP_B2), w.cat + d, 2 * d, nullptr, 0, 1.f, 0, M, d, I / 2, st));
-        // merge (e_branchformer.py:296-304)
-        RUN(mi_dwconv_f32(w.cat, 2 * d, Lf(l, MRG_DW_W), Lf(l, MRG_DW_B), nullptr, 0, w.m2, 2 * d, c.B, T2, 2 * d, km, (km - 1) / 2, 1, 0, 2, st));
-        RUN(gemm(w.m2, 2 * d, Lf(l, MRG_W), 2 * d, Lf(l, MRG_B), w.x, d, w.x, d, 1.0f, 0, M, d, 2 * d, st));
-        if (c.use_macaron) {   // e_branchformer.py:307-309
-            RUN(ln(w.x, nullptr, nullptr, Lf(l, FF2_LN_G), Lf(l, FF2_LN_B), leps, w.a0));
-            RUN(gemm(w.a0, d, Lf(l, FF2_W1), d, Lf(l, FF2_B1), w.h, I, nullptr, 0, 1.f, 1, M, I, d, st));
-            RUN(gemm(w.h, I, Lf(l, FF2_W2), I, Lf(l, FF2_B2), w.x, d, w.x, d, 0.5f, 0, M, d, I, st));
-        }
-        // final_layer_norm (:312), then the next consumer's LayerNorm(s)
-        if (l + 1 == c.L) {
-            RUN(ln(w.x, nullptr, nullptr, Lf(l, FIN_LN_G), Lf(l, FIN_LN_B), leps, w.a0));
-            float* lh = last_hidden ? last_hidden : w.hid;
-            RUN(ln(w.a0, nullptr, nullptr, Gf(G_ENC_LN_G), Gf(G_ENC_LN_B), c.ln_eps, lh));      // encoder.layer_norm (tf:707)
-            // CTC head: lm_head ⊕ blank_projection, blank LAST (e_branchformer.py:456-457)
-            if (logits) {
-                const long ldl = c.logits_ld > 0 ? c.logits_ld : c.V + 1;
-                RUN(gemm(lh, d, Gf(G_HEAD_W), d, Gf(G_HEAD_B), logits, ldl, nullptr, 0, 1.f, 0, M, c.V + 1, d, st));
-            }
-        } else {
-            RUN(ln(w.x, nullptr, nullptr, Lf(l, FIN_LN_G), Lf(l, FIN_LN_B), leps, w.x));
-            if (c.use_macaron) RUN(ln(w.x, nullptr, nullptr, Lf(l + 1, FF1_LN_G), Lf(l + 1, FF1_LN_B), leps, w.a0));
-            else {
-                RUN(ln(w.x, nullptr, nullptr, Lf(l + 1, ATT_LN_G), Lf(l + 1, ATT_LN_B), leps, w.a1));
-                RUN(ln(w.x, nullptr, nullptr, Lf(l + 1, MLP_LN_G), Lf(l + 1, MLP_LN_B), leps, w.a2));
-            }
-        }
+        RUN(f.layer(l));
+        RUN(f.exit(l, last_hidden, logits));
     }
     MI_CHECK_LAUNCH();
     return MI_OK;

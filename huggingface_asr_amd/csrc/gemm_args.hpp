@@ -64,7 +64,7 @@ bool gemm_8p128_supported(const GemmArgs& a);
 int gemm_8p128_launch(const GemmArgs& a, int ring, hipStream_t stream);
 
 
-// Profiling hand-off (diagnostics; encoder.hip `mi_profile_*`): while a profiling slot is open the dense-contraction launchers start their kernel with
+// Profiling hand-off (diagnostics; diag.hip `mi_profile_*`): while a profiling slot is open the dense-contraction launchers start their kernel with
 // hipExtLaunchKernelGGL and the slot's (start, stop) events, so the pair carries the DISPATCH's own begin / end timestamps — the quantity rocprofv3 --kernel-trace
 // reports — instead of bracketing the launch with two hipEventRecord markers, which also times the gap between the markers and the kernel.
 // `family`: 0 gemm8p 256x256 (bf16 out, no activation), 1 gemm8p + GELU epilogue, 2 gemm8p implicit-GEMM conv, 3 gemm8p fp32 out (CTC head), 4 gemm8p128 (N = 512 class),

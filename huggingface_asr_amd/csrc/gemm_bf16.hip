@@ -171,7 +171,7 @@ __global__ __launch_bounds__(NT) void gemm_bf16_kernel(GemmArgs p) {
 }
 
 }  // namespace
-// optional per-launch HIP-event timing of the dense GEMM kernel (bench.py's roofline leg); see encoder.hip
+// optional per-launch HIP-event timing of the dense GEMM kernel (bench.py's roofline leg); see diag.hip
 extern "C" int mi_profile_hook_begin(hipStream_t stream, double flops);
 extern "C" void mi_profile_hook_end(int slot, hipStream_t stream);
 namespace {

@@ -9,6 +9,7 @@
 // Parameter gradients ACCUMULATE (+=, float atomics at block granularity): the step zeroes the flat gradient buffer once.
 #include "common.hpp"
 #include "../../include/hfasr_hip.h"       // mi_lnred_desc
+#include "ebf_layout.hpp"                  // launch_subsampled_lengths
 
 namespace {
 
@@ -865,21 +866,11 @@ extern "C" int mi_add_rowvec2_bf16(const void* x, long ldx, const float* u, cons
     return MI_OK;
 }
 // frame counts behind the two-layer Conv2d sub-sampling for every utterance in one launch (the dozen one-block torch kernels of the length arithmetic were 70 us of a step):
-// inner = min(the count with the convs' padding, tmax) — what the encoder's masks use —, outer = the count without padding — what the CTC loss is given
-// (reference: _get_feat_extract_output_lengths with / without padding).  Floor division as torch.div(rounding_mode="floor").
-__global__ void subsampled_lengths_kernel(const int* __restrict__ in, int B, int k, int s, int p, int layers, int tmax, int* __restrict__ inner, int* __restrict__ outer) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    auto fdiv = [](int a, int d) { int q = a / d; if ((a % d) != 0 && ((a < 0) != (d < 0))) --q; return q; };
-    int li = in[b], lo = li;
-    for (int i = 0; i < layers; ++i) { li = fdiv(li + 2 * p - k, s) + 1; lo = fdiv(lo - k, s) + 1; }
-    inner[b] = li < tmax ? li : tmax;
-    outer[b] = lo;
-}
+// the whole-encoder drivers' length kernel (ebf_layout.hpp `launch_subsampled_lengths`) with the convs' symmetric padding
 extern "C" int mi_subsampled_lengths_i32(const int* lengths, int B, int kernel, int stride, int pad, int layers, int tmax, int* inner, int* outer, hipStream_t st) {
     MI_ENTER();
     if (!lengths || !inner || !outer || B <= 0 || kernel <= 0 || stride <= 0 || pad < 0 || layers < 0) return MI_ERR_ARG;
-    hipLaunchKernelGGL(subsampled_lengths_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, lengths, B, kernel, stride, pad, layers, tmax, inner, outer);
+    launch_subsampled_lengths(lengths, 0, B, kernel, stride, 2 * pad, layers, tmax, inner, outer, st);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }

@@ -675,7 +675,7 @@ typedef struct {
                                     then share the chip by CU instead of taking turns on all of it.  Same results as 0 up to the summation order of the row statistics. */
 } mi_ebf_config;
 
-/* weight-table slot indices: see huggingface_asr_amd/engine.py (SLOTS) — the table is an array of device pointers. */
+/* weight-table slot indices: enum G / enum LS in huggingface_asr_amd/csrc/ebf_layout.hpp, mirrored by G / LS in huggingface_asr_amd/engine.py — the table is an array of device pointers. */
 enum { MI_EBF_GLOBAL_SLOTS = 24, MI_EBF_LAYER_SLOTS = 64 };
 
 size_t mi_ebf_workspace_bytes(const mi_ebf_config* cfg);

@@ -58,7 +58,7 @@ def _mods():
 # ----------------------------------------------------------------------------------------------------------------- which kernel family ran
 @pytest.fixture(scope="module")
 def prof():
-    """the library's profiling slots (huggingface_asr_amd/csrc/encoder.hip mi_profile_*): created once per process — MI_ERR_ARG means an earlier user already made them, which is fine —
+    """the library's profiling slots (huggingface_asr_amd/csrc/diag.hip mi_profile_*): created once per process — MI_ERR_ARG means an earlier user already made them, which is fine —
     enabled for this module, disabled at teardown"""
     _lib, _ = _mods()
     L = _lib.lib()
