@@ -179,6 +179,7 @@ SIGNATURES = {
     "mi_linear_rows": [vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, i64, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp],
     "mi_greedy_advance": [vp, vp, i64, i32, i64, i64, vp, vp, vp, i32, vp],
     "mi_whisper_timestamp_argmax": [vp, i64, i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, i32, vp],
+    "mi_whisper_beam_scores": [vp, i64, i32, vp, i64, i32, i32, vp, i32, i32, i32, i32, vp, i32, vp],
     "mi_kv_cache_reorder": [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
     "mi_ctc_prefix_advance": [vp, i32, i32, i32, i32, i32, vp, vp, i64, i32, vp, vp, i64, i32, vp, vp, vp, vp],
     "mi_ctc_prefix_score_full": [vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, i64, i32, vp, vp, vp, vp],

@@ -16,7 +16,7 @@ The Whisper branch (`model_utils.py:183` on a Whisper checkpoint, `decode_whispe
 for that class (`train_enc_dec_asr.py:82-83`) — and gets the HIP encoder through `whisper.install_whisper()` (called by `bind_all()`): `WhisperEncoder.forward` is replaced,
 decoder / `generate` / checkpoints stay transformers' own — unless HFASR_WHISPER_DECODER=1 (the teacher-forced decoder pass of training on the HIP engine),
 HFASR_WHISPER_FUSED_LOSS=1 (also the training loss out of the tied head's GEMM) or HFASR_WHISPER_GENERATE=1 (`generate`'s short-form greedy decoding on the HIP decoder:
-`whisper.hip_whisper_generate`) is set in the environment `bind_all()` runs in.
+`whisper.hip_whisper_generate`; HFASR_WHISPER_BEAMS=1 implies it and adds beam search, `whisper.beam_decode`) is set in the environment `bind_all()` runs in.
 
 HFASR_CTC_BEAM=1 in the environment `install()` runs in also swaps `utilities.eval_utils.ctc_beam_decode` for the device prefix beam search (`decoding.ctc_beam_decode`);
 without it that function stays the reference's, because the two do not compute the same thing."""
@@ -73,8 +73,9 @@ def bind_all():
     from .whisper import install_whisper                          # the Whisper branch (model_utils.py:183 on a Whisper checkpoint): HF's classes, our encoder forward
     import os                                                     # HFASR_WHISPER_DECODER=1 / HFASR_WHISPER_FUSED_LOSS=1: the decoder's training pass / the fused loss (opt-in)
     install_whisper(decoder=os.environ.get("HFASR_WHISPER_DECODER") == "1", fused_loss=os.environ.get("HFASR_WHISPER_FUSED_LOSS") == "1")
-    if os.environ.get("HFASR_WHISPER_GENERATE") == "1":           # `generate` — short-form greedy decoding — on the HIP path (opt-in)
-        install_whisper(generate=True)
+    beams = os.environ.get("HFASR_WHISPER_BEAMS") == "1"          # beam search (num_beams 2 .. 64) on the HIP path too; implies HFASR_WHISPER_GENERATE (opt-in)
+    if beams or os.environ.get("HFASR_WHISPER_GENERATE") == "1":  # `generate` — short-form greedy decoding — on the HIP path (opt-in)
+        install_whisper(generate=True, beams=beams)
     ref_enc = sys.modules.get("models.encoders.e_branchformer")  # wav2vec2-style contrastive pre-training is not built on the HIP path: when the reference's
     ref_pt = getattr(ref_enc, "Wav2Vec2EBranchformerForPreTraining", None) if ref_enc is not None else None      # tree is loaded its own PyTorch class stays reachable
     if isinstance(ref_pt, type):                                 # through AutoModelForPreTraining, as its bind_all registers it (reference bind.py:42)

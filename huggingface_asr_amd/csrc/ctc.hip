@@ -5,6 +5,7 @@
 // UN-padded conv formula (SURVEY.md §8a row 8').  log_softmax is never materialised: the loss only needs
 // lse[b,t] and the logits at the blank / label columns, so the (B,T,V+1) tensor is read exactly once.
 #include "common.hpp"
+#include "row_lse.hpp"
 
 namespace {
 
@@ -35,10 +36,8 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const T* __restrict__ x, l
     float mx = -INFINITY;
     for (int c = lane; c < V; c += 64) mx = fmaxf(mx, (float)xr[c]);
     mx = wave_max(mx);
-    float s = 0.f;
-    for (int c = lane; c < V; c += 64) s += __expf((float)xr[c] - mx);
-    s = wave_sum(s);
-    if (lane == 0) lse[row] = mx + __logf(s);
+    const float r = wave_row_lse_given_max(xr, V, mx, lane);
+    if (lane == 0) lse[row] = r;
 }
 
 __device__ __forceinline__ double lse3(double a, double b, double c) {

@@ -11,7 +11,9 @@
 // One pass: per thread the best key (common.hpp argmax_*: torch.argmax's order) of each interval and an online log-sum-exp of the timestamp interval; wave reductions by
 // xor shuffles, then the four waves' partials through LDS, combined in wave order by every thread — no atomics, the result is a fixed function of the inputs.  A row in
 // which nothing finite survives gives 0, as torch.argmax over a row of -inf.
+// Beam search takes the same rules as a mask over the step's logits plus the raw row's log-sum-exp (mi_whisper_beam_scores, further down).
 #include "common.hpp"
+#include "row_lse.hpp"
 #include "../../include/hfasr_hip.h"
 
 namespace {
@@ -43,38 +45,44 @@ __device__ __forceinline__ void fold(Part& p, float v, int i, int t_lo, int t_hi
     if (i >= s_lo && i < s_hi) { p.ts = argmax_max(p.ts, argmax_key(v, i)); p.l = lse_push(p.l, v); }
 }
 
-__global__ __launch_bounds__(256) void whisper_timestamp_argmax_kernel(TsArgs a) {
-    __shared__ int s_pos[4];
-    __shared__ amax_t s_text[4], s_ts[4];
-    __shared__ float s_m[4], s_s[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
-    const long* seq = a.ids + (long)row * a.ld_ids;
-    const int tb = a.no_ts + 1, n = a.cur - a.begin;
+// The surviving intervals [t_lo, t_hi) of text and [s_lo, s_hi) of timestamps of one row under rules 1-4, by the whole 256-thread block (one barrier; s_pos: 4 ints of LDS)
+__device__ __forceinline__ void ts_intervals(const long* seq, int begin, int cur, int V, int no_ts, int eos, int max_initial, int* s_pos, int& t_lo, int& t_hi, int& s_lo,
+                                             int& s_hi) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tb = no_ts + 1, n = cur - begin;
     // history: position of the last sampled timestamp (backward scan: a thread stops at its first hit), -1 when there is none
     int pos = -1;
-    for (int j = a.cur - 1 - tid; j >= a.begin; j -= 256)
+    for (int j = cur - 1 - tid; j >= begin; j -= 256)
         if (seq[j] >= tb) { pos = j; break; }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) pos = max(pos, __shfl_xor(pos, o, 64));
     if (lane == 0) s_pos[wave] = pos;
     __syncthreads();
     pos = max(max(s_pos[0], s_pos[1]), max(s_pos[2], s_pos[3]));
-    const bool last_ts = n >= 1 && seq[a.cur - 1] >= tb;
-    const bool pen_ts = n < 2 || seq[a.cur - 2] >= tb;
-    // the surviving intervals [t_lo, t_hi) of text and [s_lo, s_hi) of timestamps
-    int t_lo = 0, t_hi = a.no_ts < a.V ? a.no_ts : a.V, s_lo = tb, s_hi = a.V;
+    const bool last_ts = n >= 1 && seq[cur - 1] >= tb;
+    const bool pen_ts = n < 2 || seq[cur - 2] >= tb;
+    t_lo = 0; t_hi = no_ts < V ? no_ts : V; s_lo = tb; s_hi = V;
     if (last_ts) {
         if (pen_ts) s_hi = 0;
-        else { t_lo = max(t_lo, a.eos); s_lo = max(s_lo, a.eos); }
+        else { t_lo = max(t_lo, eos); s_lo = max(s_lo, eos); }
     }
     if (pos >= 0) {
         const long tl = seq[pos] + ((last_ts && !pen_ts) ? 0 : 1);
-        s_lo = max(s_lo, (int)(tl < (long)a.V ? tl : (long)a.V));
+        s_lo = max(s_lo, (int)(tl < (long)V ? tl : (long)V));
     }
     if (n == 0) {
         t_hi = 0;
-        if (a.max_initial >= 0 && a.max_initial < a.V) s_hi = min(s_hi, tb + a.max_initial + 1);      // (an index past the vocabulary masks nothing)
+        if (max_initial >= 0 && max_initial < V) s_hi = min(s_hi, tb + max_initial + 1);      // (an index past the vocabulary masks nothing)
     }
+}
+
+__global__ __launch_bounds__(256) void whisper_timestamp_argmax_kernel(TsArgs a) {
+    __shared__ int s_pos[4];
+    __shared__ amax_t s_text[4], s_ts[4];
+    __shared__ float s_m[4], s_s[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
+    int t_lo, t_hi, s_lo, s_hi;
+    ts_intervals(a.ids + (long)row * a.ld_ids, a.begin, a.cur, a.V, a.no_ts, a.eos, a.max_initial, s_pos, t_lo, t_hi, s_lo, s_hi);
     // one pass over the row
     const float* xr = a.logits + (long)row * a.ld;
     Part p{ARGMAX_EMPTY, ARGMAX_EMPTY, Lse{-INFINITY, 0.f}};
@@ -119,7 +127,124 @@ __global__ __launch_bounds__(256) void whisper_timestamp_argmax_kernel(TsArgs a)
     }
 }
 
+// ---- beam search.  transformers' `_beam_search` takes log_softmax of the RAW logits first and hands the log-probabilities to the processors, so a suppressed column counts
+// in the normaliser and the greedy path's -inf head bias cannot be used.  Per row this kernel gives the beam-step kernels (which form logit - lse themselves) both halves:
+// lse of the raw row, and the row with -inf in every column the processors mask — begin-suppress / suppress (`sup`, 0 / -inf, nullable), then the timestamp rules above
+// (off when no_ts < 0) — every other value left as it is, not even re-written.  Rule 5 is decided on the surviving columns with the greedy kernel's arithmetic (lse_push /
+// lse_join, waves combined in order): the normaliser is the same on both sides and cancels.
+// Phases, one block per row: (A) all 256 threads read the row once (16-B loads where the row is aligned): the raw maximum, the best surviving text value, the online
+// log-sum-exp of the surviving timestamps;  (A') wave 0 runs mi_row_lse's sum pass (row_lse.hpp) under that maximum, over a row that is now in cache — the same code on
+// the same column order, so lse[row] is mi_row_lse's bit for bit;  (B) after a barrier (the row is rewritten in place, and (A') must have read it whole) every thread
+// stores -inf to the masked columns of its share: 16-B stores where four neighbours go together, nothing is loaded but `sup`.  No atomics, no scratch.
+struct BeamScoreArgs {
+    float* logits; long ld; int V;
+    const long* ids; long ld_ids; int begin, cur;
+    const float* sup;
+    int no_ts, eos, max_initial, detect;
+    float* lse;
+};
+
+struct Stat { float rmax, tmax; Lse l; };
+
+__device__ __forceinline__ void fold_stat(Stat& p, float v, bool suppressed, int i, int t_lo, int t_hi, int s_lo, int s_hi) {
+    p.rmax = fmaxf(p.rmax, v);
+    if (suppressed) return;
+    if (i >= t_lo && i < t_hi) p.tmax = fmaxf(p.tmax, v);
+    if (i >= s_lo && i < s_hi) p.l = lse_push(p.l, v);
+}
+
+__global__ __launch_bounds__(256) void whisper_beam_scores_kernel(BeamScoreArgs a) {
+    __shared__ int s_pos[4];
+    __shared__ float s_r[4], s_t[4], s_m[4], s_s[4];
+    __shared__ float s_mx;
+    __shared__ int s_drop;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, row = blockIdx.x;
+    int t_lo = 0, t_hi = a.V, s_lo = a.V, s_hi = a.V;                  // rules off: everything is text, nothing is a timestamp
+    if (a.no_ts >= 0) ts_intervals(a.ids + (long)row * a.ld_ids, a.begin, a.cur, a.V, a.no_ts, a.eos, a.max_initial, s_pos, t_lo, t_hi, s_lo, s_hi);
+    float* xr = a.logits + (long)row * a.ld;
+    const bool vec = (reinterpret_cast<uintptr_t>(xr) & 15) == 0 && (a.sup == nullptr || (reinterpret_cast<uintptr_t>(a.sup) & 15) == 0);
+    const int nvec = vec ? a.V / 4 : 0;
+    // (A) one read of the row
+    Stat p{-INFINITY, -INFINITY, Lse{-INFINITY, 0.f}};
+    {
+        const f32x4* xv = reinterpret_cast<const f32x4*>(xr);
+        const f32x4* sv = reinterpret_cast<const f32x4*>(a.sup);
+        for (int q = tid; q < nvec; q += 256) {
+            const f32x4 v = xv[q];
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+            if (a.sup) s = sv[q];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) fold_stat(p, v[e], s[e] == -INFINITY, q * 4 + e, t_lo, t_hi, s_lo, s_hi);
+        }
+        for (int c = nvec * 4 + tid; c < a.V; c += 256) fold_stat(p, xr[c], a.sup && a.sup[c] == -INFINITY, c, t_lo, t_hi, s_lo, s_hi);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        p.rmax = fmaxf(p.rmax, __shfl_xor(p.rmax, o, 64));
+        p.tmax = fmaxf(p.tmax, __shfl_xor(p.tmax, o, 64));
+        p.l = lse_join(p.l, Lse{__shfl_xor(p.l.m, o, 64), __shfl_xor(p.l.s, o, 64)});
+    }
+    if (lane == 0) { s_r[wave] = p.rmax; s_t[wave] = p.tmax; s_m[wave] = p.l.m; s_s[wave] = p.l.s; }
+    __syncthreads();
+    if (tid == 0) {
+        float r = s_r[0], t = s_t[0];
+        Lse l{s_m[0], s_s[0]};
+        for (int w = 1; w < 4; ++w) { r = fmaxf(r, s_r[w]); t = fmaxf(t, s_t[w]); l = lse_join(l, Lse{s_m[w], s_s[w]}); }
+        const float ts_lse = l.s > 0.f ? l.m + logf(l.s) : -INFINITY;
+        s_mx = r;
+        s_drop = (a.detect && a.no_ts >= 0 && ts_lse > t) ? 1 : 0;
+    }
+    __syncthreads();
+    // (A') the raw row's log-sum-exp: mi_row_lse's sum pass by one wave
+    if (wave == 0) {
+        const float r = wave_row_lse_given_max(xr, a.V, s_mx, lane);
+        if (lane == 0) a.lse[row] = r;
+    }
+    if (s_drop) t_hi = t_lo;                                           // rule 5: the text goes
+    __syncthreads();
+    // (B) -inf into the masked columns
+    const float NI = -INFINITY;
+    {
+        f32x4* xv = reinterpret_cast<f32x4*>(xr);
+        const f32x4* sv = reinterpret_cast<const f32x4*>(a.sup);
+        for (int q = tid; q < nvec; q += 256) {
+            f32x4 s = {0.f, 0.f, 0.f, 0.f};
+            if (a.sup) s = sv[q];
+            bool m[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int c = q * 4 + e;
+                m[e] = s[e] == -INFINITY || !((c >= t_lo && c < t_hi) || (c >= s_lo && c < s_hi));
+            }
+            if (m[0] && m[1] && m[2] && m[3]) xv[q] = f32x4{NI, NI, NI, NI};
+            else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (m[e]) xr[q * 4 + e] = NI;
+            }
+        }
+        for (int c = nvec * 4 + tid; c < a.V; c += 256)
+            if ((a.sup && a.sup[c] == -INFINITY) || !((c >= t_lo && c < t_hi) || (c >= s_lo && c < s_hi))) xr[c] = NI;
+    }
+}
+
 }  // namespace
+
+extern "C" int mi_whisper_beam_scores(float* logits, long ld, int V, const long* ids, long ld_ids, int begin_index, int cur_len, const float* suppress,
+                                      int no_timestamps_token_id, int eos_token_id, int max_initial_timestamp_index, int detect_from_logprob, float* lse, int rows,
+                                      hipStream_t stream) {
+    MI_ENTER();
+    if (!logits || !lse || rows <= 0 || V <= 0 || ld < V) return MI_ERR_ARG;
+    if (no_timestamps_token_id >= 0) {
+        if (!ids || begin_index < 0 || cur_len < begin_index || cur_len > ld_ids) return MI_ERR_ARG;
+        if (no_timestamps_token_id >= V || eos_token_id < 0 || eos_token_id > V || max_initial_timestamp_index < -1) return MI_ERR_ARG;
+    }
+    BeamScoreArgs a{logits, ld, V, ids, ld_ids, begin_index, cur_len, suppress, no_timestamps_token_id < 0 ? -1 : no_timestamps_token_id, eos_token_id,
+                    max_initial_timestamp_index, detect_from_logprob ? 1 : 0, lse};
+    hipLaunchKernelGGL(whisper_beam_scores_kernel, dim3(rows), dim3(256), 0, stream, a);
+    MI_CHECK_LAUNCH();
+    return MI_OK;
+}
 
 extern "C" int mi_whisper_timestamp_argmax(const float* logits, long ld, int V, const long* ids, long ld_ids, int begin_index, int cur_len, int no_timestamps_token_id,
                                            int eos_token_id, int max_initial_timestamp_index, int detect_from_logprob, int* best, int B, hipStream_t stream) {

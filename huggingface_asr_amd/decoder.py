@@ -431,12 +431,14 @@ class JointAEDEngine:
 _ES_MODE = {False: 0, True: 1, "never": 2}
 
 
-def _step_denoms(cur_len, max_length, length_penalty, early_stopping):
-    """(closing denominator, early-stop denominator) of the step that extends prefixes of `cur_len` tokens (one of them the start token), as fp32 values:
-    generated tokens of a hypothesis closed now = cur_len; hypothetical length of the early-stop rule = cur_len, or max_length - 1 for "never" with a positive penalty."""
+def _step_denoms(cur_len, max_length, length_penalty, early_stopping, prompt_len=1):
+    """(closing denominator, early-stop denominator) of the step that extends prefixes of `cur_len` tokens (`prompt_len` of them the prompt: the start token), as fp32
+    values: generated tokens of a hypothesis closed now = cur_len + 1 - prompt_len; hypothetical length of the early-stop rule = the same, or max_length - prompt_len for
+    "never" with a positive penalty."""
     import numpy as np
-    hyp = (max_length - 1) if (early_stopping == "never" and length_penalty > 0.0) else cur_len
-    return float(np.float32(cur_len ** length_penalty)), float(np.float32(hyp ** length_penalty))
+    gen = cur_len + 1 - prompt_len
+    hyp = (max_length - prompt_len) if (early_stopping == "never" and length_penalty > 0.0) else gen
+    return float(np.float32(gen ** length_penalty)), float(np.float32(hyp ** length_penalty))
 
 
 def _stop_rule(num_beams, cur_len, max_length, length_penalty, early_stopping):

@@ -389,6 +389,31 @@ def whisper_timestamp_argmax(logits, ids, *, begin_index, cur_len, no_timestamps
     return out
 
 
+def whisper_beam_scores(logits, ids, *, begin_index, cur_len, suppress=None, no_timestamps_token_id=None, eos_token_id=0, max_initial_timestamp_index=None,
+                        detect_from_logprob=True):
+    """One beam-search step's scores under Whisper's rules, for `mi_beam_step*` (which form logit - lse themselves): logits (rows, V) fp32 (contiguous rows, any row stride,
+    no head bias) are rewritten IN PLACE — -inf where `suppress` ((V) fp32 of 0 / -inf, or None) or transformers' `WhisperTimeStampLogitsProcessor(ids[:, :cur_len], .)`
+    masks, every other value untouched — and the raw rows' log-sum-exp is returned: (rows) fp32, `row_lse`'s bits.  `no_timestamps_token_id` None: suppression only
+    (mi_whisper_beam_scores: one launch, one block per row)."""
+    _req(logits, torch.float32); _req(ids, torch.long)
+    if logits.dim() != 2 or logits.stride(1) != 1 or ids.dim() != 2 or ids.stride(1) != 1 or ids.shape[0] != logits.shape[0]:
+        raise TypeError("whisper_beam_scores: logits (rows, V) fp32 and ids (rows, Lmax) int64, both with contiguous rows")
+    rows, V = logits.shape
+    if not 0 <= begin_index <= cur_len <= ids.shape[1]:
+        raise ValueError(f"whisper_beam_scores: need 0 <= begin_index ({begin_index}) <= cur_len ({cur_len}) <= {ids.shape[1]}")
+    if suppress is not None:
+        _req(suppress, torch.float32)
+        if suppress.shape != (V,) or not suppress.is_contiguous():
+            raise TypeError(f"whisper_beam_scores: suppress must be a contiguous ({V}) fp32 vector")
+    out = torch.empty((rows,), device=logits.device, dtype=torch.float32)
+    rc = _lib.lib().mi_whisper_beam_scores(logits.data_ptr(), logits.stride(0), V, ids.data_ptr(), ids.stride(0), int(begin_index), int(cur_len), _p(suppress),
+                                           -1 if no_timestamps_token_id is None else int(no_timestamps_token_id), int(eos_token_id),
+                                           -1 if max_initial_timestamp_index is None else int(max_initial_timestamp_index), 1 if detect_from_logprob else 0,
+                                           out.data_ptr(), rows, _stream())
+    _lib.check(rc, "mi_whisper_beam_scores")
+    return out
+
+
 def gemm_argmax(a, w, bias):
     """the CTC head without its logits: -> (M) int32 = argmax_n (a W^T + b)[m, n] out of the GEMM's epilogue (mi_gemm_argmax_bf16: no (M, N) tensor is written);
     shapes outside that kernel: the fp32 GEMM into a scratch followed by row_argmax."""

@@ -341,8 +341,11 @@ class WhisperDecoderEngine(GPT2DecoderEngine):
             return self.step_form
         return 2 if (rows, self.cfg["d_model"]) in self.STREAMING_AT else 1
 
-    def step(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, head_bias=None):
-        """ids_new (B, U) -> fp32 logits (B, V) of the last new position (+ head_bias (V) fp32, 0 / -inf); appends to the KV cache.  One C call (mi_decoder_step)."""
+    def step(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, head_bias=None, beams: int = 1):
+        """ids_new (B, U) -> fp32 logits (B, V) of the last new position (+ head_bias (V) fp32, 0 / -inf); appends to the KV cache.  One C call (mi_decoder_step).
+        `beams` > 1 (beam search): the B rows are B / beams utterances x `beams` hypotheses, utterance-major, that share their utterance's cross K/V — `kvs` are the
+        (B / beams * T_enc, 2d) tables of the un-replicated encoder output; one new token per row, no head bias (the beam loop masks log-probabilities, not logits):
+        mi_decoder_step_beams."""
         ids_new = ids_new.contiguous()
         B, U = ids_new.shape
         past, Lmax = cache["past"], cache["Lmax"]
@@ -360,6 +363,15 @@ class WhisperDecoderEngine(GPT2DecoderEngine):
         V = self._gcfg.V
         Vp = (V + 7) // 8 * 8
         buf = torch.empty((B, Vp), device=self.device, dtype=torch.float32)
+        if beams != 1:
+            if beams < 1 or B % beams or U != 1 or head_bias is not None or kvs[0].shape[0] != B // beams * T_enc:
+                raise ValueError(f"step(beams={beams}): {B} rows of {U} new tokens over cross tables of {kvs[0].shape[0]} rows (T_enc = {T_enc}), head bias "
+                                 f"{'given' if head_bias is not None else 'none'}")
+            _lib.check(L_.mi_decoder_step_beams(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, beams, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc,
+                                                None, float(self.w["scale"]), None, self._step_ws.data_ptr(), self._step_ws.numel(), buf.data_ptr(), Vp,
+                                                torch.cuda.current_stream().cuda_stream), "mi_decoder_step_beams")
+            cache["past"] = past + U
+            return buf[:, :V]
         _lib.check(L_.mi_decoder_step(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc, None,
                                       float(self.w["scale"]), head_bias.data_ptr() if head_bias is not None else None, self._step_ws.data_ptr(), self._step_ws.numel(),
                                       buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_decoder_step")
@@ -606,6 +618,132 @@ def greedy_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new
         stats["steps"] = steps
         stats["tokens"] = n
     return ids[:, :P + n]
+
+
+def fan_out_cache(dec_engine, src_cache, W, dst=None):
+    """The self-attention cache of B prompts -> a cache of B * W rows (double-buffered, as `reorder_cache` needs it) whose rows b * W + k hold row b's consumed positions:
+    `mi_kv_cache_reorder`, which gathers rows by index, with a B-row source and the index b * W + k -> b.  Positions past the consumed ones are not written: they stay
+    as `init_cache` leaves them (or as the given `dst`, a cache of B * W rows and the source's positions, holds them)."""
+    B, Lmax, d = src_cache["k"][0].shape
+    if dst is None:
+        dst = dec_engine.init_cache(B * W, Lmax)
+    elif tuple(dst["k"][0].shape) != (B * W, Lmax, d):
+        raise ValueError(f"fan_out_cache: dst holds {tuple(dst['k'][0].shape)}, needed {(B * W, Lmax, d)}")
+    idx = torch.arange(B * W, dtype=torch.long, device=dec_engine.device) // W
+    _lib.check(_lib.lib().mi_kv_cache_reorder(src_cache["tk"], src_cache["tv"], dst["tk"], dst["tv"], idx.data_ptr(), len(dst["k"]), B * W, src_cache["past"], Lmax, d,
+                                              torch.cuda.current_stream().cuda_stream), "mi_kv_cache_reorder")
+    dst["past"] = src_cache["past"]
+    return dst
+
+
+def beam_decode(enc_engine, dec_engine, input_features, prompt_ids, *, max_new_tokens, eos_token_id, pad_token_id, num_beams, length_penalty=1.0, early_stopping=False,
+                suppress_tokens=None, begin_suppress_tokens=None, run_ahead=2, stats=None, timestamps=None, state=None, route=None):
+    """Beam search with the loop on the device -> (B, P + n) LongTensor in the layout transformers' `_beam_search` returns for num_return_sequences = 1: per row the
+    prompt, the best kept hypothesis, its EOS (kept), then pad_token_id, trimmed to the longest row.  `greedy_decode`'s arguments plus `num_beams` (2 .. 64),
+    `length_penalty` and `early_stopping` (False, True, "never").
+    The prompt — what `state` has not consumed of it — runs ONCE per utterance, on B rows; `fan_out_cache` then copies each row's self-attention cache to its W hypotheses,
+    and the first step's logits are the B rows repeated W times under beam scores [0, -1e9, ...].  Per token after that: `WhisperDecoderEngine.step(beams=W)` (the W
+    hypotheses share their utterance's cross K/V: it exists B times, not B * W times), `ops.whisper_beam_scores` (transformers applies suppression and the timestamp
+    rules to log-probabilities here, so the raw row's log-sum-exp comes with the mask; the begin-suppress ids join it at the first generated position), the beam-step
+    kernel `decoder.beam_loop_route` picks (ctc NULL, mask_pad 0, the length-penalty denominators of `decoder._step_denoms` with the prompt length in place of 1) and the
+    cache re-ordering.  The host only enqueues, at most `run_ahead` steps in front of the pinned done flags it has seen; nothing is copied per token.
+    A request `beam_loop_route` would give to a host loop (more than 64 beams, W * V >= 2^24) raises NotImplementedError before anything is enqueued.  `route` forces
+    "device" / "device_wide" (tests, the bench tool).  `stats` receives steps, route and the kept hypotheses per utterance: [(score, tokens incl. the prompt)], best first."""
+    from .decoder import _ES_MODE, _step_denoms, beam_loop_route
+    if (state is None and not input_features.is_cuda) or not prompt_ids.is_cuda:
+        raise RuntimeError("beam_decode needs device tensors (no CPU fallback)")
+    dev = dec_engine.device
+    B, P = prompt_ids.shape
+    V, W = dec_engine.cfg["vocab_size"], int(num_beams)
+    if max_new_tokens < 1:
+        raise ValueError("max_new_tokens >= 1 required")
+    if W < 2:
+        raise ValueError("beam_decode needs num_beams >= 2 (one beam is greedy_decode)")
+    if early_stopping not in _ES_MODE:
+        raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
+    max_length = P + max_new_tokens
+    picked = beam_loop_route(W, V, max_length)
+    if picked == "host":
+        raise NotImplementedError(f"beam_decode: {W} beams over {V} tokens are outside the device loop (at most 64 beams, num_beams * vocab_size < 2^24)")
+    if route is not None:
+        if route not in ("device", "device_wide") or (route == "device" and picked != "device"):
+            raise ValueError(f"route {route!r} does not serve this request (beam_loop_route: {picked!r})")
+        picked = route
+    dec_engine.ensure_positions(max_length)
+    for name, t in (("eos_token_id", eos_token_id), ("pad_token_id", pad_token_id)):
+        if not 0 <= int(t) < V:
+            raise ValueError(f"{name} {t} outside the vocabulary [0, {V})")
+    eos, pad = int(eos_token_id), int(pad_token_id)
+    every, first = suppression_vectors(V, suppress_tokens, begin_suppress_tokens, dev)
+    ts = dict(no_timestamps_token_id=None, eos_token_id=eos)
+    if timestamps is not None:
+        ts = dict(no_timestamps_token_id=int(timestamps["no_timestamps_token_id"]), eos_token_id=eos,
+                  max_initial_timestamp_index=timestamps.get("max_initial_timestamp_index"), detect_from_logprob=bool(timestamps.get("detect_from_logprob", True)))
+        if not 0 <= ts["no_timestamps_token_id"] < V:
+            raise ValueError(f"no_timestamps_token_id {ts['no_timestamps_token_id']} outside the vocabulary [0, {V})")
+    if state is None:
+        enc = enc_engine.forward(input_features=input_features)
+        T2, d = enc.shape[1], enc.shape[2]
+        kvs = dec_engine.cross_kv(ops.cast_bf16(enc.reshape(B * T2, d)))
+        cache1 = dec_engine.init_cache(B, max_length)
+    else:
+        kvs, T2, cache1 = state["kvs"], state["T2"], state["cache"]
+        if cache1["k"][0].shape[0] != B or cache1["Lmax"] < max_length or not 0 <= cache1["past"] < P:
+            raise ValueError(f"state does not fit: its cache holds {cache1['k'][0].shape[0]} rows x {cache1['Lmax']} positions with {cache1['past']} consumed; "
+                             f"decoding needs {B} rows x {max_length} positions and a prompt of {P} > consumed")
+    # the prompt, once per utterance; its cache and its logits then fan out to the W hypotheses
+    base = dec_engine.step(prompt_ids[:, cache1["past"]:].to(torch.long).contiguous(), cache1, kvs, T2)
+    cache = fan_out_cache(dec_engine, cache1, W)
+    n_bh, Lmax = B * W, max_length + 1
+    Vp = (V + 7) // 8 * 8
+    logits = torch.empty((n_bh, Vp), dtype=torch.float32, device=dev)
+    logits.view(B, W, Vp)[:, :, :V] = base[:, None, :]
+    logits = logits[:, :V]
+    ids = torch.full((n_bh, Lmax), pad, dtype=torch.long, device=dev)
+    ids[:, :P] = prompt_ids.to(torch.long).repeat_interleave(W, 0)
+    beam_scores = torch.zeros((B, W), device=dev)
+    beam_scores[:, 1:] = -1e9
+    beam_scores = beam_scores.view(-1).contiguous()
+    done = torch.zeros((B,), dtype=torch.int32, device=dev)
+    nfin = torch.zeros((B,), dtype=torch.int32, device=dev)
+    fin_score = torch.zeros((B, W), dtype=torch.float32, device=dev)
+    fin_len = torch.zeros((B, W), dtype=torch.int32, device=dev)
+    fin_tok = torch.full((B, W, Lmax), pad, dtype=torch.long, device=dev)
+    done_host = torch.zeros((max_new_tokens, B), dtype=torch.int32).pin_memory()
+    L_ = _lib.lib()
+    main = torch.cuda.current_stream()
+    step_fn, step_name = (L_.mi_beam_step_wide, "mi_beam_step_wide") if picked == "device_wide" else (L_.mi_beam_step, "mi_beam_step")
+    flags, steps, cur_len = [], 0, P
+    new_tok = None
+    while cur_len < max_length:
+        if len(flags) >= run_ahead:                # bounded run-ahead on the pinned done flags, as in `decoder.generate`
+            flags[len(flags) - run_ahead].synchronize()
+            if bool(done_host[steps - run_ahead].all()):
+                break
+        if steps > 0:
+            logits = dec_engine.step(new_tok, cache, kvs, T2, beams=W)
+        lse = ops.whisper_beam_scores(logits, ids, begin_index=P, cur_len=cur_len, suppress=first if steps == 0 else every, **ts)
+        new_tok = torch.empty((n_bh, 1), dtype=torch.long, device=dev)
+        beam_idx = torch.empty((n_bh,), dtype=torch.long, device=dev)
+        denom, heur = _step_denoms(cur_len, max_length, length_penalty, early_stopping, prompt_len=P)
+        args = (logits.data_ptr(), logits.stride(0), lse.data_ptr(), None, 1.0, 0.0, 0, pad, eos, B, W, V, cur_len, max_length, Lmax, denom, heur, _ES_MODE[early_stopping],
+                ids.data_ptr(), beam_scores.data_ptr(), new_tok.data_ptr(), beam_idx.data_ptr(), done.data_ptr(), nfin.data_ptr(), fin_score.data_ptr(), fin_len.data_ptr(),
+                fin_tok.data_ptr(), None, None, done_host[steps].data_ptr())
+        if picked == "device_wide":
+            args += (None, 0, None, 0.0)
+        _lib.check(step_fn(*args, main.cuda_stream), step_name)
+        dec_engine.reorder_cache(cache, beam_idx)
+        ev = torch.cuda.Event()
+        ev.record(main)
+        flags.append(ev)
+        cur_len += 1
+        steps += 1
+    nfin_c, fs_c, fl_c, ft_c = nfin.cpu(), fin_score.cpu(), fin_len.cpu(), fin_tok.cpu()             # the first copy synchronises with everything enqueued
+    if stats is not None:
+        stats["steps"], stats["route"] = steps, picked
+        stats["hypotheses"] = [[(float(fs_c[b, k]), ft_c[b, k, :int(fl_c[b, k])].tolist()) for k in range(int(nfin_c[b]))] for b in range(B)]
+    n = int(fl_c[:, 0].max())                      # every utterance ends with kept hypotheses: at max_length the step's first W candidates all stop
+    return fin_tok[:, 0, :n].contiguous()
 
 
 _GENERATE_REFUSED = ("logits_processor", "stopping_criteria", "prefix_allowed_tokens_fn", "assistant_model", "streamer", "prompt_ids", "negative_prompt_ids")
@@ -1137,19 +1275,33 @@ _GENERATION_CONFIG_NEUTRAL = dict(repetition_penalty=1.0, encoder_repetition_pen
                                   num_beam_groups=1, penalty_alpha=None, prompt_lookup_num_tokens=None, cache_implementation=None)
 
 
-def generate_route(kwargs: dict, generation_config, config, input_shape) -> tuple[str, str | None]:
+BEAMS_ON_HIP = False            # the opt-in of `install_whisper(generate=True, beams=True)` / HFASR_WHISPER_BEAMS=1: `hip_whisper_generate` passes it to `generate_route`
+
+
+def generate_route(kwargs: dict, generation_config, config, input_shape, beams: bool = False) -> tuple[str, str | None]:
     """Where a `WhisperForConditionalGeneration.generate(**kwargs)` call runs: ("hip", None) or ("stock", reason) — transformers' own generate, said once per reason;
     HFASR_WHISPER_STRICT=1 raises.  `kwargs`: the call's keyword arguments; `generation_config`: the one the call decodes under (the model's with the call's overrides
     applied, `GenerationMixin._prepare_generation_config`); `input_shape`: of input_features, or None.  Pure: tensors are only asked for `.is_cuda`.
     HIP: greedy (num_beams 1 / None, no sampling), short-form input (B, mel, 2 max_source_positions) on the GPU, max_length / max_new_tokens, decoder_input_ids, language
     (a string or one per row), task, is_multilingual, forced_decoder_ids of the (generation) config, return_timestamps as a bool, attention_mask (not read for short-form
-    input, as in transformers), return_dict_in_generate False, labels (`Seq2SeqTrainer.prediction_step` passes the collator's along; not read, as in transformers)."""
+    input, as in transformers), return_dict_in_generate False, labels (`Seq2SeqTrainer.prediction_step` passes the collator's along; not read, as in transformers).
+    `beams` (the opt-in switch `BEAMS_ON_HIP`): num_beams 2 .. 64 — of the call or of the generation config — goes to the HIP path too (`beam_decode`, with the
+    generation config's length_penalty and early_stopping and num_return_sequences 1 / None); a request outside the device beam loop's limits is handed over with a
+    reason of its own.  With `beams` False every answer and every reason is what it was before the switch existed."""
     g, gc = kwargs.get, generation_config
     for name, why in _GENERATE_HANDED_OVER:
         if g(name) is not None and g(name) is not False:
             return "stock", why
-    if (g("num_beams") or getattr(gc, "num_beams", 1) or 1) > 1:
-        return "stock", "num_beams > 1"
+    num_beams = g("num_beams") or getattr(gc, "num_beams", 1) or 1
+    if num_beams > 1:
+        if not beams:
+            return "stock", "num_beams > 1"
+        from .decoder import _ES_MODE, beam_loop_route
+        if beam_loop_route(num_beams, config.vocab_size, config.max_target_positions) == "host":
+            return "stock", "num_beams beyond the device beam loop (at most 64 beams, num_beams * vocab_size < 2^24)"
+        es = g("early_stopping") if g("early_stopping") is not None else getattr(gc, "early_stopping", False)
+        if (False if es is None else es) not in _ES_MODE:
+            return "stock", "early_stopping that is not False, True or 'never'"
     temperature = g("temperature")
     if isinstance(temperature, (list, tuple)):
         if len(temperature) != 1:
@@ -1286,10 +1438,11 @@ def resolved_generation_config(model, generation_config, kwargs: dict):
 def hip_whisper_generate(self, input_features=None, generation_config=None, **kwargs):
     """`WhisperForConditionalGeneration.generate`: short-form greedy calls — `generate_route` — on the HIP path (`build_prompt`, `detect_language`, `greedy_decode`, the
     timestamp rules in `mi_whisper_timestamp_argmax`), returning what transformers' own generate returns for the call (`generate_segments`); every other call is
-    transformers' own generate."""
+    transformers' own generate.  With `BEAMS_ON_HIP` set (`install_whisper(generate=True, beams=True)`) calls whose resolved num_beams is 2 .. 64 take the HIP path too:
+    their `decode_segment` is `beam_decode`, whose layout `generate_segments` strips like the greedy one."""
     raw = dict(kwargs, input_features=input_features, generation_config=generation_config)
     gc = resolved_generation_config(self, generation_config, kwargs)
-    route, why = generate_route(raw, gc, self.config, tuple(input_features.shape) if input_features is not None else None)
+    route, why = generate_route(raw, gc, self.config, tuple(input_features.shape) if input_features is not None else None, beams=BEAMS_ON_HIP)
     if route == "hip" and not next(self.parameters()).is_cuda:
         route, why = "stock", "CPU tensors"
     if route != "hip":
@@ -1300,6 +1453,9 @@ def hip_whisper_generate(self, input_features=None, generation_config=None, **kw
     rules = _token_rules(gc, self.config)
     gc.eos_token_id, gc.pad_token_id = rules["eos_token_id"], rules["pad_token_id"]
     timestamps = _timestamp_rules(gc) if rt else None
+    num_beams = int(getattr(gc, "num_beams", 1) or 1)                                             # > 1 only where `generate_route` let it through: BEAMS_ON_HIP
+    length_penalty = float(gc.length_penalty if getattr(gc, "length_penalty", None) is not None else 1.0)
+    early_stopping = getattr(gc, "early_stopping", False) or False
     cfg, B = self.config, input_features.shape[0]
     enc_eng, dec_eng = _engine_for(self.model.encoder), _decoder_engine_for(self.model.decoder)
     dec_in = g("decoder_input_ids")
@@ -1313,6 +1469,9 @@ def hip_whisper_generate(self, input_features=None, generation_config=None, **kw
 
         def decode_segment(segment_input, prompt, n_new, first):
             st = state if first and state is not None and state["cache"]["Lmax"] >= prompt.shape[1] + n_new else None       # the detection step's encoder output and cache
+            if num_beams > 1:
+                return beam_decode(enc_eng, dec_eng, segment_input, prompt.contiguous(), max_new_tokens=n_new, num_beams=num_beams, length_penalty=length_penalty,
+                                   early_stopping=early_stopping, timestamps=timestamps, state=st, **rules)
             return greedy_decode(enc_eng, dec_eng, segment_input, prompt.contiguous(), max_new_tokens=n_new, timestamps=timestamps, state=st, **rules)
         return generate_segments(gc, cfg, input_features, decode_segment, init_tokens=init_tokens, decoder_input_ids=dec_in, device=self.device)
 
@@ -1325,14 +1484,20 @@ def _replace_forward(cls, ours):
     cls.forward = ours
 
 
-def install_whisper(decoder: bool = False, fused_loss: bool = False, generate: bool = False):
+def install_whisper(decoder: bool = False, fused_loss: bool = False, generate: bool = False, beams: bool = False):
     """Give transformers' `WhisperEncoder` the HIP forward (idempotent).  The original stays reachable as `WhisperEncoder._hfasr_reference_forward` (tests compare against it).
     Opt-in: decoder=True also replaces `WhisperDecoder.forward` (`hip_whisper_decoder_forward`: the teacher-forced training pass on the HIP engine), fused_loss=True
     (implies decoder=True) wraps `WhisperForConditionalGeneration.forward` (`hip_whisper_lm_forward`: the training loss out of the tied head's GEMM, no logits),
     generate=True replaces `WhisperForConditionalGeneration.generate` (`hip_whisper_generate`: short-form greedy decoding on the HIP path; the original stays reachable as
     `WhisperForConditionalGeneration._hfasr_reference_generate`); the other originals stay reachable under `_hfasr_reference_forward`.  With none of them, the decoder and
-    `WhisperForConditionalGeneration` are left untouched."""
+    `WhisperForConditionalGeneration` are left untouched.  generate=True with beams=True also sends beam search (num_beams 2 .. 64) to the HIP path (`beam_decode`): the
+    module-level switch `BEAMS_ON_HIP`, which every call with generate=True sets — to off when `beams` is not given."""
+    global BEAMS_ON_HIP
     from transformers.models.whisper import modeling_whisper as MW
+    if beams and not generate:
+        raise ValueError("install_whisper(beams=True) needs generate=True")
+    if generate:
+        BEAMS_ON_HIP = bool(beams)
     _replace_forward(MW.WhisperEncoder, hip_whisper_encoder_forward)
     if decoder or fused_loss:
         _replace_forward(MW.WhisperDecoder, hip_whisper_decoder_forward)

@@ -596,6 +596,14 @@ int mi_greedy_advance(const int* best, long* ids, long ld_ids, int col, long eos
  * atomics: bit-reproducible. */
 int mi_whisper_timestamp_argmax(const float* logits, long ld, int V, const long* ids, long ld_ids, int begin_index, int cur_len, int no_timestamps_token_id,
                                 int eos_token_id, int max_initial_timestamp_index, int detect_from_logprob, int* best, int B, mi_stream_t stream);
+/* The scores of one beam-search step under Whisper's rules (csrc/whisper_rules.hip), for mi_beam_step / mi_beam_step_wide, which form logit - lse themselves.  transformers'
+ * `_beam_search` applies log_softmax to the RAW logits and the processors to the log-probabilities, so per row (one block): lse[r] = log-sum-exp of the raw row — equal to
+ * mi_row_lse's bit for bit — and, in place, -inf in every column that `suppress` ((V) fp32 of 0 / -inf, nullable: SuppressTokens[AtBegin]LogitsProcessor) or
+ * WhisperTimeStampLogitsProcessor masks for the row's history; every other value is not written.  logits (rows, ld) fp32 WITHOUT a head bias; ids, begin_index, cur_len and
+ * the timestamp parameters as in mi_whisper_timestamp_argmax; no_timestamps_token_id < 0: no timestamp rules (ids may be NULL).  No atomics: bit-reproducible. */
+int mi_whisper_beam_scores(float* logits, long ld, int V, const long* ids, long ld_ids, int begin_index, int cur_len, const float* suppress,
+                           int no_timestamps_token_id, int eos_token_id, int max_initial_timestamp_index, int detect_from_logprob, float* lse, int rows,
+                           mi_stream_t stream);
 int mi_kv_cache_reorder(const void* const* src_k, const void* const* src_v, void* const* dst_k, void* const* dst_v, const long* beam_idx,
                         int L, int BW, int rows, int Lmax, int d, mi_stream_t stream);
 
