@@ -205,6 +205,12 @@ SIGNATURES = {
     "mi_attention_f32": [vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, vp, sz, vp],
     "mi_ebf_f32_workspace_bytes": [C.POINTER(EbfConfig)],
     "mi_ebf_forward_f32": [C.POINTER(EbfConfig), vp, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, vp, vp],
+    # ... for the joint model's decoder (csrc/decoder_f32.hip)
+    "mi_linear_rows_f32_workspace_bytes": [i32, i32, i32],
+    "mi_linear_rows_f32": [vp, i64, vp, i64, vp, i32, vp, i64, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp],
+    "mi_attention_general_f32": [vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i64, i32, i32, f32, i32, vp],
+    "mi_decoder_step_f32_workspace_bytes": [C.POINTER(Gpt2Config), i32, i32],
+    "mi_decoder_step_f32": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
 }
 
 _lib = None
@@ -233,7 +239,7 @@ def lib():
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
                                           "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes",
-                                          "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes") else i32
+                                          "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes", "mi_linear_rows_f32_workspace_bytes", "mi_decoder_step_f32_workspace_bytes") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None
         h.mi_profile_reset.argtypes = []; h.mi_profile_reset.restype = None

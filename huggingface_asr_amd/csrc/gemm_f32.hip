@@ -19,6 +19,8 @@ namespace {
 constexpr int BM = 128, BN = 128, BK = 16, LD = BK + 1;
 
 __device__ __forceinline__ float gelu_exact(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+// GPT-2's gelu_new with the exact tanhf (the decoder MLP of the fp32 token step above 64 rows and of the teacher-forced forward)
+__device__ __forceinline__ float gelu_new_exact(float v) { return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v))); }
 
 struct RowSrc { const float* p; bool ok; int t0, f0; };
 
@@ -165,6 +167,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmF32Args g, cons
                 if (m >= g.M) continue;
                 float v = acc[i][j][r] + bv;
                 if (g.act == 1) v = gelu_exact(v);
+                else if (g.act == 2) v = gelu_new_exact(v);
                 v *= g.alpha;
                 if (g.resid) v = g.resid[(long)m * g.ldr + n] + v;
                 C[(long)m * g.ldc + n] = v;
@@ -177,7 +180,7 @@ bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 int gemm_f32_launch(const GemmF32Args& a, hipStream_t st) {
-    if (!a.A || !a.W || !a.C || a.M < 1 || a.N < 1 || a.K < 1 || a.nz < 1 || a.nh < 1 || a.nz > 65535 || (a.act != 0 && a.act != 1)) return MI_ERR_ARG;
+    if (!a.A || !a.W || !a.C || a.M < 1 || a.N < 1 || a.K < 1 || a.nz < 1 || a.nh < 1 || a.nz > 65535 || a.act < 0 || a.act > 2) return MI_ERR_ARG;
     if (a.resid && a.nz != 1) return MI_ERR_ARG;
     const long gy = (a.N + BN - 1) / BN;
     if (gy > 65535) return MI_ERR_UNSUPPORTED;

@@ -13,7 +13,7 @@ struct GemmF32Args {
     const float* bias;
     const float* resid; long ldr;
     float* C; long ldc, sCb, sCh;
-    float alpha; int act;          // act: 0 none, 1 erf-GELU (exact erff)
+    float alpha; int act;          // act: 0 none, 1 erf-GELU (exact erff), 2 gelu_new (exact tanhf)
     int M, N, K, nz, nh;
     int conv, T1, F1, C1, KW, stride, pt, pf, T2, F2;
 };

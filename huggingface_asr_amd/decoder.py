@@ -9,6 +9,8 @@ Host-side orchestration (one C-ABI call per op) of
   * reference `src/models/ctc_encoder_plus_autoregressive_decoder.py:237-358` (JointAED: encoder CTC loss, enc_to_dec_proj,
     cross mask from the OUTER length formula, shift_tokens_right, loss = w*CTC + (1-w)*CE).
 Eval-mode semantics; the fp32 residual stream / bf16 GEMM operands precision model is the encoder's.
+`precision="fp32"` (engine.py's switch, DESIGN.md §4 'fp32 inference mode'): every packed tensor, the cross K/V tables, the KV cache and the token step stay fp32
+(csrc/decoder_f32.hip) — what the reference's decode recipes, which carry no --bf16, compute.
 """
 from __future__ import annotations
 
@@ -17,8 +19,8 @@ import time
 
 import torch
 
-from . import _lib, ops
-from .engine import EBranchformerEngine
+from . import _lib, ops, ops_f32
+from .engine import PRECISIONS, EBranchformerEngine
 from .packing import _dec_map, _lm_map, decoder_specs, head_fold, head_taps, lm_specs, mapped_fp32, mixes_heads, packed
 
 BF16 = torch.bfloat16
@@ -31,10 +33,22 @@ def _sinusoid_table(n: int, d: int, device) -> torch.Tensor:
     return torch.cat([s.sin(), s.cos()], -1).to(device).contiguous()
 
 
+def _check_precision(who: str, precision: str) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"{who}: precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
+
+
 class GPT2DecoderEngine:
-    def __init__(self, cfg: dict, device="cuda:0"):
+    precision = "bf16"          # (engines that build themselves without this constructor run the default mode)
+
+    def __init__(self, cfg: dict, device="cuda:0", precision="bf16"):
+        self.precision = _check_precision("GPT2DecoderEngine", precision)
         self.cfg = dict(cfg)
         self.device = torch.device(device)
+        if precision == "fp32" and mixes_heads(cfg):
+            raise NotImplementedError("precision='fp32' does not cover the mixing decoder (GPT2LMMultiHeadModelMixing's mixing_mode, average_logits: the folded multi-tap "
+                                      "head): use the default precision='bf16'")
         d, H = cfg["n_embd"], cfg["n_head"]
         if d // H not in (64, 128):
             raise NotImplementedError("HIP decoder attention supports head sizes 64 and 128 (the reference's GPT-2 configs use 64)")
@@ -44,17 +58,19 @@ class GPT2DecoderEngine:
 
     # ------------------------------------------------------------------ weights
     def load_state_dict(self, sd: dict, prefix: str = "decoder."):
-        """every packed parameter of packing.decoder_specs (Conv1D weights transposed to (out, in) there), matrices in bf16, the rest in fp32"""
+        """every packed parameter of packing.decoder_specs (Conv1D weights transposed to (out, in) there), matrices in bf16, the rest in fp32.
+        precision="fp32": the same tensors in the same slots, every one of them fp32; a tied head is `wte` itself."""
         c, dev = self.cfg, self.device
+        f32 = self.precision == "fp32"
         d, L = c["n_embd"], c["n_layer"]
         m = _dec_map(c, False, prefix)
         specs = decoder_specs(c, d, False)
         F = {s.name: t for s, t in packed(specs, m, mapped_fp32(m, sd, dev))}               # fp32 on the device: what the head fold reads
-        P = {s.name: (F[s.name].to(BF16) if s.mat and s.name != "wte" else F[s.name]).contiguous() for s in specs}      # wte stays fp32: the embedding gather reads it
+        P = {s.name: (F[s.name].to(BF16) if s.mat and s.name != "wte" and not f32 else F[s.name]).contiguous() for s in specs}      # wte stays fp32: the embedding gather reads it
         fixed = c.get("pos_emb_fixed", False)
         w = dict(wte=P["wte"], scale=float(d) ** 0.5 if fixed else 1.0, pos=_sinusoid_table(c.get("n_positions", 1024), d, dev) if fixed else P["wpe"],
                  lnf=(P["lnf_g"], P["lnf_b"]), heads=[P[f"head{k}"] for k in range(len(c.get("head_locations") or []))],
-                 lm_head=P["lm_head"] if "lm_head" in P else P["wte"].to(BF16))               # tied: the token embedding is the head
+                 lm_head=P["lm_head"] if "lm_head" in P else (P["wte"] if f32 else P["wte"].to(BF16)))      # tied: the token embedding is the head
         w["layers"] = [dict({n: P[f"h{l}.{n}"] for n in ("wqkv", "bqkv", "wo", "bo", "wq", "bq", "wkv", "bkv", "wco", "bco", "wfc", "bfc", "wpr", "bpr")},
                             **{n: (P[f"h{l}.{n}_g"], P[f"h{l}.{n}_b"]) for n in ("ln1", "lnc", "ln2")}) for l in range(L)]
         self.w = w
@@ -97,14 +113,16 @@ class GPT2DecoderEngine:
 
     # ------------------------------------------------------------------ building blocks
     def cross_kv(self, enc_bf16: torch.Tensor):
-        """Per-layer cross-attention keys/values of the encoder frames: list of (B*T', 2d) bf16 (computed once per utterance)."""
+        """Per-layer cross-attention keys/values of the encoder frames: list of (B*T', 2d) bf16 (computed once per utterance); fp32 in and out with precision="fp32"."""
+        if self.precision == "fp32":
+            return [ops_f32.gemm(enc_bf16, lw["wkv"], lw["bkv"]) for lw in self.w["layers"]]
         return [ops.gemm(enc_bf16, lw["wkv"], lw["bkv"]) for lw in self.w["layers"]]
 
     def _logits(self, hid_bf16, head_w, bias=None):
         V = head_w.shape[0]
         Vp = (V + 7) // 8 * 8
         buf = torch.empty((hid_bf16.shape[0], Vp), device=self.device, dtype=torch.float32)
-        ops.gemm(hid_bf16, head_w, bias, out=buf[:, :V])
+        (ops_f32.gemm if self.precision == "fp32" else ops.gemm)(hid_bf16, head_w, bias, out=buf[:, :V])
         return buf[:, :V]
 
     def _head_input(self, taps: dict, hid):
@@ -154,14 +172,60 @@ class GPT2DecoderEngine:
         ops.gemm(m, lw["wpr"], lw["bpr"], out=x, resid=x, alpha=1.0)
         return x
 
+    def _block_f32(self, l, x, B, U, kv, T_enc, enc_len, self_k=None, self_v=None, past=0, Lmax=0, beams=1):
+        """`_block` with every operand fp32 (ops_f32); `beams`: the B sequences are B / beams utterances whose hypotheses share one cross table `kv` each"""
+        c, lw = self.cfg, self.w["layers"][l]
+        d, H, eps = c["n_embd"], c["n_head"], c.get("layer_norm_epsilon", 1e-5)
+        qkv = ops_f32.gemm(ops_f32.layernorm(x, *lw["ln1"], eps), lw["wqkv"], lw["bqkv"])
+        if self_k is None:
+            ctx = ops_f32.attention_general(qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:], B, U, U, H, causal=True)
+        else:
+            self_k[:, past:past + U] = qkv[:, d:2 * d].reshape(B, U, d)
+            self_v[:, past:past + U] = qkv[:, 2 * d:].reshape(B, U, d)
+            ctx = ops_f32.attention_general(qkv[:, :d], self_k.view(B * Lmax, d), self_v.view(B * Lmax, d), B, U, past + U, H, causal=True, kv_bstride=Lmax * d)
+        ops_f32.gemm(ctx, lw["wo"], lw["bo"], out=x, resid=x)
+        qq = ops_f32.gemm(ops_f32.layernorm(x, *lw["lnc"], eps), lw["wq"], lw["bq"])
+        ctx = ops_f32.attention_general(qq, kv[:, :d], kv[:, d:], B, U, T_enc, H, lengths=enc_len, beams=beams)
+        ops_f32.gemm(ctx, lw["wco"], lw["bco"], out=x, resid=x)
+        m = ops_f32.gemm(ops_f32.layernorm(x, *lw["ln2"], eps), lw["wfc"], lw["bfc"], act="gelu_new")
+        ops_f32.gemm(m, lw["wpr"], lw["bpr"], out=x, resid=x)
+        return x
+
     # ------------------------------------------------------------------ teacher-forced forward
+    def _forward_f32(self, ids, enc, T_enc, enc_len, labels):
+        """`forward` with precision="fp32": LayerNorms, GEMMs and attention of ops_f32, the auxiliary heads of `head_locations` read the fp32 stream"""
+        c, w = self.cfg, self.w
+        B, U = ids.shape
+        L, eps = c["n_layer"], c.get("layer_norm_epsilon", 1e-5)
+        x = ops.embed_tokens(ids, w["wte"], w["pos"], scale=w["scale"])
+        kvs = self.cross_kv(enc)
+        locs = list(c.get("head_locations") or [])
+        taps = {0: x.clone()} if 0 in locs else {}
+        for l in range(L):
+            x = self._block_f32(l, x, B, U, kvs[l], T_enc, enc_len)
+            if (l + 1) in locs and l + 1 < L:
+                taps[l + 1] = x.clone()
+        hid = ops_f32.layernorm(x, *w["lnf"], eps)
+        logits = self._logits(hid, w["lm_head"]).view(B, U, -1)
+        loss = None
+        if labels is not None:
+            weights = list(c.get("head_weights") or [1.0])
+            lsm = c.get("lsm_factor", 0.0)
+            loss = weights[-1] * ops.ce_label_smoothing(logits, labels, shift=1, eps=lsm)
+            for k, loc in enumerate(locs):
+                lg = self._logits(taps[loc] if loc in taps else hid, w["heads"][k]).view(B, U, -1)
+                loss = loss + weights[k] * ops.ce_label_smoothing(lg, labels, shift=1, eps=lsm)
+        return dict(logits=logits, loss=loss)
+
     def forward(self, ids: torch.Tensor, enc_bf16: torch.Tensor, T_enc: int, enc_len, labels=None):
-        """ids (B,U) int64; enc_bf16 (B*T', d) bf16 (already projected to the decoder width); enc_len (B) int32 valid frames
+        """ids (B,U) int64; enc_bf16 (B*T', d) bf16 (already projected to the decoder width; fp32 with precision="fp32"); enc_len (B) int32 valid frames
         or None.  Returns dict(logits (B,U,V) fp32, loss | None) = GPT2LMMultiHeadModel.forward."""
         c, w = self.cfg, self.w
         B, U = ids.shape
         d, L, eps = c["n_embd"], c["n_layer"], c.get("layer_norm_epsilon", 1e-5)
         self.ensure_positions(U)
+        if self.precision == "fp32":
+            return self._forward_f32(ids, enc_bf16, T_enc, enc_len, labels)
         x = ops.embed_tokens(ids, w["wte"], w["pos"], scale=w["scale"])
         kvs = self.cross_kv(enc_bf16)
         locs = list(c.get("head_locations") or [])
@@ -196,13 +260,13 @@ class GPT2DecoderEngine:
 
     # ------------------------------------------------------------------ incremental decoding
     def init_cache(self, B: int, Lmax: int):
-        """KV cache: two sets of (B, Lmax, d) tensors per layer (beam re-ordering copies set A -> set B in one kernel and swaps)."""
+        """KV cache: two sets of (B, Lmax, d) tensors per layer (beam re-ordering copies set A -> set B in one kernel and swaps); fp32 with precision="fp32"."""
         d, L = self.cfg["n_embd"], self.cfg["n_layer"]
         if self.cfg.get("pos_emb_fixed", False):
             self.ensure_positions(Lmax)
         # one allocation and one fill for all 4 L tensors.  Zero, not empty: the MFMA attention kernel stages whole 32-key tiles, and a V row past the last key meets a
         # probability of exactly 0 — which only gives 0 if the row holds finite numbers
-        buf = torch.zeros((4, L, B, Lmax, d), device=self.device, dtype=BF16)
+        buf = torch.zeros((4, L, B, Lmax, d), device=self.device, dtype=torch.float32 if self.precision == "fp32" else BF16)
         cache = dict(k=list(buf[0].unbind(0)), v=list(buf[1].unbind(0)), k2=list(buf[2].unbind(0)), v2=list(buf[3].unbind(0)), past=0, Lmax=Lmax)
         self._cache_tables(cache)
         return cache
@@ -216,6 +280,7 @@ class GPT2DecoderEngine:
         """transformers' `_reorder_cache`: every layer's K and V rows follow their beam (one kernel for all 2L tensors)."""
         L = len(cache["k"])
         B, Lmax, d = cache["k"][0].shape
+        d *= cache["k"][0].element_size() // 2               # the kernel copies rows of `d` 2-byte elements: an fp32 cache is the same copy at twice the width
         beam_idx = beam_idx.to(device=self.device, dtype=torch.long).contiguous()
         _lib.check(_lib.lib().mi_kv_cache_reorder(cache["tk"], cache["tv"], cache["tk2"], cache["tv2"], beam_idx.data_ptr(), L, B, cache["past"], Lmax, d,
                                                   torch.cuda.current_stream().cuda_stream), "mi_kv_cache_reorder")
@@ -227,13 +292,33 @@ class GPT2DecoderEngine:
     def step(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, enc_len, beams: int = 1):
         """ids_new (B, U_new) -> logits (B, V) of the LAST new position; appends to the KV cache.  One C call (mi_gpt2_step).
         `beams` > 1: the B rows are B / beams utterances x `beams` hypotheses that share their utterance's encoder frames — `kvs` are (B / beams * T_enc, 2d) and
-        `enc_len` (B / beams) (mi_decoder_step_beams; one new token per row)."""
+        `enc_len` (B / beams) (mi_decoder_step_beams; one new token per row).
+        precision="fp32": mi_decoder_step_f32 on fp32 caches and tables, which always reads the cross tables as shared by `beams` hypotheses (1: one table per row)."""
         c, w = self.cfg, self.w
         ids_new = ids_new.contiguous()
         B, U = ids_new.shape
         past, Lmax = cache["past"], cache["Lmax"]
         self.ensure_positions(past + U)
         L_ = _lib.lib()
+        if self.precision == "fp32":
+            if beams < 1 or B % beams or kvs[0].shape[0] != B // beams * T_enc or (enc_len is not None and enc_len.numel() != B // beams):
+                raise ValueError(f"step(beams={beams}): {B} rows of {U} new tokens over cross tables of {kvs[0].shape[0]} rows (T_enc = {T_enc})")
+            if kvs[0].dtype != torch.float32 or cache["k"][0].dtype != torch.float32:
+                raise TypeError("precision='fp32': the cross K/V tables and the KV cache must be fp32 (cross_kv / init_cache of this engine)")
+            nbytes = L_.mi_decoder_step_f32_workspace_bytes(C.byref(self._gcfg), B, U)
+            if self._step_ws is None or self._step_ws.numel() < nbytes:
+                self._step_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            if cache.get("kv_id") != id(kvs):
+                cache["tkv"] = (C.c_void_p * len(kvs))(*[t.data_ptr() for t in kvs])
+                cache["kv_id"] = id(kvs)
+            V = self._gcfg.V
+            Vp = (V + 7) // 8 * 8
+            buf = torch.empty((B, Vp), device=self.device, dtype=torch.float32)
+            _lib.check(L_.mi_decoder_step_f32(C.byref(self._gcfg), self._wtable, ids_new.data_ptr(), B, beams, U, past, Lmax, cache["tk"], cache["tv"], cache["tkv"], T_enc,
+                                              enc_len.data_ptr() if enc_len is not None else None, float(w["scale"]), None, self._step_ws.data_ptr(),
+                                              self._step_ws.numel(), buf.data_ptr(), Vp, torch.cuda.current_stream().cuda_stream), "mi_decoder_step_f32")
+            cache["past"] = past + U
+            return buf[:, :V]
         taps = w.get("taps")
         nbytes = L_.mi_decoder_step_taps_workspace_bytes(C.byref(self._gcfg), B, U, len(taps)) if taps else L_.mi_gpt2_step_workspace_bytes(C.byref(self._gcfg), B, U)
         if self._step_ws is None or self._step_ws.numel() < nbytes:
@@ -267,14 +352,21 @@ class GPT2DecoderEngine:
         cache["past"] = past + U
         return buf[:, :V]
 
-    def step_py(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, enc_len):
-        """same step driven op by op from Python (kept as the cross-check of the C driver)"""
+    def step_py(self, ids_new: torch.Tensor, cache, kvs, T_enc: int, enc_len, beams: int = 1):
+        """same step driven op by op from Python (kept as the cross-check of the C driver); precision="fp32": the same operations through ops_f32 (`beams` as in `step`)"""
         c, w = self.cfg, self.w
         B, U = ids_new.shape
         d, L, eps = c["n_embd"], c["n_layer"], c.get("layer_norm_epsilon", 1e-5)
         past, Lmax = cache["past"], cache["Lmax"]
         self.ensure_positions(past + U)
         x = ops.embed_tokens(ids_new, w["wte"], w["pos"], scale=w["scale"], pos_offset=past)
+        if self.precision == "fp32":
+            for l in range(L):
+                x = self._block_f32(l, x, B, U, kvs[l], T_enc, enc_len, cache["k"][l], cache["v"][l], past, Lmax, beams)
+            cache["past"] = past + U
+            return self._logits(ops_f32.layernorm(x.view(B, U, d)[:, -1].contiguous(), *w["lnf"], eps), w["lm_head"])
+        if beams != 1:
+            raise ValueError("step_py(beams > 1) is the fp32 cross-check; the bf16 one reads one cross table per row")
         locs = w.get("taps") or []
         last_of = lambda t: t.view(B, U, d)[:, -1].clone()             # a copy: the blocks update the stream in place
         taps = {0: last_of(x)} if 0 in locs else {}
@@ -305,7 +397,9 @@ class GPT2LMEngine(GPT2DecoderEngine):
     src/decoding/shallow_fussion.py:41-53, which re-runs the LM over the whole prefix for every token).  `GPT2DecoderEngine` without the cross parts: the same pointer
     table with the six cross entries of a layer null, `mi_gpt2_step` called without encoder K/V; cache, beam re-ordering and the position check are inherited."""
 
-    def __init__(self, cfg: dict, device="cuda:0"):
+    def __init__(self, cfg: dict, device="cuda:0", precision="bf16"):
+        if _check_precision("GPT2LMEngine", precision) == "fp32":
+            raise NotImplementedError("precision='fp32' does not cover GPT2LMEngine (shallow fusion, generate(lm=...)): use the default precision='bf16'")
         super().__init__(cfg, device)                      # head size 64 / 128, gelu_new
         d = cfg["n_embd"]
         if cfg.get("n_inner") not in (None, 4 * d):
@@ -379,9 +473,11 @@ def shift_tokens_right(labels: torch.Tensor, pad_id: int, start_id: int) -> torc
 class JointAEDEngine:
     """JointCTCAttentionEncoderDecoder.forward (eval) on the HIP path."""
 
-    def __init__(self, enc_cfg: dict, dec_cfg: dict, joint_cfg: dict, device="cuda:0"):
-        self.enc = EBranchformerEngine(enc_cfg, device)
-        self.dec = GPT2DecoderEngine(dec_cfg, device)
+    def __init__(self, enc_cfg: dict, dec_cfg: dict, joint_cfg: dict, device="cuda:0", precision="bf16"):
+        """precision="fp32": both engines in that mode (what either refuses keeps raising from its constructor), fp32 encoder states, tables, caches and token step"""
+        self.precision = _check_precision("JointAEDEngine", precision)
+        self.enc = EBranchformerEngine(enc_cfg, device, precision=precision)
+        self.dec = GPT2DecoderEngine(dec_cfg, device, precision=precision)
         self.jcfg = dict(joint_cfg)
         self.device = torch.device(device)
         self.proj = None
@@ -390,15 +486,17 @@ class JointAEDEngine:
         self.enc.load_state_dict({k[len("encoder."):]: v for k, v in sd.items() if k.startswith("encoder.")})
         self.dec.load_state_dict(sd, "decoder.")
         if "enc_to_dec_proj.weight" in sd:
-            self.proj = (sd["enc_to_dec_proj.weight"].detach().to(self.device, torch.float32).to(BF16).contiguous(),
+            self.proj = (sd["enc_to_dec_proj.weight"].detach().to(self.device, torch.float32).to(torch.float32 if self.precision == "fp32" else BF16).contiguous(),
                          sd["enc_to_dec_proj.bias"].detach().to(self.device, torch.float32).contiguous())
 
     def encode(self, feats, feat_len):
-        """-> (encoder out dict, encoder states for the decoder (B*T', d_dec) bf16, T', cross-attention key lengths)."""
+        """-> (encoder out dict, encoder states for the decoder (B*T', d_dec) bf16 — fp32 with precision="fp32" —, T', cross-attention key lengths)."""
         out = self.enc.forward(feats, feat_len, want_hidden=True)
         B, T2, d = out["last_hidden"].shape
         hid = out["last_hidden"].reshape(B * T2, d)
-        if self.proj is not None:
+        if self.precision == "fp32":
+            enc_bf = ops_f32.gemm(hid, self.proj[0], self.proj[1]) if self.proj is not None else hid
+        elif self.proj is not None:
             enc_bf = ops.gemm(ops.cast_bf16(hid), self.proj[0], self.proj[1])       # ctc_encoder_plus...:289-293
         else:
             enc_bf = ops.cast_bf16(hid)
@@ -464,6 +562,8 @@ def _check_generate_args(joint, num_beams, max_length, early_stopping, lm=None, 
     """-> the LM engine to use (None when the term is off)"""
     if early_stopping not in _ES_MODE:
         raise ValueError(f"early_stopping must be False, True or 'never', got {early_stopping!r}")
+    if lm is not None and lm_weight > 0 and getattr(joint, "precision", "bf16") == "fp32":
+        raise NotImplementedError("precision='fp32' does not cover shallow fusion (generate(lm=...): GPT2LMEngine is bf16-only): decode without lm, or with precision='bf16'")
     if num_beams < 1 or max_length < 2:
         raise ValueError(f"num_beams >= 1 and max_length >= 2 required, got {num_beams}, {max_length}")
     joint.dec.ensure_positions(max_length - 1)           # the last step feeds position max_length - 2: a learned table too short is refused before decoding starts
@@ -504,8 +604,10 @@ def cross_kv_layout(B: int, W: int, T_enc: int, d: int, n_layer: int, share=None
 
 def _beam_cross_kv(joint, enc_bf, key_len, B, W, T2, share=None):
     """-> (per-layer cross K/V, key lengths, `beams` of the token step) for B utterances x W hypotheses: the arrangement `generate` and `generate_stepwise` both decode on
-    (the same step on the same tables: that is what keeps the two loops bit-identical to each other)"""
+    (the same step on the same tables: that is what keeps the two loops bit-identical to each other).  precision="fp32": always the shared layout, the only one its step has"""
     d = enc_bf.shape[1]
+    if getattr(joint, "precision", "bf16") == "fp32":
+        share = True
     lay = cross_kv_layout(B, W, T2, joint.dec.cfg["n_embd"], joint.dec.cfg["n_layer"], share)
     if lay["beams"] > 1:
         return joint.dec.cross_kv(enc_bf), key_len, lay["beams"]

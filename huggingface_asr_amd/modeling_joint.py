@@ -325,12 +325,19 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
     def freeze_feature_encoder(self):
         self.encoder.freeze_feature_encoder()
 
+    def _precision(self) -> str:
+        """numeric mode of the HIP inference engine, resolved as the CTC model resolves it: `config.hip_precision`, else the environment variable HFASR_PRECISION, else
+        "bf16" ("fp32": decoder.py, engine.py)"""
+        import os
+        return getattr(self.config, "hip_precision", None) or os.environ.get("HFASR_PRECISION") or "bf16"
+
     def _get_engine(self, device) -> JointAEDEngine:
         dc = _dec_cfg_dict(self.decoder.config)           # the decoder that is there NOW: the module may have been replaced after construction (`__setattr__`)
-        if self._engine is None or self._engine.device != torch.device(device) or self._engine.dec.cfg != dc:
+        prec = self._precision()
+        if self._engine is None or self._engine.device != torch.device(device) or self._engine.dec.cfg != dc or self._engine.precision != prec:
             jc = dict(ctc_weight=self.config.ctc_weight, pad_token_id=self.config.pad_token_id,
                       decoder_start_token_id=self.config.decoder_start_token_id)
-            self._engine = JointAEDEngine(cfg_from_hf(self.config.encoder), dc, jc, device)
+            self._engine = JointAEDEngine(cfg_from_hf(self.config.encoder), dc, jc, device, precision=prec)
             self._engine_key = None
         from .autograd_bridge import bridge_generation
         key = (sum(p._version for p in self.parameters()), bridge_generation(self), tuple(p.data_ptr() for p in self.parameters()))
@@ -365,6 +372,8 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
                 past_key_values=None, decoder_inputs_embeds=None, labels=None, use_cache=None, output_attentions=None,
                 output_hidden_states=None, input_values=None, input_features=None, return_dict=None, **kwargs):
         training = self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if training and self._precision() == "fp32":
+            raise NotImplementedError("hip_precision='fp32' is an inference mode: the HIP trainer is bf16-only (call model.eval(), or train with the default precision)")
         if training and isinstance(self.decoder, GPT2LMMultiHeadModelMixing):
             return self._forward_mixing_finetune(self._pick_inputs(inputs, input_values, input_features), attention_mask, labels)
         if labels is None or decoder_input_ids is not None or encoder_outputs is not None or decoder_inputs_embeds is not None:

@@ -1,4 +1,4 @@
-"""Torch-tensor wrappers over the fp32 entries of the C ABI (csrc/gemm_f32.hip, csrc/encoder_f32.hip): the operators of the `precision="fp32"`
+"""Torch-tensor wrappers over the fp32 entries of the C ABI (csrc/gemm_f32.hip, csrc/encoder_f32.hip, csrc/decoder_f32.hip): the operators of the `precision="fp32"`
 inference mode, one by one.  The engine calls the whole-encoder entry (mi_ebf_forward_f32); these exist for the operator tests and for callers who want
 one exact-fp32 piece.  Every tensor is an fp32 device tensor with a contiguous last dimension; there is no CPU path.
 """
@@ -24,7 +24,8 @@ def _rows(t):
 
 
 def gemm(a, w, bias=None, out=None, *, act="none", resid=None, alpha=1.0):
-    """out (M,N) = resid + alpha * act(a (M,K) @ w (N,K)^T + bias) on the f32-input MFMA; act "none" | "gelu" (exact erf); resid may be `out` itself."""
+    """out (M,N) = resid + alpha * act(a (M,K) @ w (N,K)^T + bias) on the f32-input MFMA; act "none" | "gelu" (exact erf) | "gelu_new" (exact tanh); resid may be `out`
+    itself."""
     _rows(a); _rows(w)
     M, K = a.shape
     N = w.shape[0]
@@ -34,7 +35,7 @@ def gemm(a, w, bias=None, out=None, *, act="none", resid=None, alpha=1.0):
         out = torch.empty((M, N), device=a.device, dtype=F32)
     _rows(out)
     rc = _lib.lib().mi_gemm_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias), out.data_ptr(), out.stride(0),
-                                _p(resid), resid.stride(0) if resid is not None else 0, float(alpha), {"none": 0, "gelu": 1}[act], M, N, K, _stream())
+                                _p(resid), resid.stride(0) if resid is not None else 0, float(alpha), {"none": 0, "gelu": 1, "gelu_new": 2}[act], M, N, K, _stream())
     _lib.check(rc, "mi_gemm_f32")
     return out
 
@@ -141,4 +142,45 @@ def attention(q, k, v, B, T, H, *, pos=None, bias_u=None, bias_v=None, lengths=N
                                      _p(bias_u), _p(bias_v), _p(lengths), out.data_ptr(), out.stride(0), B, T, H, hd, 1.0 / math.sqrt(hd), int(bool(causal)),
                                      ws.data_ptr(), nbytes, _stream())
     _lib.check(rc, "mi_attention_f32")
+    return out
+
+
+def linear_rows_workspace_bytes(M, N, K):
+    return int(_lib.lib().mi_linear_rows_f32_workspace_bytes(M, N, K))
+
+
+def linear_rows(x, w, bias=None, out=None, *, act="none", accumulate=False, kcache=None, vcache=None, U=1, past=0):
+    """out (M,N) = act(x (M,K) @ w (N,K)^T + bias), or out += that (`accumulate`: the residual stream), for 1 <= M <= 64 rows with the weights streamed once
+    (mi_linear_rows_f32); act "none" | "gelu_new".  kcache / vcache (B, Lmax, N/3) fp32: columns [N/3, N) of row b*U + u are also appended at row past + u."""
+    _rows(x); _rows(w)
+    M, K = x.shape
+    N = w.shape[0]
+    if w.shape[1] != K:
+        raise ValueError("linear_rows: x (M,K) and w (N,K) disagree on K")
+    if out is None:
+        if accumulate:
+            raise ValueError("linear_rows: accumulate needs `out`")
+        out = torch.empty((M, N), device=x.device, dtype=F32)
+    _rows(out)
+    nbytes = linear_rows_workspace_bytes(M, N, K)
+    ws = torch.empty((max(nbytes, 4),), dtype=torch.uint8, device=x.device)
+    Lmax, dkv = (kcache.shape[1], kcache.shape[2]) if kcache is not None else (0, 0)
+    rc = _lib.lib().mi_linear_rows_f32(x.data_ptr(), x.stride(0), w.data_ptr(), w.stride(0), _p(bias), {"none": 0, "gelu_new": 2}[act], out.data_ptr(), out.stride(0),
+                                       int(bool(accumulate)), _p(kcache), _p(vcache), int(U), int(past), Lmax, dkv, M, N, K, ws.data_ptr(), nbytes, _stream())
+    _lib.check(rc, "mi_linear_rows_f32")
+    return out
+
+
+def attention_general(q, k, v, B, Tq, Tk, H, *, lengths=None, causal=False, out=None, kv_bstride=0, beams=1):
+    """`ops.attention_general` in fp32: q (B*Tq, .) / k, v row views with head h at columns [h*hd, (h+1)*hd) -> context (B*Tq, d) fp32.  Cross-attention (`lengths` =
+    valid keys) and KV-cache steps (causal offset Tk - Tq, `kv_bstride` floats between the batches of a cache).  `beams`: the B batches are B / beams utterances whose
+    hypotheses read ONE K / V table (and one `lengths` entry) each."""
+    _rows(q); _rows(k); _rows(v)
+    d = q.shape[1]
+    hd = d // H
+    if out is None:
+        out = torch.empty((B * Tq, d), device=q.device, dtype=F32)
+    rc = _lib.lib().mi_attention_general_f32(q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), _p(lengths), out.data_ptr(), out.stride(0),
+                                             B, int(beams), Tq, Tk, int(kv_bstride), H, hd, 1.0 / math.sqrt(hd), int(bool(causal)), _stream())
+    _lib.check(rc, "mi_attention_general_f32")
     return out

@@ -297,7 +297,10 @@ class WhisperDecoderEngine(GPT2DecoderEngine):
     # than the run-to-run spread of the same call (tools/whisper_decode_bench.py, DESIGN "Whisper decoding"); every other shape runs form 1
     STREAMING_AT = ((1, 768), (16, 768), (16, 1024))          # measured and lost: (64, 768); every other shape: not measured
 
-    def __init__(self, cfg: dict, device="cuda:0"):
+    def __init__(self, cfg: dict, device="cuda:0", precision="bf16"):
+        from .decoder import _check_precision
+        if _check_precision("WhisperDecoderEngine", precision) == "fp32":
+            raise NotImplementedError("precision='fp32' does not cover the Whisper decoder engine: use the default precision='bf16'")
         d, H = cfg["d_model"], cfg["decoder_attention_heads"]
         if d % H or d // H != 64:
             raise NotImplementedError("the HIP Whisper decoder supports head size 64 (every released checkpoint)")

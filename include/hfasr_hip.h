@@ -722,7 +722,7 @@ int mi_ebf_forward_greedy(const mi_ebf_config* cfg, const void* const* weights, 
 
 /* ---- precision = "fp32" inference mode (csrc/gemm_f32.hip, csrc/encoder_f32.hip): the encoder + CTC head with every operand, activation and weight in fp32 — what the
  * reference's decode recipes (no --bf16) compute.  Opt-in; nothing above changes.  DESIGN.md §4 'fp32 inference mode'. */
-/* C (M,N) = resid + alpha * act(A (M,K) · W (N,K)^T + bias), all fp32, row-major with leading dimensions; act 0 none / 1 erf-GELU (exact erff); bias, resid nullable,
+/* C (M,N) = resid + alpha * act(A (M,K) · W (N,K)^T + bias), all fp32, row-major with leading dimensions; act 0 none / 1 erf-GELU (exact erff) / 2 gelu_new (exact tanhf); bias, resid nullable,
  * resid may alias C.  f32-input MFMA (v_mfma_f32_32x32x2_f32), LDS-tiled; any M, N, K >= 1 (edges zero-filled / guarded).  An element is the k-ordered fmaf chain over
  * its row of A and its row of W: no split-K, no atomics, run-to-run bit-identical. */
 int mi_gemm_f32(const float* A, long lda, const float* W, long ldw, const float* bias, float* C, long ldc, const float* resid, long ldr,
@@ -759,6 +759,36 @@ size_t mi_ebf_f32_workspace_bytes(const mi_ebf_config* cfg);
 int mi_ebf_forward_f32(const mi_ebf_config* cfg, const void* const* weights, const float* feats, const int* feat_lengths,
                        const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
                        float* last_hidden, float* logits, int* inner_len, int* outer_len, mi_stream_t stream);
+
+/* ---- precision = "fp32" for the joint model's decoder (csrc/decoder_f32.hip): the GPT-2 token step with fp32 weights, caches, cross tables and activations.  Opt-in;
+ * nothing above changes (mi_gemm_f32 gains act 2 = gelu_new with the exact tanhf; its other values keep their bits).  DESIGN.md §4 'fp32 inference mode'. */
+/* Rows-streaming fp32 linear, the counterpart of mi_linear_rows: out = act(x W^T + b), or out += that when accumulate (the in-place residual add), for 1 <= M <= 64
+ * rows, any N; x (M, K), W (N, K), out (M, ldo) fp32; x and W 16-B aligned, ldx % 4 == ldw % 4 == 0.  K % 4 != 0 is MI_ERR_UNSUPPORTED, checked before anything else.
+ * act 0 none / 2 gelu_new.  kcache != NULL (N == 3 dkv, M % U == 0): columns [dkv, 2 dkv) / [2 dkv, 3 dkv) of row m = b U + u also go to the fp32 kcache / vcache
+ * (.., Lmax, dkv) at row past + u of sequence b.  W is the 32-row operand of v_mfma_f32_32x32x2_f32: each weight byte is read once per launch.  The launch spreads over N
+ * and, where that leaves fewer blocks than CUs, over K (fp32 partials in workspace, added in slice order by a second launch): no float atomics, bit-reproducible, and a
+ * row's result depends on that row alone, whatever M is.  workspace: mi_linear_rows_f32_workspace_bytes(M, N, K) bytes (0 when the launch is not split over K). */
+size_t mi_linear_rows_f32_workspace_bytes(int M, int N, int K);
+int mi_linear_rows_f32(const float* x, long ldx, const float* W, long ldw, const float* bias, int act, float* out, long ldo, int accumulate,
+                       float* kcache, float* vcache, int U, int past, int Lmax, int dkv, int M, int N, int K, void* workspace, size_t workspace_bytes,
+                       mi_stream_t stream);
+/* fp32 attention of B batches of Tq queries over Tk keys (cross-attention, KV-cache steps): q (B*Tq, >= H*hd), head h at columns [h*hd, (h+1)*hd); k / v rows with strides
+ * ldk / ldv, batch stride kv_bstride floats (0: Tk * ldk, which then needs ldk == ldv).  The B batches are B / beams utterances x `beams` hypotheses that read ONE K / V
+ * table (and one entry of lengths) per utterance: batch b reads table b / beams.  lengths (B / beams) valid keys or NULL; causal: query i sees keys j <= i + Tk - Tq.
+ * Scores, softmax (expf, division by the sum) and P V in fp32; a key outside the valid set contributes exactly 0 and is not read; a row with no key at all is uniform
+ * over all Tk keys (as mi_attention_f32).  hd 64 or 128 and Tk <= 15360 (a row's scores live in LDS), else MI_ERR_UNSUPPORTED.  No atomics: bit-reproducible. */
+int mi_attention_general_f32(const float* q, long ldq, const float* k, long ldk, const float* v, long ldv, const int* lengths, float* out, long ldo,
+                             int B, int beams, int Tq, int Tk, long kv_bstride, int H, int hd, float scale, int causal, mi_stream_t stream);
+/* mi_decoder_step_beams in fp32: the same config struct, pointer-table order (5 globals, 18 per layer) and argument meaning, EVERY slot pointing at fp32 (matrices
+ * (out, in) included; slot 4 may be slot 0 itself: the tied head).  kcache / vcache: L pointers to (B, Lmax, d) fp32; cross_kv: L pointers to (B / beams * T_enc, 2d) fp32,
+ * shared by an utterance's `beams` hypotheses (beams == 1: one table per row); enc_len (B / beams) or NULL.  U > 1 (a prompt) returns the last position's logits.  Up to 64
+ * rows the linears stream their weights (mi_linear_rows_f32), above they run as mi_gemm_f32.  cfg->act must be 0 (gelu_new), step_form is ignored.  Head sizes other than
+ * 64 / 128 are MI_ERR_UNSUPPORTED, checked before any pointer is read.  The workspace (mi_decoder_step_f32_workspace_bytes) needs no initialisation.  Beam
+ * re-ordering of the fp32 caches: mi_kv_cache_reorder, a row copy in units of 2-byte elements, called with d = 2 * cfg->d. */
+size_t mi_decoder_step_f32_workspace_bytes(const mi_gpt2_config* cfg, int B, int U);
+int mi_decoder_step_f32(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
+                        void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
+                        const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
 
 #ifdef __cplusplus
 }
