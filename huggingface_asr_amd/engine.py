@@ -353,6 +353,21 @@ class EBranchformerEngine:
             out["last_hidden"] = hidden
         return out
 
+    def align(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None, labels: torch.Tensor, *, span="valid", slot=0):
+        """CTC forced alignment of `labels` (B, U) int64 (negative entries are padding) to feats (B,T,F): the forward that yields fp32-or-`logits_dtype` logits — with
+        their row log-sum-exp out of the head's epilogue where `head_lse` is on, else (and in precision="fp32") by ops.row_lse — then ops.ctc_align over them.
+        -> ops.ctc_align's dict (path (B,T2) int32, score (B), tgt_len (B), start / end (B,U) int32, token_lp (B,U); frames are encoder output frames, blank = the last
+        class) plus inner_len, outer_len.  span "valid": frames beyond outer_len do not count (the lengths the CTC loss is trained with); "all": every frame does.
+        `slot` and the lanes of a ForwardPipeline as in forward()."""
+        if span not in ("valid", "all"):
+            raise ValueError(f"align: span must be 'valid' or 'all', got {span!r}")
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 2 or labels.shape[0] != feats.shape[0]:
+            raise ValueError(f"align: labels must be ({feats.shape[0]}, U) int64")
+        fwd = self.forward(feats, feat_lengths, want_hidden=False, want_logits=True, slot=slot)
+        out = ops.ctc_align(fwd["logits"], labels.to(self.device), fwd["outer_len"] if span == "valid" else None, blank=self.cfg["vocab_size"], lse=fwd["lse"])
+        out.update(inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
+        return out
+
     def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
         """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
         Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also

@@ -13,7 +13,7 @@ step does not cover raise NotImplementedError rather than silently falling back 
 from __future__ import annotations
 
 import os
-from typing import Optional, Tuple, Union
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch
 from torch import nn
@@ -29,6 +29,16 @@ def _dropout_seed() -> int:
     """dropout-mask seed of the HIP training step: torch's seed (set by HF Trainer's set_seed) offset by the data-parallel rank"""
     rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
     return (torch.initial_seed() + 7919 * rank) & 0xFFFFFFFF
+
+
+class CTCAlignment(NamedTuple):
+    """what `Wav2Vec2EBranchformerForCTC.align` returns (frames are encoder output frames)"""
+    path: torch.Tensor
+    score: torch.Tensor
+    start: torch.Tensor
+    end: torch.Tensor
+    token_lp: torch.Tensor
+    n_tokens: torch.Tensor
 
 
 class _Holder(nn.Module):
@@ -284,6 +294,27 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
         feat_len = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
         out = eng.transcribe(input_values, feat_len, span=span, pad_id=int(pad))
         return out["tokens"], out["n_tokens"]
+
+    def align(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None, span: str = "valid"):
+        """CTC forced alignment on the device (eval mode only): the best frame-level alignment of each transcript in `labels` (B, U) int64, padded with any negative
+        value as the collator pads them (-100), to its utterance.  -> CTCAlignment(path (B, T') int32 = the class of every frame on the best path (blank =
+        config.vocab_size), -1 past the utterance; score (B) fp32 = the path's log-probability; start, end (B, U) int32 = token u occupies frames [start, end), -1 past
+        the transcript; token_lp (B, U) fp32 = the token's summed log-probability over its frames; n_tokens (B) int32).  A transcript that does not fit its utterance
+        (more tokens, counting one extra frame between equal neighbours, than frames) gets score -inf and -1 everywhere.  span as in transcribe().
+        Frames are encoder output frames: one frame is prod(config.conv_stride) feature frames (4 with the two stride-2 convs of the shipped configs); converting to
+        seconds needs the feature extractor's hop, which the model does not know."""
+        if span not in ("valid", "all"):
+            raise ValueError(f"align: span must be 'valid' or 'all', got {span!r}")
+        if self.training:
+            raise RuntimeError("align() is an inference call: put the model in eval mode first (model.eval())")
+        if not input_values.is_cuda:
+            raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): inputs must be on the GPU; there is no CPU fallback")
+        if labels is None or labels.dtype != torch.int64 or labels.dim() != 2 or labels.shape[0] != input_values.shape[0]:
+            raise ValueError(f"align: labels must be ({input_values.shape[0]}, U) int64 (negative entries are padding)")
+        eng = self._get_engine(input_values.device)
+        feat_len = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        out = eng.align(input_values, feat_len, labels.to(input_values.device), span=span)
+        return CTCAlignment(path=out["path"], score=out["score"], start=out["start"], end=out["end"], token_lp=out["token_lp"], n_tokens=out["tgt_len"])
 
     def forward(
         self,

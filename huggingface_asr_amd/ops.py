@@ -611,6 +611,62 @@ def ctc_loss(logits, labels, in_len, *, reduction="mean", zero_infinity=False, l
     return loss[0], nll, tl
 
 
+def _row_lse_3d(logits):
+    """the rows' log-sum-exp of (B, T, V1) logits with contiguous rows and any (batch, row) strides -> (B*T) fp32, without copying them: mi_row_lse's bits"""
+    B, T, V1 = logits.shape
+    if B == 1 or logits.stride(0) == T * logits.stride(1):
+        return row_lse(logits.as_strided((B * T, V1), (logits.stride(1), 1)))
+    return torch.cat([row_lse(logits[b]) for b in range(B)])
+
+
+def ctc_align(logits, labels, in_len=None, *, blank=None, lse=None, return_spans=True):
+    """CTC forced alignment (csrc/ctc_align.hip states the exact semantics): the best path of each transcript through logits (B, T, V1) f32|bf16 (last dim contiguous,
+    any row / batch strides).  labels (B, U) int64: a row's non-negative entries, in order, are its target (negatives are padding wherever they stand); in_len (B) int32:
+    the frames that count (None: all T); blank: None = the last class; lse (B*T) fp32: the rows' log-sum-exp when the caller already holds it (None: ops.row_lse runs first).
+    -> dict(path (B, T) int32 = the class of every counted frame on the best path, then -1; score (B) fp32 = its log-probability; tgt_len (B) int32[; start, end (B, U) int32:
+    token u emits on frames [start, end), then -1; token_lp (B, U) fp32 = the token's summed log-probability over them, then 0]).  Utterances that cannot be aligned (fewer
+    frames than the target needs, a label >= V1 or == blank): score -inf, path / start / end -1, token_lp 0.  One launch, one block per utterance, bit-identical run to run."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, BF16):
+        raise ValueError("ctc_align: logits must be an fp32 or bf16 tensor")
+    if logits.dim() != 3 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.shape[2] < 2:
+        raise ValueError(f"ctc_align: logits must be (B, T, V1) with at least one utterance, one frame and two classes, got {tuple(logits.shape)}")
+    if logits.stride(2) != 1:
+        raise ValueError("ctc_align: the last dimension of logits must be contiguous")
+    B, T, V1 = logits.shape
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 2 or labels.shape[0] != B:
+        raise ValueError(f"ctc_align: labels must be ({B}, U) int64")
+    if in_len is not None and (not isinstance(in_len, torch.Tensor) or in_len.dtype != torch.int32 or in_len.shape != (B,)):
+        raise ValueError(f"ctc_align: in_len must be ({B},) int32")
+    if lse is not None and (not isinstance(lse, torch.Tensor) or lse.dtype != torch.float32 or lse.numel() != B * T):
+        raise ValueError(f"ctc_align: lse must hold {B * T} fp32 values")
+    blank = V1 - 1 if blank is None else int(blank)
+    if not 0 <= blank < V1:
+        raise ValueError(f"ctc_align: blank {blank} outside [0, {V1})")
+    U = labels.shape[1]
+    for t in (logits, labels, in_len, lse):
+        if t is not None:
+            _req(t)
+    dev = logits.device
+    labels = labels.contiguous()
+    in_len = torch.full((B,), T, device=dev, dtype=torch.int32) if in_len is None else in_len.contiguous()
+    lse = _row_lse_3d(logits) if lse is None else lse.contiguous()
+    L = _lib.lib()
+    nbytes = int(L.mi_ctc_align_workspace_bytes(B, T, U))
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8) if nbytes else None
+    path = torch.empty((B, T), device=dev, dtype=torch.int32)
+    score = torch.empty((B,), device=dev, dtype=torch.float32)
+    tl = torch.empty((B,), device=dev, dtype=torch.int32)
+    start, end = (torch.empty((B, U), device=dev, dtype=torch.int32) for _ in range(2)) if return_spans else (None, None)
+    tlp = torch.empty((B, U), device=dev, dtype=torch.float32) if return_spans else None
+    rc = L.mi_ctc_align(logits.data_ptr(), logits.stride(0), logits.stride(1), 0 if logits.dtype == torch.float32 else 1, lse.data_ptr(), T, labels.data_ptr(), U,
+                        in_len.data_ptr(), blank, V1, B, _p(ws), nbytes, path.data_ptr(), score.data_ptr(), tl.data_ptr(), _p(start), _p(end), _p(tlp), _stream())
+    _lib.check(rc, "mi_ctc_align")
+    out = dict(path=path, score=score, tgt_len=tl)
+    if return_spans:
+        out.update(start=start, end=end, token_lp=tlp)
+    return out
+
+
 def embed_tokens(ids, wte, pos, *, scale=1.0, pos_offset=0, U=None):
     """ids (B,U) int64 -> (B*U, d) fp32 = wte[ids]*scale + pos[pos_offset + u]."""
     ids = ids.contiguous()

@@ -274,6 +274,18 @@ int mi_ctc_beam_cut(const void* logits, long ld_row, long ld_batch, int dtype, i
 int mi_ctc_beam_walk(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, long pad_id, int W, int K, int nbest,
                      const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* workspace, size_t workspace_bytes, void* tokens,
                      int tokens_dtype, int* n_tokens, float* scores, int* frames, mi_stream_t stream);
+/* ---- CTC forced alignment (csrc/ctc_align.hip, whose header states the exact semantics): the best (Viterbi) path of a given transcript, one launch, one block per
+ * utterance.  Arguments as mi_ctc_loss_fwd: logits (B, T, V1) fp32 (dtype 0) / bf16 (1) with element strides (ld_b, ld_t), lse (B*T) the rows' log-sum-exp, labels
+ * (B, U) int64 (negative entries are padding wherever they stand), in_len (B) int32 clamped to [0, T].  Out: path (B, T) int32 = the class of every frame t < n_b on
+ * the best path, then -1; score (B) fp32 = that path's log-probability; tgt_len (B) int32; start / end (B, U) int32 = token u emits on frames [start, end), then -1;
+ * token_lp (B, U) fp32 = the sum of the token's log-probabilities over those frames, then 0 (the last three nullable as a group).  Infeasible utterances (too few
+ * frames, a label >= V1 or == blank, a best score of -inf): score -inf, path / start / end -1, token_lp 0.  workspace: mi_ctc_align_workspace_bytes(B, T, U) bytes
+ * (0 where the backpointers fit in LDS: workspace may then be null), 16-B aligned, contents irrelevant before and after.  No atomics: bit-identical run to run.
+ * MI_ERR_ARG before any launch: V1 < 2, blank outside [0, V1), T < 1, U < 0, B < 1, a bad dtype, a workspace too small or misaligned.  MI_ERR_UNSUPPORTED: U > 1023
+ * or T > 2^20. */
+size_t mi_ctc_align_workspace_bytes(int B, int T, int U);
+int mi_ctc_align(const void* logits, long ld_b, long ld_t, int dtype, const float* lse, int T, const long* labels, int U, const int* in_len, int blank, int V1, int B,
+                 void* workspace, size_t workspace_bytes, int* path, float* score, int* tgt_len, int* start, int* end, float* token_lp, mi_stream_t stream);
 /* the CTC head without its logits: best[m] = argmax_n (A W^T + b)[m][n] out of the 256 x 256 GEMM's epilogue, which leaves one (max, index) pair per row and 64 columns
  * in `workspace` (mi_gemm_argmax_workspace_floats(M, N) floats) and stores no C; a small second launch folds a row's pairs.  Equals mi_row_argmax over the fp32 output of
  * mi_gemm_bf16 on the same operands.  MI_ERR_UNSUPPORTED outside that kernel's shapes (K % 64, K >= 128, 16-B aligned operands): the caller runs mi_gemm_bf16 into a
