@@ -871,6 +871,8 @@ class TnBatch:
 def gemm_tn_(dw, dy, x, n_store=None, db=None, variant=0, defer=None):
     """dw (n_store, K) f32 += dy[:, :N]^T · x   (dy (M,N) bf16, x (M,K) bf16 row views; contraction over rows, no transposes).
     db (n_store) f32: the bias gradient db += column sums of dy, computed from the same LDS tiles.
+    variant 0 at M >= 32768 with N, K >= 256 (the CTC-head and second-Conv2d gradients at the recipes' batch sizes) leaves the 128 x 128 tile for the 256 x 256
+    tile split over M (gemm_tn.hip `tn_big` / gemm_tn_big_kernel).
     defer: a TnBatch — the product is recorded and runs with the batch's next flush()."""
     M, N = dy.shape
     K = x.shape[1]
