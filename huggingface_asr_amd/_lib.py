@@ -213,6 +213,10 @@ SIGNATURES = {
     "mi_attention_general_f32": [vp, i64, vp, i64, vp, i64, vp, vp, i64, i32, i32, i32, i32, i64, i32, i32, f32, i32, vp],
     "mi_decoder_step_f32_workspace_bytes": [C.POINTER(Gpt2Config), i32, i32],
     "mi_decoder_step_f32": [C.POINTER(Gpt2Config), vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, f32, vp, vp, sz, vp, i64, vp],
+    # two-pass joint decoding (csrc/rescore.hip)
+    "mi_rescore_pack": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp],
+    "mi_rows_nll_f32": [vp, i64, vp, vp, i32, vp, i32, vp],
+    "mi_rescore_select": [vp, vp, vp, vp, f32, f32, i32, i32, i32, i32, vp, i32, i32, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp],
 }
 
 _lib = None

@@ -146,9 +146,10 @@ class GPT2DecoderEngine:
             out.copy_(sum(m[h] * per_head[h] for h in range(len(per_head))))
         return out
 
-    def _block(self, l, x, B, U, kv, T_enc, enc_len, self_k=None, self_v=None, past=0, Lmax=0):
+    def _block(self, l, x, B, U, kv, T_enc, enc_len, self_k=None, self_v=None, past=0, Lmax=0, beams=1):
         """One GPT-2 block on the fp32 stream x (B*U, d).  With a KV cache (self_k/self_v (B, Lmax, d)) U new tokens are
-        appended at position `past` and attend to past+U keys."""
+        appended at position `past` and attend to past+U keys.  `beams` (teacher-forced, no cache): the B sequences are B / beams utterances whose hypotheses share
+        one cross table `kv` (B / beams * T_enc rows) each — cross-attention runs as B / beams batches of beams * U queries (it is not causal: the same kernel)."""
         c, lw = self.cfg, self.w["layers"][l]
         d, H, eps = c["n_embd"], c["n_head"], c.get("layer_norm_epsilon", 1e-5)
         M = x.shape[0]
@@ -165,7 +166,7 @@ class GPT2DecoderEngine:
         ops.gemm(ctx, lw["wo"], lw["bo"], out=x, resid=x, alpha=1.0)
         ops.layernorm_chain(x, lna=lw["lnc"], eps2=eps, outa=a)
         qq = ops.gemm(a, lw["wq"], lw["bq"])
-        ctx = ops.attention_general(qq, kv[:, :d], kv[:, d:], B, U, T_enc, H, lengths=enc_len)
+        ctx = ops.attention_general(qq, kv[:, :d], kv[:, d:], B // beams, beams * U, T_enc, H, lengths=enc_len)
         ops.gemm(ctx, lw["wco"], lw["bco"], out=x, resid=x, alpha=1.0)
         ops.layernorm_chain(x, lna=lw["ln2"], eps2=eps, outa=a)
         m = ops.gemm(a, lw["wfc"], lw["bfc"], act="gelu_new")
@@ -257,6 +258,53 @@ class GPT2DecoderEngine:
                 lg = self._logits(hb, w["heads"][k]).view(B, U, -1)
                 loss = loss + weights[k] * ops.ce_label_smoothing(lg, labels, shift=1, eps=c.get("lsm_factor", 0.0))
         return dict(logits=logits, loss=loss)
+
+    # ------------------------------------------------------------------ teacher-forced scoring of given hypotheses (two-pass decoding)
+    NLL_SCRATCH_BYTES = 64 << 20          # precision="fp32": the head's logits go through a scratch of at most this size, in row chunks
+
+    def token_nll(self, ids: torch.Tensor, labels: torch.Tensor, enc, T_enc: int, enc_len, hyps_per_utt: int = 1):
+        """Per-position negative log-likelihood of given hypotheses under the DECODING head: ids, labels (rows, U) int64 (`ops.rescore_pack`: labels[r, u] is the token
+        that follows ids[r, :u + 1], negative = ignored), rows = B * hyps_per_utt with an utterance's hypotheses adjacent; enc (B*T', d) the utterance's encoder states
+        (bf16; fp32 with precision="fp32"), enc_len (B) or None.  -> nll (rows * U) fp32 = lse - logit[label], exactly 0 on ignored positions.
+        The blocks of `forward()`, laid out so that an utterance's cross K / V are computed and read once: self-attention over rows causal batches of U queries,
+        cross-attention over B batches of hyps_per_utt * U queries.  Head: `lm_head`, or the folded multi-tap head of the mixing / average_logits decoders — what
+        `step()` decodes with.  bf16: ops.gemm_ce, no (rows * U, V) logits are written; fp32: ops_f32.gemm into a bounded scratch, ops.row_lse, ops.rows_nll."""
+        c, w = self.cfg, self.w
+        rows, U = ids.shape
+        N = int(hyps_per_utt)
+        if labels.shape != ids.shape or N < 1 or rows % N or enc.shape[0] != rows // N * T_enc or (enc_len is not None and enc_len.numel() != rows // N):
+            raise ValueError(f"token_nll: {tuple(ids.shape)} ids, {tuple(labels.shape)} labels, {N} hypotheses per utterance over {enc.shape[0]} encoder rows (T_enc = {T_enc})")
+        d, L, eps = c["n_embd"], c["n_layer"], c.get("layer_norm_epsilon", 1e-5)
+        self.ensure_positions(U)
+        flat = labels.reshape(-1)
+        x = ops.embed_tokens(ids, w["wte"], w["pos"], scale=w["scale"])
+        kvs = self.cross_kv(enc)
+        if self.precision == "fp32":
+            for l in range(L):
+                x = self._block_f32(l, x, rows, U, kvs[l], T_enc, enc_len, beams=N)
+            hid = ops_f32.layernorm(x, *w["lnf"], eps)
+            V = w["lm_head"].shape[0]
+            Vp = (V + 7) // 8 * 8
+            M = rows * U
+            chunk = max(1, min(M, self.NLL_SCRATCH_BYTES // (4 * Vp)))
+            buf = torch.empty((chunk, Vp), device=self.device, dtype=torch.float32)
+            out = []
+            for lo in range(0, M, chunk):
+                n = min(chunk, M - lo)
+                lg = ops_f32.gemm(hid[lo:lo + n], w["lm_head"], out=buf[:n, :V])
+                out.append(ops.rows_nll(lg, ops.row_lse(lg), flat[lo:lo + n]))
+            return out[0] if len(out) == 1 else torch.cat(out)
+        locs = w.get("taps") or []
+        taps = {0: x.clone()} if 0 in locs else {}
+        for l in range(L):
+            x = self._block(l, x, rows, U, kvs[l], T_enc, enc_len, beams=N)
+            if (l + 1) in locs and l + 1 < L:
+                taps[l + 1] = x.clone()
+        hid = torch.empty((rows * U, d), device=self.device, dtype=BF16)
+        ops.layernorm_chain(x, lna=w["lnf"], eps2=eps, outa=hid)
+        if locs:
+            return ops.gemm_ce(self._head_input(taps, hid), w["head_fold"], flat, bias=w["head_bias"])[2]
+        return ops.gemm_ce(hid, w["lm_head"], flat)[2]
 
     # ------------------------------------------------------------------ incremental decoding
     def init_cache(self, B: int, Lmax: int):
@@ -503,6 +551,14 @@ class JointAEDEngine:
         # cross mask uses the OUTER (un-padded) length formula, quirk 8' (:296-301); no attention_mask -> all frames
         key_len = torch.clamp(out["outer_len"], max=T2) if feat_len is not None else None
         return out, enc_bf, T2, key_len
+
+    def transcribe(self, *args, **kwargs):
+        """the joint model's CTC head decoded on its own: `EBranchformerEngine.transcribe` of the encoder engine (greedy, or prefix beam search with `beams=`)"""
+        return self.enc.transcribe(*args, **kwargs)
+
+    def align(self, *args, **kwargs):
+        """CTC forced alignment with the joint model's CTC head: `EBranchformerEngine.align` of the encoder engine"""
+        return self.enc.align(*args, **kwargs)
 
     def forward(self, feats, feat_len, labels):
         c = self.jcfg
@@ -855,3 +911,167 @@ def generate_stepwise(joint: "JointAEDEngine", feats, feat_len, *, num_beams=1, 
         if lm is not None:
             lm.reorder_cache(lm_cache, beam_idx)
     return [dict(tokens=kept[b][0][1], score=float(kept[b][0][0]), hypotheses=[(float(s), t) for s, t in kept[b]]) for b in range(B)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Two-pass joint decoding ("attention rescoring"; DESIGN.md §4 'Two-pass decoding'): the CTC head's n-best (ops.ctc_beam_decode), ONE teacher-forced decoder pass over
+# all hypotheses of the batch (GPT2DecoderEngine.token_nll) and a ranking by the objective `generate` maximises,
+#     score(h) = (w log p_ctc(h) + (1 - w) sum_u log p_att(h_u | h_<u, x)) / (|h| + 1) ** length_penalty        (the sum over the tokens and the closing EOS)
+# (csrc/rescore.hip).  At EOS `generate`'s prefix scorer holds the full-sequence CTC probability, and a hypothesis of |h| tokens closes with the denominator
+# `_step_denoms(|h| + 1, ...)`: a hypothesis gets here the score `generate` would give it, up to rounding — and up to the CTC term's source: the beam search's score is
+# the mass of the alignments it kept (at most the exact probability, ops.ctc_loss's, which `score` uses), and its blank is the CTC head's last class (`generate` takes
+# `pad_token_id`, the same class in every recipe).  No counterpart in the reference.
+RESCORE_MAXN = 64                          # csrc/rescore.hip RS_MAXN, csrc/ctc_beam.hip's beam limit
+
+
+def _check_rescore_args(joint, feats, *, num_beams, nbest, ctc_weight, max_length, num_return, who):
+    """every refusal of `rescore` / `score`, on the host, before the device is touched; -> (nbest, num_return)"""
+    for name, v in (("num_beams", num_beams), ("nbest", nbest), ("num_return", num_return), ("max_length", max_length)):
+        if v is not None and (not isinstance(v, int) or isinstance(v, bool)):
+            raise ValueError(f"{who}: {name} must be an int, got {v!r}")
+    if not 1 <= num_beams <= RESCORE_MAXN:
+        raise ValueError(f"{who}: num_beams must be in 1..{RESCORE_MAXN}, got {num_beams}")
+    nbest = num_beams if nbest is None else nbest
+    if not 1 <= nbest <= num_beams:
+        raise ValueError(f"{who}: nbest must be in 1..num_beams, got {nbest} with {num_beams} beams")
+    if not 0.0 <= float(ctc_weight) <= 1.0:                # (a NaN fails both comparisons)
+        raise ValueError(f"{who}: ctc_weight must be in [0, 1], got {ctc_weight}")
+    if max_length is None or max_length < 2:
+        raise ValueError(f"{who}: max_length >= 2 required, got {max_length}")
+    num_return = nbest if num_return is None else num_return
+    if not 1 <= num_return <= nbest:
+        raise ValueError(f"{who}: num_return must be in 1..nbest, got {num_return} with nbest = {nbest}")
+    if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
+        raise RuntimeError(f"{who}: inputs must be on the GPU; there is no CPU fallback")
+    V, V1 = joint.dec.w["lm_head"].shape[0], joint.enc.cfg["vocab_size"] + 1
+    if V1 != V:
+        raise ValueError(f"CTC head has {V1} classes, the decoder {V}: joint decoding needs one vocabulary")
+    return nbest, num_return
+
+
+def _length_denoms(U, length_penalty):
+    """denom[l] = fp32(l ** length_penalty), l = 0..U: `_step_denoms`' closing denominator of a hypothesis of l generated tokens (the closing EOS included)"""
+    import numpy as np
+    return [float(np.float32(float(l) ** float(length_penalty))) for l in range(U + 1)]
+
+
+def ctc_term(logits, lens, hyps, lse=None):
+    """log p_ctc of GIVEN hypotheses: logits (B, T, V + 1) the CTC head's (blank = the last class), lens (B) int32 the frames that count, hyps (B, N, Tt) int64 with
+    negative entries as padding -> (B, N) fp32 = -ops.ctc_loss(reduction="none") per hypothesis; an infeasible one (an infinite loss; a token that is no CTC class): -inf."""
+    B, N, Tt = hyps.shape
+    V1 = logits.shape[2]
+    if lse is None:
+        lse = ops._row_lse_3d(logits) if logits.stride(2) == 1 else None
+    bad = (hyps >= V1 - 1).any(-1)
+    lab = hyps.clamp(max=V1 - 2)
+    cols = []
+    for n in range(N):
+        _, nll, _ = ops.ctc_loss(logits, lab[:, n].contiguous(), lens, reduction="none", zero_infinity=False, lse=lse)
+        cols.append(nll)
+    out = -torch.stack(cols, 1)
+    return torch.where(bad | ~torch.isfinite(out), torch.full_like(out, float("-inf")), out).contiguous()
+
+
+def _rescore_pass(joint, enc_bf, T2, key_len, nb_tokens, nb_n, nb_ctc, nb_frames, *, K, ctc_weight, length_penalty, max_length, eos, pad, start, trace, marks):
+    """pack -> token_nll -> select -> the per-utterance dictionaries (shared by `rescore` and `score`)"""
+    B, N, _ = nb_tokens.shape
+    V = joint.dec.w["lm_head"].shape[0]
+    longest = int(nb_n.max())                              # the one device -> host copy before the results: it sizes the pass
+    U = max(1, min(longest + 1, max_length - 1))
+    joint.dec.ensure_positions(U)
+    pk = ops.rescore_pack(nb_tokens, nb_n, nb_ctc, vocab=V, U=U, start_id=start, eos_id=eos, pad_id=pad)
+    nll = joint.dec.token_nll(pk["ids"], pk["labels"], enc_bf, T2, key_len, N)
+    marks("decoder_pass")
+    denom = torch.tensor(_length_denoms(U, length_penalty), dtype=torch.float32).to(joint.device)
+    w_ctc, w_att = float(ctc_weight), float(1 - ctc_weight)            # `generate`'s two weights, as it forms them
+    sel = ops.rescore_select(nll, pk["len"], nb_ctc, denom, nb_tokens, w_ctc=w_ctc, w_att=w_att, K=K, eos_id=eos, pad_id=pad, frames=nb_frames)
+    marks("select")
+    if trace is not None:
+        trace.update(tokens=nb_tokens, n_tokens=nb_n, ctc=nb_ctc, frames=nb_frames, ids=pk["ids"], labels=pk["labels"], len=pk["len"], nll=nll, U=U, denom=denom,
+                     w_ctc=w_ctc, w_att=w_att, select=sel)
+    c = {k: v.cpu() for k, v in sel.items()}               # the first copy synchronises with everything enqueued
+    out = []
+    for b in range(B):
+        hyps, tlp, frs = [], [], []
+        for k in range(K):
+            n = int(c["n_tokens"][b, k])
+            hyps.append((float(c["total"][b, k]), [start] + c["tokens"][b, k, :n + 1].tolist()))
+            tlp.append(c["token_lp"][b, k, :n + 1].tolist())
+            frs.append(c["frames"][b, k, :n].tolist() if "frames" in c else None)
+        out.append(dict(tokens=hyps[0][1], score=hyps[0][0], hypotheses=hyps, ctc_score=c["ctc"][b].tolist(), att_score=c["att"][b].tolist(), token_logprobs=tlp,
+                        frames=frs, order=c["order"][b].tolist()))
+    return out
+
+
+def _stage_marks(stats):
+    """-> (mark(name), finish()): device-side time per stage into `stats` (events on the current stream; nothing is recorded without `stats`)"""
+    if stats is None:
+        return (lambda name: None), (lambda: None)
+    evs = [("start", torch.cuda.Event(enable_timing=True))]
+    evs[0][1].record()
+
+    def mark(name):
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        evs.append((name, e))
+
+    def finish():
+        torch.cuda.current_stream().synchronize()
+        for (_, a), (name, b) in zip(evs, evs[1:]):
+            stats[name + "_ms"] = a.elapsed_time(b)
+    return mark, finish
+
+
+def rescore(joint: "JointAEDEngine", feats, feat_len, *, num_beams, nbest=None, token_topk=None, ctc_weight=0.3, length_penalty=1.0, max_length=64, num_return=None,
+            eos_token_id, pad_token_id=None, start_token_id=None, stats=None, trace=None):
+    """Two-pass joint decoding: `joint.encode`, the CTC prefix beam search over the encoder logits (`num_beams` hypotheses, the `nbest` best kept; lengths =
+    outer_len.clamp(max=T'), what `generate` gives its prefix scorer), one teacher-forced decoder pass over all B * nbest hypotheses, ranking by the joint objective.
+    U = min(longest hypothesis + 1, max_length - 1) positions; a hypothesis that does not fit is dropped (ops.rescore_pack).  Returns per utterance what `generate`
+    returns — dict(tokens = [start, ..., eos], score, hypotheses = the `num_return` (default nbest) best (score, tokens), best first) — plus, aligned with `hypotheses`,
+    ctc_score, att_score, token_logprobs (per token and the closing EOS), frames (the CTC search's frame per token) and order (index into the CTC n-best).  Entries past
+    the hypotheses that exist: [start, eos] with score -inf (an utterance with none yields that as its result).  One device -> host copy (the longest hypothesis) before
+    the results are read.  `stats` (a dict) receives the device time per stage in ms (encoder, ctc_beam, decoder_pass, select); `trace` (a dict) the device tensors of
+    the pass (the n-best, the packed operands, nll, the select's outputs)."""
+    nbest, num_return = _check_rescore_args(joint, feats, num_beams=num_beams, nbest=nbest, ctc_weight=ctc_weight, max_length=max_length, num_return=num_return,
+                                            who="rescore")
+    c = joint.jcfg
+    pad = c["pad_token_id"] if pad_token_id is None else pad_token_id
+    start = c["decoder_start_token_id"] if start_token_id is None else start_token_id
+    mark, finish = _stage_marks(stats)
+    enc_out, enc_bf, T2, key_len = joint.encode(feats, feat_len)
+    mark("encoder")
+    lens = enc_out["outer_len"].clamp(max=T2)
+    nb = ops.ctc_beam_decode(enc_out["logits"], joint.enc.cfg["vocab_size"], pad, lens, beams=num_beams, token_topk=token_topk, nbest=nbest, return_frames=True)
+    mark("ctc_beam")
+    out = _rescore_pass(joint, enc_bf, T2, key_len, nb["tokens"], nb["n_tokens"], nb["scores"], nb["frames"], K=num_return, ctc_weight=ctc_weight,
+                        length_penalty=length_penalty, max_length=max_length, eos=eos_token_id, pad=pad, start=start, trace=trace, marks=mark)
+    finish()
+    return out
+
+
+def score(joint: "JointAEDEngine", feats, feat_len, hyps, *, ctc_weight=0.3, length_penalty=1.0, max_length=64, eos_token_id, pad_token_id=None, start_token_id=None,
+          stats=None, trace=None):
+    """The joint objective of GIVEN hypotheses: hyps (B, N, Tt) int64 on the device, N <= 64, a hypothesis' tokens first (no start / EOS), then negative entries as
+    padding.  The CTC term is -ops.ctc_loss(reduction="none") (the exact full-sequence log-probability; infeasible: -inf), the decoder pass and the ranking are
+    `rescore`'s with every hypothesis returned (K = N).  Returns `rescore`'s dictionaries (`order` indexes `hyps`; `frames` entries are None)."""
+    if not isinstance(hyps, torch.Tensor) or hyps.dtype != torch.int64 or hyps.dim() != 3 or hyps.shape[0] != feats.shape[0] or hyps.shape[2] < 1:
+        raise ValueError(f"score: hyps must be ({feats.shape[0]}, N, Tt) int64")
+    N = int(hyps.shape[1])
+    _check_rescore_args(joint, feats, num_beams=N, nbest=N, ctc_weight=ctc_weight, max_length=max_length, num_return=N, who="score")
+    if not hyps.is_cuda:
+        raise RuntimeError("score: hyps must be on the GPU; there is no CPU fallback")
+    c = joint.jcfg
+    pad = c["pad_token_id"] if pad_token_id is None else pad_token_id
+    start = c["decoder_start_token_id"] if start_token_id is None else start_token_id
+    hyps = hyps.contiguous()
+    mark, finish = _stage_marks(stats)
+    enc_out, enc_bf, T2, key_len = joint.encode(feats, feat_len)
+    mark("encoder")
+    lens = enc_out["outer_len"].clamp(max=T2)
+    ctc = ctc_term(enc_out["logits"], lens, hyps, enc_out.get("lse"))
+    mark("ctc_loss")
+    n_tok = (hyps >= 0).sum(-1).to(torch.int32)
+    out = _rescore_pass(joint, enc_bf, T2, key_len, hyps, n_tok, ctc, None, K=N, ctc_weight=ctc_weight, length_penalty=length_penalty, max_length=max_length,
+                        eos=eos_token_id, pad=pad, start=start, trace=trace, marks=mark)
+    finish()
+    return out

@@ -18,7 +18,7 @@ from transformers.modeling_outputs import Seq2SeqLMOutput
 from transformers.models.speech_encoder_decoder.configuration_speech_encoder_decoder import SpeechEncoderDecoderConfig
 
 from .configuration_ebranchformer import Wav2Vec2EBranchformerConfig
-from .decoder import GPT2LMEngine, JointAEDEngine, check_lm_args, generate as _generate, lm_cfg_dict, lm_engine_for
+from .decoder import GPT2LMEngine, JointAEDEngine, check_lm_args, generate as _generate, lm_cfg_dict, lm_engine_for, rescore as _rescore, score as _score
 from .engine import cfg_from_hf
 from .modeling_ebranchformer import _dropout_seed, Wav2Vec2EBranchformerForCTC, _Holder
 
@@ -485,7 +485,9 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
         As in the reference, the CTC processor's parameters come from the MODEL's `generation_config` (:385-396) while the passed configuration only gates it (:382).
         Shallow fusion (:398-403): `lm_weight` > 0 in the PASSED configuration (or as a keyword argument) adds `lm_weight * log_softmax(lm_model logits)` behind the CTC mix;
         `lm_model` is a transformers `GPT2LMHeadModel` in eval mode, run as a KV-cached HIP token step beside the decoder's (decoder.GPT2LMEngine).
-        Every other option that would change the decoding raises instead of being ignored."""
+        Every other option that would change the decoding raises instead of being ignored.
+        Opt-in: with the environment variable HFASR_JOINT_RESCORE=1 a validated request with 1 < num_beams <= 64, no LM term and no EOS-space trick is decoded by the
+        two-pass route (`decoder.rescore`, DESIGN.md §4 'Two-pass decoding') and returned in the same layouts; unset, no call changes route."""
         import copy
 
         from transformers.generation.utils import GenerateBeamEncoderDecoderOutput, GenerateEncoderDecoderOutput
@@ -581,8 +583,14 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
         eng = self._get_engine(inputs.device)
         fl = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
         lm = lm_engine_for(lm_model, inputs.device) if lm_model is not None else None
-        hyps = _generate(eng, inputs, fl, num_beams=W, max_length=max_length, length_penalty=lp, early_stopping=es, eos_token_id=eos, pad_token_id=pad,
-                         start_token_id=start, lm=lm, lm_weight=lm_w, **ctc)
+        import os
+        if os.environ.get("HFASR_JOINT_RESCORE") == "1" and 1 < W <= 64 and lm is None and not ctc["apply_eos_space_trick"]:
+            # opt-in two-pass route (decoder.rescore): the CTC head's W-best rescored by one teacher-forced decoder pass, ranked by the objective the beam search maximises
+            hyps = _rescore(eng, inputs, fl, num_beams=W, ctc_weight=ctc["ctc_weight"], length_penalty=lp, max_length=max_length, num_return=nret, eos_token_id=eos,
+                            pad_token_id=pad, start_token_id=start)
+        else:
+            hyps = _generate(eng, inputs, fl, num_beams=W, max_length=max_length, length_penalty=lp, early_stopping=es, eos_token_id=eos, pad_token_id=pad,
+                             start_token_id=start, lm=lm, lm_weight=lm_w, **ctc)
         rows = [h["hypotheses"][k] for h in hyps for k in range(nret)]
         L = max(len(t) for _, t in rows)                  # (greedy: transformers runs every row until all have stopped and closed rows take pad tokens — the same layout)
         seq = torch.full((len(rows), L), pad, dtype=torch.long)
@@ -595,3 +603,95 @@ class JointCTCAttentionEncoderDecoder(PreTrainedModel):
             return GenerateEncoderDecoderOutput(sequences=seq)
         scores = torch.tensor([s for s, _ in rows], dtype=torch.float32, device=inputs.device) if getattr(g, "output_scores", False) else None
         return GenerateBeamEncoderDecoderOutput(sequences=seq, sequences_scores=scores)
+
+    # ------------------------------------------------------------------ two-pass decoding (decoder.rescore / decoder.score; DESIGN.md §4 'Two-pass decoding')
+    def _two_pass_options(self, max_length, length_penalty, ctc_weight):
+        """(max_length, length_penalty, ctc_weight, eos, pad, start): the arguments, else the model's generation configuration, else `generate`'s defaults"""
+        g = self.generation_config
+        pick = lambda v, name, default: v if v is not None else (getattr(g, name, None) if getattr(g, name, None) is not None else default)
+        eos = getattr(g, "eos_token_id", None)
+        if isinstance(eos, (list, tuple)):
+            if len(eos) != 1:
+                raise NotImplementedError("JointCTCAttentionEncoderDecoder (HIP): one eos_token_id")
+            eos = eos[0]
+        eos = self.config.decoder.eos_token_id if eos is None else int(eos)
+        pad = getattr(g, "pad_token_id", None)
+        pad = self.config.pad_token_id if pad is None else int(pad)
+        start = getattr(g, "decoder_start_token_id", None)
+        start = self.config.decoder_start_token_id if start is None else int(start)
+        return int(pick(max_length, "max_length", 20)), float(pick(length_penalty, "length_penalty", 1.0)), float(pick(ctc_weight, "ctc_weight", 0.0)), eos, pad, start
+
+    @staticmethod
+    def _two_pass_output(hyps, k, pad, device, return_dict):
+        rows = [(u, j) for u in range(len(hyps)) for j in range(k)]
+        toks = [hyps[u]["hypotheses"][j][1] for u, j in rows]
+        L = max(len(t) for t in toks)
+        seq = torch.full((len(rows), L), pad, dtype=torch.long)
+        for i, t in enumerate(toks):
+            seq[i, : len(t)] = torch.tensor(t)
+        seq = seq.to(device)
+        if not return_dict:
+            return seq
+        f32 = lambda key: torch.tensor([hyps[u][key][j] for u, j in rows], dtype=torch.float32, device=device)
+        tlp = torch.zeros((len(rows), L - 1), dtype=torch.float32)             # token_logprobs[i, u]: the log-probability of sequences[i, u + 1]
+        for i, (u, j) in enumerate(rows):
+            v = hyps[u]["token_logprobs"][j]
+            tlp[i, : len(v)] = torch.tensor(v)
+        return dict(sequences=seq, sequences_scores=torch.tensor([hyps[u]["hypotheses"][j][0] for u, j in rows], dtype=torch.float32, device=device),
+                    ctc_scores=f32("ctc_score"), attention_scores=f32("att_score"), token_logprobs=tlp.to(device), frames=[hyps[u]["frames"][j] for u, j in rows])
+
+    @torch.no_grad()
+    def rescore(self, inputs=None, attention_mask=None, *, input_values=None, input_features=None, num_beams=None, nbest=None, num_return_sequences=1, max_length=None,
+                length_penalty=None, ctc_weight=None, token_topk=None, return_dict=False):
+        """Two-pass joint decoding (decoder.rescore): the CTC head's n-best (`num_beams` hypotheses searched, `nbest` kept: default all) rescored by ONE teacher-forced
+        decoder pass and ranked by the objective `generate`'s beam search maximises.  Options left None come from `self.generation_config`.  Returns the
+        `num_return_sequences` best per utterance as a (B * k, L) LongTensor in `generate()`'s layout ([start, ..., eos] then pad_token_id), or with `return_dict` a dict of
+        sequences, sequences_scores, ctc_scores, attention_scores (B * k), token_logprobs (B * k, L - 1: of sequences[:, 1:], 0 past the EOS) and frames (per row the CTC
+        search's frame of each token).  Rows past the hypotheses that exist are [start, eos] with score -inf."""
+        inputs = self._pick_inputs(inputs, input_values, input_features)
+        W = int(num_beams if num_beams is not None else (getattr(self.generation_config, "num_beams", None) or 1))
+        max_length, lp, w, eos, pad, start = self._two_pass_options(max_length, length_penalty, ctc_weight)
+        k = int(num_return_sequences)
+        if not inputs.is_cuda:
+            raise RuntimeError("JointCTCAttentionEncoderDecoder (HIP): inputs must be on the GPU; there is no CPU fallback")
+        fl = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        hyps = _rescore(self._get_engine(inputs.device), inputs, fl, num_beams=W, nbest=nbest, token_topk=token_topk, ctc_weight=w, length_penalty=lp, max_length=max_length,
+                        num_return=k, eos_token_id=eos, pad_token_id=pad, start_token_id=start)
+        return self._two_pass_output(hyps, k, pad, inputs.device, return_dict)
+
+    @torch.no_grad()
+    def score(self, inputs=None, attention_mask=None, sequences=None, *, input_values=None, input_features=None, max_length=None, length_penalty=None, ctc_weight=None,
+              return_dict=False):
+        """The joint objective of GIVEN transcripts (decoder.score): `sequences` (B * k, L) or (B, k, L) int64 in `generate()`'s layout — the start token, the tokens,
+        the EOS, then padding (a row is read from behind its first token up to its first EOS / pad_token_id) — k <= 64 per utterance.  The CTC term is the exact
+        full-sequence log-probability (ops.ctc_loss).  Returns the (B * k) scores in the rows' order, or with `return_dict` `rescore`'s dict in that order (frames None)."""
+        inputs = self._pick_inputs(inputs, input_values, input_features)
+        max_length, lp, w, eos, pad, start = self._two_pass_options(max_length, length_penalty, ctc_weight)
+        B = inputs.shape[0]
+        if not isinstance(sequences, torch.Tensor) or sequences.dtype != torch.int64 or sequences.dim() not in (2, 3) or sequences.numel() == 0:
+            raise ValueError("score: sequences must be a (B * k, L) or (B, k, L) int64 tensor")
+        seq = sequences.detach().cpu()
+        if seq.dim() == 2:
+            if seq.shape[0] % B:
+                raise ValueError(f"score: {seq.shape[0]} sequences for {B} utterances")
+            seq = seq.view(B, seq.shape[0] // B, seq.shape[1])
+        if seq.shape[0] != B:
+            raise ValueError(f"score: {seq.shape[0]} groups of sequences for {B} utterances")
+        k, L = seq.shape[1], seq.shape[2]
+        hyp = torch.full((B, k, max(L - 1, 1)), -1, dtype=torch.long)
+        for b in range(B):
+            for j in range(k):
+                t = seq[b, j, 1:].tolist()
+                n = next((i for i, v in enumerate(t) if v == eos or v == pad or v < 0), len(t))
+                hyp[b, j, :n] = torch.tensor(t[:n], dtype=torch.long)
+        if not inputs.is_cuda:
+            raise RuntimeError("JointCTCAttentionEncoderDecoder (HIP): inputs must be on the GPU; there is no CPU fallback")
+        fl = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        ranked = _score(self._get_engine(inputs.device), inputs, fl, hyp.to(inputs.device), ctc_weight=w, length_penalty=lp, max_length=max_length, eos_token_id=eos,
+                        pad_token_id=pad, start_token_id=start)
+        given = []                                             # back into the order of the rows that were passed
+        for h in ranked:
+            inv = sorted(range(k), key=lambda r: h["order"][r])
+            given.append(dict(hypotheses=[h["hypotheses"][r] for r in inv], **{key: [h[key][r] for r in inv] for key in ("ctc_score", "att_score", "token_logprobs", "frames")}))
+        out = self._two_pass_output(given, k, pad, inputs.device, True)
+        return out if return_dict else out["sequences_scores"]

@@ -430,11 +430,11 @@ def gemm_argmax(a, w, bias):
     return best
 
 
-def gemm_ce(a, w, labels, *, return_target=False):
+def gemm_ce(a, w, labels, *, return_target=False, bias=None):
     """the language-model head with its cross-entropy, without the logits: a (M, K), w (N, K) bf16, labels (M) int64 (negative = ignored, CrossEntropyLoss's ignore_index)
     -> (acc [sum of the valid rows' nll, their count] fp32, lse (M) fp32, nll (M) fp32 = lse - logit[label], exactly 0 on ignored rows) out of the GEMM's epilogue
     (mi_gemm_ce_f32: no (M, N) tensor is written).  Shapes outside that kernel: the fp32 GEMM into a scratch, row_lse and ce_label_smoothing(shift=0, eps=0).
-    return_target: also the label's logit per row (M) fp32 (tests; undefined on ignored rows)."""
+    return_target: also the label's logit per row (M) fp32 (tests; undefined on ignored rows).  bias: (N) fp32 added to the logits (the folded multi-tap head's), or None."""
     _req(a, BF16); _req(w, BF16); _req(labels, torch.int64)
     M, K = a.shape
     N = w.shape[0]
@@ -443,10 +443,10 @@ def gemm_ce(a, w, labels, *, return_target=False):
     dev = a.device
     acc, lse, nll, tgt = (torch.empty((n,), device=dev, dtype=torch.float32) for n in (2, M, M, M))
     ws = torch.empty((int(L.mi_gemm_lse_workspace_floats(M, N)),), device=dev, dtype=torch.float32)
-    rc = L.mi_gemm_ce_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), None, labels.data_ptr(), acc.data_ptr(), lse.data_ptr(), nll.data_ptr(), tgt.data_ptr(),
+    rc = L.mi_gemm_ce_f32(a.data_ptr(), a.stride(0), w.data_ptr(), w.stride(0), _p(bias), labels.data_ptr(), acc.data_ptr(), lse.data_ptr(), nll.data_ptr(), tgt.data_ptr(),
                           ws.data_ptr(), M, N, K, _stream())
     if rc == _lib.ERR_UNSUPPORTED:
-        logits = gemm(a, w, out_dtype=torch.float32)
+        logits = gemm(a, w, bias, out_dtype=torch.float32)
         lse = row_lse(logits)
         acc = torch.zeros((2,), device=dev, dtype=torch.float32)
         L_rc = L.mi_ce_label_smoothing(logits.data_ptr(), logits.stride(0), labels.data_ptr(), 1, M, 0, N, 0.0, acc.data_ptr(), nll.data_ptr(), _stream())
@@ -457,6 +457,86 @@ def gemm_ce(a, w, labels, *, return_target=False):
     else:
         _lib.check(rc, "mi_gemm_ce_f32")
     return (acc, lse, nll, tgt) if return_target else (acc, lse, nll)
+
+
+def rows_nll(logits, lse, labels):
+    """logits (M, V) fp32 (contiguous rows, any row stride), lse (M) fp32 their log-sum-exp, labels (M) int64 -> nll (M) fp32 = lse - logits[m, labels[m]], exactly 0
+    where labels[m] < 0 (or >= V): `gemm_ce`'s nll for the routes that materialise logits (mi_rows_nll_f32)."""
+    _req(logits, torch.float32); _req(lse, torch.float32); _req(labels, torch.int64)
+    if logits.dim() != 2 or logits.stride(1) != 1 or lse.shape != (logits.shape[0],) or labels.shape != (logits.shape[0],):
+        raise TypeError("rows_nll: logits (M, V) fp32 with contiguous rows, lse (M) fp32, labels (M) int64")
+    M, V = logits.shape
+    lse, labels = lse.contiguous(), labels.contiguous()
+    nll = torch.empty((M,), device=logits.device, dtype=torch.float32)
+    rc = _lib.lib().mi_rows_nll_f32(logits.data_ptr(), logits.stride(0), lse.data_ptr(), labels.data_ptr(), V, nll.data_ptr(), M, _stream())
+    _lib.check(rc, "mi_rows_nll_f32")
+    return nll
+
+
+def _nbest_tokens(tokens, what):
+    if not isinstance(tokens, torch.Tensor) or tokens.dtype not in (torch.int32, torch.int64) or tokens.dim() != 3:
+        raise TypeError(f"{what}: tokens must be (B, N, Tt) int32 / int64")
+    _req(tokens)
+    return tokens.contiguous()
+
+
+def rescore_pack(tokens, n_tokens, ctc, *, vocab, U, start_id, eos_id, pad_id):
+    """An n-best as the teacher-forced decoder's operands (mi_rescore_pack, csrc/rescore.hip): tokens (B, N, Tt) int32 | int64, n_tokens (B, N) int32, ctc (B, N) fp32
+    -> dict(ids (B*N, U) int64 = [start, t_0 .. t_{k-1}, pad ..], labels (B*N, U) int64 = [t_0 .. t_{k-1}, eos, -100 ..], len (B*N) int32 = k + 1).  A hypothesis
+    with a non-finite score, more than U - 1 tokens or a token outside [0, vocab) does not exist: ids = [start, pad ..], labels = -100, len = 0."""
+    tokens = _nbest_tokens(tokens, "rescore_pack")
+    B, N, Tt = tokens.shape
+    _req(n_tokens, torch.int32); _req(ctc, torch.float32)
+    if n_tokens.shape != (B, N) or ctc.shape != (B, N):
+        raise ValueError(f"rescore_pack: n_tokens and ctc must be ({B}, {N})")
+    if U < 1 or vocab < 1 or B < 1 or N < 1 or Tt < 1:
+        raise ValueError(f"rescore_pack: B, N, Tt, vocab and U must be >= 1, got {B}, {N}, {Tt}, {vocab}, {U}")
+    dev = tokens.device
+    ids, labels = torch.empty((B * N, U), device=dev, dtype=torch.int64), torch.empty((B * N, U), device=dev, dtype=torch.int64)
+    ln = torch.empty((B * N,), device=dev, dtype=torch.int32)
+    rc = _lib.lib().mi_rescore_pack(tokens.data_ptr(), int(tokens.dtype == torch.int64), n_tokens.contiguous().data_ptr(), ctc.contiguous().data_ptr(), B, N, Tt, int(vocab),
+                                    int(U), int(start_id), int(eos_id), int(pad_id), ids.data_ptr(), labels.data_ptr(), ln.data_ptr(), _stream())
+    _lib.check(rc, "mi_rescore_pack")
+    return dict(ids=ids, labels=labels, len=ln)
+
+
+def rescore_select(nll, lens, ctc, denom, tokens, *, w_ctc, w_att, K, eos_id, pad_id, frames=None):
+    """Rank the N <= 64 hypotheses of every utterance by the joint objective and gather the best K (mi_rescore_select, csrc/rescore.hip): nll (B*N*U) fp32 the decoder's
+    per-position lse - logit[label], lens (B*N) int32, ctc (B, N) fp32, denom (U + 1) fp32 = l ** length_penalty from the host, tokens (B, N, Tt) the n-best, frames
+    (B, N, Tt) int32 or None.  total = (w_ctc * ctc + w_att * att) / denom[len], att = -(the nll of positions u < len summed in ascending order); len = 0 and NaN count
+    as -inf; descending total, equal totals by lower n.  -> dict(order (B, K) int32, total, att, ctc (B, K) fp32, token_lp (B, K, U) fp32 = -nll then 0, tokens (B, K, U)
+    int64 = the tokens, eos, then pad, n_tokens (B, K) int32[, frames (B, K, U) int32 then -1]), best first."""
+    tokens = _nbest_tokens(tokens, "rescore_select")
+    B, N, Tt = tokens.shape
+    _req(nll, torch.float32); _req(lens, torch.int32); _req(ctc, torch.float32); _req(denom, torch.float32)
+    if not 1 <= N <= 64 or not 1 <= int(K) <= N:
+        raise ValueError(f"rescore_select: 1 <= K <= N <= 64 required, got K = {K}, N = {N}")
+    if nll.numel() % (B * N) or nll.numel() < B * N:
+        raise ValueError(f"rescore_select: nll holds {nll.numel()} values for {B * N} hypotheses")
+    U = nll.numel() // (B * N)
+    if lens.numel() != B * N or ctc.numel() != B * N or denom.numel() != U + 1:
+        raise ValueError(f"rescore_select: lens and ctc must hold {B * N} values and denom {U + 1}")
+    K = int(K)
+    dev = tokens.device
+    if frames is not None:
+        _req(frames, torch.int32)
+        if frames.shape != tokens.shape:
+            raise ValueError("rescore_select: frames must have the shape of tokens")
+        frames = frames.contiguous()
+    nll, lens, ctc, denom = nll.contiguous(), lens.contiguous(), ctc.contiguous(), denom.contiguous()
+    order, out_n = torch.empty((B, K), device=dev, dtype=torch.int32), torch.empty((B, K), device=dev, dtype=torch.int32)
+    total, att, ctc_o = (torch.empty((B, K), device=dev, dtype=torch.float32) for _ in range(3))
+    tlp = torch.empty((B, K, U), device=dev, dtype=torch.float32)
+    otok = torch.empty((B, K, U), device=dev, dtype=torch.int64)
+    ofr = torch.empty((B, K, U), device=dev, dtype=torch.int32) if frames is not None else None
+    rc = _lib.lib().mi_rescore_select(nll.data_ptr(), lens.data_ptr(), ctc.data_ptr(), denom.data_ptr(), float(w_ctc), float(w_att), B, N, U, K, tokens.data_ptr(),
+                                      int(tokens.dtype == torch.int64), Tt, _p(frames), int(eos_id), int(pad_id), order.data_ptr(), total.data_ptr(), att.data_ptr(),
+                                      ctc_o.data_ptr(), tlp.data_ptr(), otok.data_ptr(), out_n.data_ptr(), _p(ofr), _stream())
+    _lib.check(rc, "mi_rescore_select")
+    out = dict(order=order, total=total, att=att, ctc=ctc_o, token_lp=tlp, tokens=otok, n_tokens=out_n)
+    if ofr is not None:
+        out["frames"] = ofr
+    return out
 
 
 def _lengths_i32(lengths, B, device):

@@ -801,6 +801,24 @@ size_t mi_decoder_step_f32_workspace_bytes(const mi_gpt2_config* cfg, int B, int
 int mi_decoder_step_f32(const mi_gpt2_config* cfg, const void* const* weights, const long* ids_new, int B, int beams, int U, int past, int Lmax,
                         void* const* kcache, void* const* vcache, const void* const* cross_kv, int T_enc, const int* enc_len, float emb_scale,
                         const float* head_bias, void* workspace, size_t workspace_bytes, float* logits, long ld_logits, mi_stream_t stream);
+/* ---- Two-pass joint decoding (csrc/rescore.hip, whose header states the exact semantics): a CTC n-best rescored by one teacher-forced decoder pass.  No counterpart
+ * in the reference.  No atomics, fixed summation order: bit-identical run to run.
+ * mi_rescore_pack: tokens (B, N, Tt) int32 (tokens_dtype 0) / int64 (1), n_tokens (B, N) int32, ctc (B, N) fp32 -> ids, labels (B*N, U) int64 and len (B*N) int32.  Row
+ * r = b N + n exists iff ctc[r] is finite, 0 <= k = n_tokens[r] <= min(U - 1, Tt) and its k tokens lie in [0, V): ids = [start, t_0 .. t_{k-1}, pad ..], labels =
+ * [t_0 .. t_{k-1}, eos, -100 ..], len = k + 1; otherwise ids = [start, pad ..], labels = -100, len = 0.
+ * mi_rows_nll_f32: nll[m] = lse[m] - x[m * ld + labels[m]], exactly 0 for labels[m] < 0 or >= V (x (M, ld >= V) fp32).
+ * mi_rescore_select: one block per utterance, N <= 64.  att[n] = -(((nll[0] + nll[1]) + nll[2]) ...) over u < len[n], ascending; total[n] = (w_ctc * ctc[n] + w_att *
+ * att[n]) / denom[len[n]], each multiply, the add and the divide rounded once (denom: U + 1 fp32 values from the host).  len = 0 (or outside [0, U]) and NaN totals
+ * count as -inf; descending total, equal totals by lower n.  For the best K <= N, best first: order (B, K) int32 = n, total / att / ctc_out (B, K), token_lp (B, K, U) =
+ * -nll then 0, out_tokens (B, K, U) int64 = the tokens, eos, then pad, out_n (B, K) int32 = the token count, out_frames (B, K, U) int32 = frames (B, N, Tt) then -1
+ * (frames and out_frames both null or both given).
+ * MI_ERR_ARG before any launch: a null operand, B / N / Tt / V / U < 1, N > 64, K outside 1..N, a bad tokens_dtype. */
+int mi_rescore_pack(const void* tokens, int tokens_dtype, const int* n_tokens, const float* ctc, int B, int N, int Tt, int V, int U, long start, long eos, long pad,
+                    long* ids, long* labels, int* len, mi_stream_t stream);
+int mi_rows_nll_f32(const float* x, long ld, const float* lse, const long* labels, int V, float* nll, int M, mi_stream_t stream);
+int mi_rescore_select(const float* nll, const int* len, const float* ctc, const float* denom, float w_ctc, float w_att, int B, int N, int U, int K, const void* tokens,
+                      int tokens_dtype, int Tt, const int* frames, long eos, long pad, int* order, float* total, float* att, float* ctc_out, float* token_lp,
+                      long* out_tokens, int* out_n, int* out_frames, mi_stream_t stream);
 
 #ifdef __cplusplus
 }
