@@ -368,6 +368,14 @@ class EBranchformerEngine:
         out.update(inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
         return out
 
+    def stream(self, batch: int, chunk_frames: int, max_frames: int):
+        """Streaming inference of a causal model (bf16): -> streaming.EncoderStream for `batch` streams advanced in lock-step, `chunk_frames` encoder frames (4x as many
+        feature frames) per `feed`, K/V caches of `max_frames` encoder frames.  Fed an utterance piece by piece it returns forward()'s logits of that utterance alone, each
+        frame num_hidden_layers * (merge_conv_kernel - 1) / 2 frames late (csrc/stream.hip; DESIGN.md §4 'Streaming').  Refused before any launch: a non-causal config
+        (ValueError); precision="fp32", layer mixing, an additional layer (NotImplementedError)."""
+        from .streaming import EncoderStream
+        return EncoderStream(self, batch, chunk_frames, max_frames)
+
     def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
         """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
         Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also

@@ -778,3 +778,59 @@ def cast_bf16(x):
     rc = _lib.lib().mi_cast_f32_bf16(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), M, d, _stream())
     _lib.check(rc, "mi_cast_f32_bf16")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- streaming inference (csrc/stream.hip)
+def attention_chunk(q, k_cache, v_cache, n_k, H, *, pos=None, bias_u=None, bias_v=None, scale=None, ref=0):
+    """q (B, n_q, d) bf16 = the new rows' queries; k_cache / v_cache (B, Lmax, d) bf16 row views of one cache (same strides) whose first n_k rows are keys, the new rows'
+    own last; query i sees keys j <= n_k - n_q + i.  pos (>= n_k, d) bf16 = the projected sinusoid of distance i - j in row i - j, with bias_u / bias_v (d) fp32 (all
+    three or none).  ref 0..3: whose key walk the bf16 rounding of the probabilities follows (0 the row maximum; 1 / 2 / 3 the full forward's kernels).
+    -> (B, n_q, d) bf16.  mi_attention_chunk_bf16."""
+    _req(q, BF16); _req(k_cache, BF16); _req(v_cache, BF16)
+    B, n_q, d = q.shape
+    q = q.contiguous()
+    if k_cache.stride() != v_cache.stride() or k_cache.stride(2) != 1:
+        raise ValueError("attention_chunk: k_cache and v_cache must be row views with equal strides")
+    hd = d // H
+    out = torch.empty((B, n_q, d), device=q.device, dtype=BF16)
+    rc = _lib.lib().mi_attention_chunk_bf16(q.data_ptr(), d, k_cache.data_ptr(), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(1), k_cache.stride(0),
+                                            _p(pos), 0 if pos is None else pos.stride(0), _p(bias_u), _p(bias_v), out.data_ptr(), d, B, n_q, int(n_k), H, hd,
+                                            float(scale if scale is not None else 1.0 / math.sqrt(hd)), int(ref), _stream())
+    _lib.check(rc, "mi_attention_chunk_bf16")
+    return out
+
+
+DWCONV_STREAM_MODES = {"csgu": 0, "merge": 1, "conv": 2}
+
+
+def dwconv_stream(x, w, bias, ring, *, mode, p, K, dil=1, left, o0, n_out, ring_stats=None, stats=None, gamma=None, beta=None, mul=None, end=None, act=0):
+    """Stateful depthwise conv over time (mi_dwconv_stream_bf16): x (B, n_new, C) bf16 (last dim contiguous, any row stride; batch b at row b * n_new) = rows
+    [p, p + n_new); ring (B, Hr, C) bf16 = rows [p - Hr, p) at slot t % Hr, advanced in place (ring_stats (B, ceil(C/64), Hr, 2) fp32 with modes "csgu" / "conv");
+    -> (B, n_out, C) bf16 = rows [o0, o0 + n_out).  mode "csgu": x_r * act(conv(LN(x_g)) + b) with stats (B * n_new, 2), gamma, beta, mul = x_r; "merge": x + conv(x)
+    + b, rows >= end[b] zero (a stream ends among the rows of the call that carries `end`, or where they end: end[b] >= p); "conv": the conv of "csgu" alone."""
+    _req(x, BF16); _req(ring, BF16)
+    B, n_new, Cc = x.shape
+    Hr = ring.shape[1]
+    out = torch.empty((B, n_out, Cc), device=x.device, dtype=BF16)
+    if end is not None:
+        end = _lengths_i32(end, B, x.device)
+    rc = _lib.lib().mi_dwconv_stream_bf16(x.data_ptr(), x.stride(1) if n_new else Cc, _p(mul), 0 if mul is None else mul.stride(1), _p(stats), _p(gamma), _p(beta), w.data_ptr(), _p(bias),
+                                          ring.data_ptr() if Hr else 0, _p(ring_stats), _p(end), out.data_ptr(), Cc, B, Cc, int(K), int(dil), int(left), Hr, int(p), n_new,
+                                          int(o0), int(n_out), DWCONV_STREAM_MODES[mode], int(act), _stream())
+    _lib.check(rc, "mi_dwconv_stream_bf16")
+    return out
+
+
+def ctc_collapse_stream(best, blank, prev, n_valid=None, offset=0):
+    """best (B, T) int32 per-frame classes of one call, prev (B) int32 = the class before its first frame (-1 at stream start; updated in place) -> (ids (B, T) int32 =
+    the newly emitted tokens then -1, n_ids (B) int32).  Frames t < n_valid[b] - offset count (all T without n_valid).  mi_ctc_collapse_stream."""
+    _req(best, torch.int32); _req(prev, torch.int32)
+    best = best.contiguous()
+    B, T = best.shape
+    ids = torch.empty((B, T), device=best.device, dtype=torch.int32)
+    n = torch.empty((B,), device=best.device, dtype=torch.int32)
+    if n_valid is not None:
+        n_valid = _lengths_i32(n_valid, B, best.device)
+    rc = _lib.lib().mi_ctc_collapse_stream(best.data_ptr(), B, T, _p(n_valid), int(offset), int(blank), prev.data_ptr(), ids.data_ptr(), n.data_ptr(), _stream())
+    _lib.check(rc, "mi_ctc_collapse_stream")
+    return ids, n

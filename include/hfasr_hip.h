@@ -732,6 +732,43 @@ int mi_ebf_forward_greedy(const mi_ebf_config* cfg, const void* const* weights, 
                           const void* pos_table, void* posp, int compute_posp, void* workspace, size_t workspace_bytes,
                           float* last_hidden, int* best, float* argmax_workspace, void* head_scratch, int* inner_len, int* outer_len, mi_stream_t stream);
 
+/* ---- streaming inference for the causal (is_causal) encoder + CTC head: a stateful chunk step (csrc/stream.hip, whose header states the exact semantics).
+ * replaces: nothing the reference runs — it trains streaming models (src/models/streaming_modules.py, recipes *_streaming.sh) and decodes them on whole utterances; the step
+ * returns, piece by piece, the logits mi_ebf_forward returns for the utterance alone.  Opt-in; nothing above changes.  DESIGN.md §4 'Streaming'. */
+/* attention of n_q new queries over a (B, Lmax, .) K/V cache of n_k >= n_q keys per stream, the causal diagonal at the end: query i sees keys j <= n_k - n_q + i.
+ * q (B*n_q, ldq) bf16; k / v rows of the cache (row stride ldk == ldv, batch stride kv_bstride, elements; 16-B aligned, strides % 8 == 0); pos (>= n_k rows, ldp) bf16 = the
+ * projected sinusoid of distance i - j in row i - j, with bias_u / bias_v (H*hd) — all three or none (plain attention; rotary is applied upstream); out (B*n_q, ldo) bf16.
+ * ref: the probabilities are rounded to bf16 for the PV product as 2^(s - m); m = 0: the row maximum; 1 / 2 / 3: the running reference of the full forward's kernel walking
+ * 32-key tiles — mi_attention_bf16's, the four-wave and the eight-wave form of mi_attention_qkv_bf16 —, which keeps a streamed layer closest to that forward.
+ * MI_ERR_UNSUPPORTED: hd outside {16, 64, 128}, n_k > 8192.  No atomics; a stream's rows do not depend on the other streams. */
+int mi_attention_chunk_bf16(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, long kv_bstride, const void* pos, long ldp,
+                            const float* bias_u, const float* bias_v, void* out, long ldo, int B, int n_q, int n_k, int H, int hd, float scale, int ref, mi_stream_t stream);
+/* stateful depthwise conv over time: in (B, n_new, ld_in) bf16 = rows [p, p + n_new) of every stream; ring (B, Hr, C) bf16 = rows [p - Hr, p) at slot t % Hr, advanced by
+ * the same launch (modes 0 / 2 also ring_stats (B, ceil(C/64), Hr, 2) fp32); out (B, n_out, ld_out) bf16 = rows [o0, o0 + n_out).  Tap k reads row t - left + k*dil;
+ * rows < 0, >= p + n_new and >= end[b] (end (B) int32, nullable) read as zero.  mode 0 CSGU: out = x_r * act(conv(LN(x_g)) + b) with the rows' given (mean, rstd) `stats`
+ * (B*n_new, 2), gamma / beta, mul = x_r of the output rows (needs o0 == p, n_out == n_new), act 0..3 as mi_csgu_bf16; mode 1 MERGE: out = m + conv(m) + b; mode 2: the
+ * conv of mode 0 alone (csgu_use_linear_after_conv).  MI_ERR_ARG: a window that leaves [p - Hr, p + n_new) (beyond the end only with `end`). */
+int mi_dwconv_stream_bf16(const void* in, long ld_in, const void* mul, long ld_mul, const float* stats, const float* gamma, const float* beta,
+                          const float* w, const float* bias, void* ring, float* ring_stats, const int* end, void* out, long ld_out,
+                          int B, int C, int K, int dil, int left, int Hr, int p, int n_new, int o0, int n_out, int mode, int act, mi_stream_t stream);
+/* mi_ctc_collapse across calls: best (B, T) int32; frames t < n_b count (n_b = n_valid[b] - offset clamped to [0, T]; T when n_valid is null); a frame is kept iff its
+ * class is not blank and differs from the class before it — for t = 0 prev[b], the last class of the previous call (-1 at stream start); prev is updated.
+ * ids (B, T) int32: the newly emitted tokens then -1; n_ids (B). */
+int mi_ctc_collapse_stream(const int* best, int B, int T, const int* n_valid, int offset, int blank, int* prev, int* ids, int* n_ids, mi_stream_t stream);
+/* the driver.  cfg as for mi_ebf_forward with B = streams, T = 4 * chunk_frames, fp32 logits; same weight table.  Refused (size 0 / MI_ERR_ARG / MI_ERR_UNSUPPORTED): a
+ * non-causal config, a front end other than 3x3 / stride 2 / padding 1, the fine-tuning head, head sizes outside {16, 64, 128}, max_frames > 8192.
+ * state: mi_ebf_stream_state_bytes bytes (host arithmetic; linear in max_frames) — caches, histories and the step's scratch; mi_ebf_stream_reset starts the streams
+ * (relative positions: pos_table (max_frames, d) bf16 = the sinusoid of distance 0 .. max_frames - 1, projected per layer into the state).
+ * mi_ebf_stream_step: feats (B, 4*chunk_frames, F) fp32; rows: HOST array of 2*(L+1) ints = (lo, hi) of the input rows of every layer and of the emitted rows
+ * (streaming.plan); ends (B) int32 device, non-null exactly in the last step: every stream's frame count; pos_table: rotary fp32 [cos (max_frames, hd) | sin], else
+ * unused.  For the n_out emitted frames: logits (B, n_out, logits_ld) fp32, best (B, n_out) int32, ids (B, n_out) int32 then -1, n_ids (B).  One call advances every
+ * layer; no host round trip. */
+size_t mi_ebf_stream_state_bytes(const mi_ebf_config* cfg, int chunk_frames, int max_frames);
+int mi_ebf_stream_reset(const mi_ebf_config* cfg, const void* const* weights, int chunk_frames, int max_frames, const void* pos_table, void* state, size_t state_bytes,
+                        mi_stream_t stream);
+int mi_ebf_stream_step(const mi_ebf_config* cfg, const void* const* weights, int chunk_frames, int max_frames, const void* pos_table, void* state, size_t state_bytes,
+                       const float* feats, const int* rows, const int* ends, float* logits, int* best, int* ids, int* n_ids, mi_stream_t stream);
+
 /* ---- precision = "fp32" inference mode (csrc/gemm_f32.hip, csrc/encoder_f32.hip): the encoder + CTC head with every operand, activation and weight in fp32 — what the
  * reference's decode recipes (no --bf16) compute.  Opt-in; nothing above changes.  DESIGN.md §4 'fp32 inference mode'. */
 /* C (M,N) = resid + alpha * act(A (M,K) · W (N,K)^T + bias), all fp32, row-major with leading dimensions; act 0 none / 1 erf-GELU (exact erff) / 2 gelu_new (exact tanhf); bias, resid nullable,
