@@ -156,13 +156,19 @@ int Fwd::front_end(const float* feats) const {
         RUN(mi_conv2d_cl_geo_bf16(w.act1, Gw(G_GATE2_W), Gf(G_GATE2_B), w.g2, c.B, D.T1, D.F1, c.C1, c.C2, KH, c.K, sg, c.stride, pg, pl, Tg2, D.F2, 0, 0, st));
         RUN(mi_gated_act_bf16(w.z2, c.C2, w.g2, c.C2, w.act2, c.C2, c.B, D.T2, D.F2, c.C2, 4, 0, st));
     }
+    // Both Linears below are N = d GEMMs: in throughput mode they run on the 256 x 256 tile like the layers' (folded_layer's gv); a shape that kernel refuses keeps the product's call
+    const int gv = c.wide_tiles ? 40 : 0;
+    auto linear = [&](const bf16_t* A, long K, const void* W, const float* bias, float* C) {
+        int rc = gv ? mi_gemm_bf16_v(A, K, W, K, bias, 1, C, d, 1, nullptr, 0, 1.f, 0, M, d, (int)K, 0, 0, gv, st) : MI_ERR_UNSUPPORTED;
+        if (rc == MI_ERR_UNSUPPORTED) rc = mi_gemm_bf16(A, K, W, K, bias, 1, C, d, 1, nullptr, 0, 1.f, 0, M, d, (int)K, 0, 0, st);
+        return rc;
+    };
     // (B,C,T',F') -> transpose -> flatten -> Linear: act2 is already (B*T', F'*C) with the weight columns permuted to match
-    RUN(mi_gemm_bf16(w.act2, (long)D.F2 * c.C2, Gw(G_FEOUT_W), (long)D.F2 * c.C2, Gf(G_FEOUT_B), 1, w.feo, d, 1, nullptr, 0, 1.f, 0,
-                     M, d, D.F2 * c.C2, 0, 0, st));
+    RUN(linear(w.act2, (long)D.F2 * c.C2, Gw(G_FEOUT_W), Gf(G_FEOUT_B), w.feo));
     // feature projection: LN -> Linear (extractors.py:130-131; tf:328-333)
     RUN(mi_layernorm_chain(w.feo, d, nullptr, T2, nullptr, nullptr, 0.f, nullptr, 0, Gf(G_FP_LN_G), Gf(G_FP_LN_B), c.ln_eps,
                            w.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, M, d, st));
-    return mi_gemm_bf16(w.a0, d, Gw(G_FP_W), d, Gf(G_FP_B), 1, w.x, d, 1, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st);
+    return linear(w.a0, d, Gw(G_FP_W), Gf(G_FP_B), w.x);
 }
 
 // x = src with padded frames zeroed (tf:662-665); first LayerNorm(s) of layer l

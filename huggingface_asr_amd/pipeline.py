@@ -16,19 +16,35 @@ import torch
 from .engine import EBranchformerEngine
 
 
+DEFAULT_HW_QUEUES = 4          # the HIP runtime's own GPU_MAX_HW_QUEUES
+
+
 def reserve_hw_queues(lanes: int) -> int:
     """The HIP runtime maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and reads that variable once, when it initialises:
     with four lanes next to the default stream two of them take turns on one queue (measured, base encoder, wide tiles: 4.61 ms per step; with 8 queues 3.85).
-    Call this BEFORE the first HIP call of the process (torch.cuda.is_available() is one); it leaves a value the user exported alone.
+    Call this BEFORE the first HIP call of the process (torch.cuda.is_available() is one).  Four or more lanes need 8 queues: the variable is raised to 8 when it is
+    absent or holds the runtime's default of 4 — an environment that spells the default out (a job wrapper exporting GPU_MAX_HW_QUEUES=4 for every command) expresses no
+    choice about lanes.  It is never lowered and never set above 8 here; a value above the need stays, and so does one BELOW the runtime's default (1-3: a restriction
+    somebody chose).  HFASR_HW_QUEUES=<n> pins the count whatever the lanes need.
     -> the queue count the runtime will see."""
-    want = 8 if lanes > 3 else 4
+    want = 8 if lanes > 3 else DEFAULT_HW_QUEUES
     have = os.environ.get("GPU_MAX_HW_QUEUES")
-    if have is None and want > 4:
-        if torch.cuda.is_initialized():
-            raise RuntimeError("reserve_hw_queues: the HIP runtime is already initialised; export GPU_MAX_HW_QUEUES=8 before starting the process")
-        os.environ["GPU_MAX_HW_QUEUES"] = str(want)
+    pin = os.environ.get("HFASR_HW_QUEUES")
+    if pin is not None:
+        want = int(pin)
+        if not 1 <= want <= 32:
+            raise ValueError(f"HFASR_HW_QUEUES={pin!r}: a queue count from 1 to 32")
+    elif have is None:
+        if want == DEFAULT_HW_QUEUES:
+            return want                              # nothing to raise: the variable stays absent
+    elif not DEFAULT_HW_QUEUES <= int(have) < want:
+        return int(have)                             # enough already, or a restriction below the default
+    if have is not None and int(have) == want:
         return want
-    return int(have) if have is not None else 4
+    if torch.cuda.is_initialized():
+        raise RuntimeError(f"reserve_hw_queues: the HIP runtime is already initialised; export GPU_MAX_HW_QUEUES={want} before starting the process")
+    os.environ["GPU_MAX_HW_QUEUES"] = str(want)
+    return want
 
 
 class ForwardPipeline:
@@ -40,8 +56,9 @@ class ForwardPipeline:
         self.device = torch.device(device)
         if lanes > 3 and int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) < 8:
             import warnings
-            warnings.warn("ForwardPipeline: more than 3 lanes on the HIP runtime's default 4 hardware queues — two lanes will take turns on one queue (measured: 4.6 instead of "
-                          "3.8 ms per step); call pipeline.reserve_hw_queues(lanes) before the first HIP call of the process, or export GPU_MAX_HW_QUEUES=8", RuntimeWarning)
+            warnings.warn("ForwardPipeline: more than 3 lanes on fewer than 8 hardware queues — lanes will take turns on one queue (measured on 4 queues: 4.6 instead of "
+                          "3.8 ms per step); call pipeline.reserve_hw_queues(lanes) before the first HIP call of the process (it raises an absent or default "
+                          "GPU_MAX_HW_QUEUES to 8; HFASR_HW_QUEUES pins another count), or export GPU_MAX_HW_QUEUES=8", RuntimeWarning)
         self.engines = []
         for i in range(lanes):
             e = EBranchformerEngine(cfg, self.device)

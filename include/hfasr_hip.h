@@ -689,7 +689,8 @@ typedef struct {
                                     the N = d GEMMs that produce the residual stream also emit its bf16 copy and per-row partial statistics, the consumers take those instead of
                                     a LayerNorm kernel's output — one LayerNorm launch per layer instead of three.  Needs the layer slots *_WF / *_SF / *_CF (engine.py LS), relative
                                     or no positions, macaron FFNs, d in {256, 512}, I % 256 == 0, no fine-tuning head.  0: LayerNorm kernels + plain GEMMs. */
-    int wide_tiles;              /* throughput mode (with ln_fold): the N = d GEMMs of a layer (FFN out x2, attention out, cgMLP out, merge) run on 256 x 256 tiles too — a quarter
+    int wide_tiles;              /* throughput mode (with ln_fold): the N = d GEMMs of a layer (FFN out x2, attention out, cgMLP out, merge) and of the front end (the conv
+                                    sub-sampling's output Linear, the feature projection) run on 256 x 256 tiles too — a quarter
                                     of the blocks of the 128 x 128 kernel (64 per launch at M = 8000, d = 512), 2x the FLOP per ingested byte.  Alone such a launch leaves most
                                     of the chip idle; it is meant for several independent steps in flight on their own streams (huggingface_asr_amd/pipeline.py), whose kernels
                                     then share the chip by CU instead of taking turns on all of it.  Same results as 0 up to the summation order of the row statistics. */
