@@ -81,6 +81,9 @@ SIGNATURES = {
     "mi_ctc_beam_workspace_bytes": [i32, i32, i32],
     "mi_ctc_beam_cut": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp],
     "mi_ctc_beam_walk": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp, i32, vp, vp, vp, vp],
+    "mi_ctc_beam_stream_state_bytes": [i32, i32, i32],
+    "mi_ctc_beam_stream_reset": [vp, sz, i32, i32, i32, vp],
+    "mi_ctc_beam_stream_walk": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "mi_ctc_align_workspace_bytes": [i32, i32, i32],
     "mi_ctc_align": [vp, i64, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp],
     "mi_gemm_argmax_workspace_floats": [i32, i32],
@@ -251,7 +254,7 @@ def lib():
             fn.argtypes = args
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
-                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes", "mi_ctc_align_workspace_bytes",
+                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes", "mi_ctc_beam_stream_state_bytes", "mi_ctc_align_workspace_bytes",
                                           "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes", "mi_ebf_stream_state_bytes", "mi_linear_rows_f32_workspace_bytes", "mi_decoder_step_f32_workspace_bytes") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None

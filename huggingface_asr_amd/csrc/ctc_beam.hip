@@ -43,25 +43,18 @@
 //   ctc_walk_kernel   256 threads (W (K + 1) <= 1024) or 1024, 65 VGPRs, 44576 B of LDS (32.5 KiB candidate keys, 4 KiB merge flags, the two beams); no scratch
 #include "common.hpp"
 #include "radix_select.hpp"
+#include "ctc_walk_step.hpp"
 #include "../../include/hfasr_hip.h"
 
 namespace {
 
-constexpr int CB_MAXW = 64, CB_MAXK = 64, CB_MAXC = CB_MAXW * (CB_MAXK + 1);
 constexpr int CUT_THREADS = 256, CUT_VCACHE = 8192;
-constexpr unsigned KEY_NEG_INF = 0x007FFFFFu;                           // ord_key(-inf): a candidate counts iff its value key is above it
-constexpr float NEG_INF = -__builtin_inff();
 
 template <typename T> struct Vec16;
 template <> struct Vec16<float> { typedef f32x4 type; static constexpr int N = 4; };
 template <> struct Vec16<bf16_t> { typedef bf16x8 type; static constexpr int N = 8; };
 
 __device__ __forceinline__ unsigned value_key(float v) { return (unsigned)(argmax_key(v, 0) >> 32); }      // ord_key with every NaN on top, the shared argmax order
-__device__ __forceinline__ float logaddexp_f(float a, float b) {
-    const float m = fmaxf(a, b), d = fminf(a, b) - m;
-    return m == NEG_INF ? m : m + log1pf(expf(d));
-}
-__device__ __forceinline__ float log_prob(float x, float lse) { return x == NEG_INF ? NEG_INF : x - lse; }
 
 struct CutArgs {
     const void* x; long ld_t, ld_b;
@@ -192,30 +185,12 @@ struct WalkArgs {
     void* tokens; int* n_tokens; float* scores; int* frames;
 };
 
-// a table word: (parent node + 1) in bits 63..42, the token in 41..22, the node in 21..0; 0 = empty
-__device__ __forceinline__ u64 node_word(int parent, int token) { return ((u64)(unsigned)(parent + 1) << 42) | ((u64)(unsigned)token << 22); }
-__device__ __forceinline__ unsigned node_hash(u64 w) {
-    u64 z = (w >> 22) * 0x9E3779B97F4A7C15ull;
-    return (unsigned)(z >> 32);
-}
-
-struct Beam {
-    float pb[CB_MAXW], pnb[CB_MAXW], sc[CB_MAXW];
-    int node[CB_MAXW], last[CB_MAXW], parent[CB_MAXW], len[CB_MAXW];
-};
-
+// the frame step (walk_frame) and the backtrace (walk_backtrace) are ctc_walk_step.hpp's: ctc_beam_stream.hip walks with the same ones
 template <typename TOK>
 __global__ __launch_bounds__(1024) void ctc_walk_kernel(WalkArgs p) {
-    __shared__ u64 keys[CB_MAXC];
-    __shared__ unsigned dead_words[CB_MAXW * CB_MAXK / 4];             // one byte per extension (i, k): it was folded into a survivor
-    __shared__ Beam beams[2];
-    __shared__ float tot[CB_MAXW], spb[CB_MAXW], spnb[CB_MAXW], ssc[CB_MAXW], tlp[CB_MAXK];
-    __shared__ int tcls[CB_MAXK], isnew[CB_MAXW], outlen[CB_MAXW];
-    __shared__ u64 surv[CB_MAXW];
-    __shared__ int hist[256], ctl[4], taken, n_next, n_nodes[2];
+    __shared__ WalkLds L;
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    unsigned char* dead = reinterpret_cast<unsigned char*>(dead_words);
-    const int W = p.W, K = p.K, T = p.T, Kk = min(K, p.V1 - 1), nbest = p.nbest;
+    const int W = p.W, T = p.T, nbest = p.nbest;
     const int n_b = p.lengths ? min(max(p.lengths[b], 0), T) : T;
     int4* arena = p.arena + (long)b * p.arena_stride;
     u64* table = p.table + (long)b * p.table_stride;
@@ -223,168 +198,21 @@ __global__ __launch_bounds__(1024) void ctc_walk_kernel(WalkArgs p) {
     while (H < 2u * (1u + (unsigned)n_b * (unsigned)W)) H <<= 1;
     for (unsigned i = tid; i < H; i += nt) __hip_atomic_store(&table[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid == 0) {
-        Beam& s = beams[0];
+        Beam& s = L.beams[0];
         s.pb[0] = 0.f; s.pnb[0] = NEG_INF; s.sc[0] = 0.f; s.node[0] = 0; s.last[0] = -1; s.parent[0] = -1; s.len[0] = 0;
         arena[0] = make_int4(-1, -1, -1, 0);
-        n_nodes[0] = 1;
+        L.n_nodes[0] = 1;
     }
     __syncthreads();
 
+    const WalkIn q{p.x, p.dtype, W, p.K, min(p.K, p.V1 - 1), p.lse, p.lpb, p.cut_lp, p.cut_id, arena, p.arena_stride, table, H};
     int n = 1, cur = 0;
-    for (int t = 0; t < n_b && n > 0; ++t, cur ^= 1) {
-        const Beam& s = beams[cur];
-        Beam& nx = beams[cur ^ 1];
-        const long row = (long)b * T + t;
-        const float lpb = p.lpb[row], lse = p.lse[row];
-        if (tid < Kk) { tlp[tid] = p.cut_lp[row * K + tid]; tcls[tid] = p.cut_id[row * K + tid]; }
-        for (int i = tid; i < CB_MAXW * CB_MAXK / 4; i += nt) dead_words[i] = 0u;
-        if (tid == 0) { taken = 0; n_next = 0; }
-        if (tid < n) {                                                 // the survivor terms
-            const float a = s.pb[tid], c = s.pnb[tid];
-            const float tt = logaddexp_f(a, c);
-            const int last = s.last[tid];
-            float own = NEG_INF;
-            if (last >= 0) {
-                const long at = (long)b * p.ld_b + (long)t * p.ld_t + last;
-                const float xv = p.dtype ? (float)((const bf16_t*)p.x)[at] : ((const float*)p.x)[at];
-                own = c + log_prob(xv, lse);
-            }
-            tot[tid] = tt; spb[tid] = tt + lpb; spnb[tid] = own;
-        }
-        __syncthreads();
-        if (tid < n) {                                                 // the merge: survivor tid absorbs the extension of its parent by its last token
-            const int last = s.last[tid], par = s.parent[tid];
-            float own = spnb[tid];
-            if (last >= 0) {
-                int pi = -1, pk = -1;
-                for (int i = 0; i < n; ++i) pi = s.node[i] == par ? i : pi;
-                for (int k = 0; k < Kk; ++k) pk = tcls[k] == last ? k : pk;
-                if (pi >= 0 && pk >= 0) {
-                    own = logaddexp_f(own, (s.last[pi] == last ? s.pb[pi] : tot[pi]) + tlp[pk]);
-                    dead[pi * K + pk] = 1;
-                    spnb[tid] = own;
-                }
-            }
-            ssc[tid] = logaddexp_f(spb[tid], own);
-        }
-        __syncthreads();
-        const int ntot = n * (Kk + 1), kk = min(W, ntot);
-        for (int e = tid; e < ntot; e += nt) {
-            float v; int idx;
-            if (e < n) { v = ssc[e]; idx = e; }
-            else {
-                const int q = e - n, i = q / Kk, k = q - i * Kk;
-                idx = W + i * K + k;
-                v = dead[i * K + k] ? NEG_INF : (tcls[k] == s.last[i] ? s.pb[i] : tot[i]) + tlp[k];
-            }
-            keys[e] = cand_key(ord_key(v), idx);
-        }
-        auto each = [&](auto&& f) {
-            for (int e = tid; e < ntot; e += nt) f(keys[e]);
-        };
-        u64 thr; int shift;
-        radix_select(each, kk, hist, ctl, thr, shift);                 // (its first barrier publishes the keys)
-        each([&](u64 key) {
-            if ((key >> shift) >= thr) {
-                const int slot = atomicAdd(&taken, 1);
-                if (slot < CB_MAXW) surv[slot] = key;
-            }
-        });
-        __syncthreads();
-        if (tid < kk) {                                                // best first; a selected extension looks for the node its prefix had
-            const u64 my = surv[tid];
-            int rank = 0;
-            for (int j = 0; j < kk; ++j) rank += surv[j] > my ? 1 : 0;
-            const unsigned hi = (unsigned)(my >> 24);
-            int fresh = 0;
-            if (hi > KEY_NEG_INF) {
-                const float v = ord_value(hi);
-                int idx = key_index(my);
-                atomicAdd(&n_next, 1);
-                if (idx < W) {
-                    idx = idx < n ? idx : 0;                           // (never taken)
-                    nx.pb[rank] = spb[idx]; nx.pnb[rank] = spnb[idx]; nx.sc[rank] = v;
-                    nx.node[rank] = s.node[idx]; nx.last[rank] = s.last[idx]; nx.parent[rank] = s.parent[idx]; nx.len[rank] = s.len[idx];
-                } else {
-                    int i = (idx - W) / K, k = (idx - W) - i * K;
-                    i = i < n ? i : 0; k = k < Kk ? k : 0;             // (never taken)
-                    const int tok = tcls[k], par = s.node[i];
-                    const u64 w = node_word(par, tok);
-                    int found = -1;
-                    unsigned h = node_hash(w);
-                    for (unsigned probe = 0; probe < H; ++probe, ++h) {
-                        const u64 e = __hip_atomic_load(&table[h & (H - 1)], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        if (e == 0ull) break;
-                        if ((e >> 22) == (w >> 22)) { found = (int)(e & 0x3FFFFFull); break; }
-                    }
-                    fresh = found < 0 ? 1 : 0;
-                    nx.pb[rank] = NEG_INF; nx.pnb[rank] = v; nx.sc[rank] = v;
-                    nx.node[rank] = found; nx.last[rank] = tok; nx.parent[rank] = par; nx.len[rank] = s.len[i] + 1;
-                }
-            }
-            isnew[rank] = fresh;
-        }
-        __syncthreads();
-        const int nn = n_next, base = n_nodes[cur];
-        if (tid < nn) {                                                // new prefixes get the next node ids in rank order, and enter the table
-            int off = 0;
-            for (int r = 0; r < tid; ++r) off += isnew[r];
-            if (isnew[tid]) {
-                const int id = base + off, par = nx.parent[tid], tok = nx.last[tid];
-                nx.node[tid] = id;
-                arena[id < p.arena_stride ? id : 0] = make_int4(par, tok, t, nx.len[tid]);
-                const u64 w = node_word(par, tok) | (u64)(unsigned)id;
-                unsigned h = node_hash(w);
-                for (unsigned probe = 0; probe < H; ++probe, ++h)
-                    if (atomicCAS(&table[h & (H - 1)], 0ull, w) == 0ull) break;
-            }
-            if (tid == nn - 1) n_nodes[cur ^ 1] = base + off + isnew[tid];
-        }
-        if (nn == 0 && tid == 0) n_nodes[cur ^ 1] = base;
-        __syncthreads();
-        n = nn;
-    }
+    for (int t = 0; t < n_b && n > 0; ++t, cur ^= 1) n = walk_frame(L, q, cur, n, (long)b * T + t, (long)b * p.ld_b + (long)t * p.ld_t, t);
 
     // ---- the n best, backtraced; rows that do not exist
-    const Beam& s = beams[cur];
-    TOK* tokens = (TOK*)p.tokens + (long)b * nbest * T;
-    int* frames = p.frames ? p.frames + (long)b * nbest * T : nullptr;
-    if (tid < nbest) {
-        const long row = (long)b * nbest + tid;
-        int len = 0;
-        float sc = NEG_INF;
-        if (tid < n) {
-            len = min(s.len[tid], T);
-            sc = s.sc[tid];
-            int nd = s.node[tid];
-            for (int pos = len - 1; pos >= 0 && nd > 0; --pos) {
-                const int4 e = arena[nd < p.arena_stride ? nd : 0];
-                tokens[(long)tid * T + pos] = (TOK)e.y;
-                if (frames) frames[(long)tid * T + pos] = e.z;
-                nd = e.x;
-            }
-        }
-        outlen[tid] = len;
-        p.n_tokens[row] = len;
-        p.scores[row] = sc;
-    }
-    __syncthreads();
-    for (long i = tid; i < (long)nbest * T; i += nt) {
-        const int r = (int)(i / T), pos = (int)(i - (long)r * T);
-        if (pos >= outlen[r]) {
-            tokens[i] = (TOK)p.pad_id;
-            if (frames) frames[i] = -1;
-        }
-    }
+    walk_backtrace<TOK>(L, L.beams[cur], n, nbest, T, arena, p.arena_stride, p.pad_id, (TOK*)p.tokens + (long)b * nbest * T,
+                        p.frames ? p.frames + (long)b * nbest * T : nullptr, p.n_tokens + (long)b * nbest, p.scores + (long)b * nbest);
 }
-
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-long table_words(int T, int W) {
-    long h = 2;
-    while (h < 2 * (1 + (long)T * W)) h <<= 1;
-    return h;
-}
-bool walk_sizes_ok(int T, int W, int V1) { return 1 + (long)T * W < (1l << 22) - 1 && V1 <= (1 << 20); }
 
 }  // namespace
 

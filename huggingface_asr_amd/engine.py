@@ -368,13 +368,16 @@ class EBranchformerEngine:
         out.update(inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
         return out
 
-    def stream(self, batch: int, chunk_frames: int, max_frames: int):
+    def stream(self, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
         """Streaming inference of a causal model (bf16): -> streaming.EncoderStream for `batch` streams advanced in lock-step, `chunk_frames` encoder frames (4x as many
         feature frames) per `feed`, K/V caches of `max_frames` encoder frames.  Fed an utterance piece by piece it returns forward()'s logits of that utterance alone, each
         frame num_hidden_layers * (merge_conv_kernel - 1) / 2 frames late (csrc/stream.hip; DESIGN.md §4 'Streaming').  Refused before any launch: a non-causal config
-        (ValueError); precision="fp32", layer mixing, an additional layer (NotImplementedError)."""
+        (ValueError); precision="fp32", layer mixing, an additional layer (NotImplementedError).
+        beams=W (1..64): the stream also walks the prefix beam search of transcribe(beams=) over the frames it emits (ops.CtcBeamStream, csrc/ctc_beam_stream.hip): `feed`
+        and `finish` gain a "beam" entry — the committed tokens after every step, the `nbest` hypotheses at `finish` (and per step with feed(..., partial=True)) —, bit
+        for bit what ops.ctc_beam_decode gives on the concatenated logits.  Without beams nothing is allocated and no launch is added."""
         from .streaming import EncoderStream
-        return EncoderStream(self, batch, chunk_frames, max_frames)
+        return EncoderStream(self, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
 
     def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
         """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.

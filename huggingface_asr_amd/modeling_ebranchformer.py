@@ -316,16 +316,17 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
         out = eng.align(input_values, feat_len, labels.to(input_values.device), span=span)
         return CTCAlignment(path=out["path"], score=out["score"], start=out["start"], end=out["end"], token_lp=out["token_lp"], n_tokens=out["tgt_len"])
 
-    def stream(self, batch: int, chunk_frames: int, max_frames: int, device=None):
+    def stream(self, batch: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, token_topk=None, nbest=1):
         """Streaming inference of a causal model (config.is_causal; eval mode only): -> streaming.EncoderStream over this model's weights — `feed` whole chunks of
         4 * chunk_frames feature frames for `batch` streams in lock-step, `finish` the rest; the concatenated logits are forward()'s of each utterance alone, the ids its
-        greedy transcription.  A frame becomes final num_hidden_layers * (merge_conv_kernel - 1) / 2 frames late (DESIGN.md §4 'Streaming')."""
+        greedy transcription.  A frame becomes final num_hidden_layers * (merge_conv_kernel - 1) / 2 frames late (DESIGN.md §4 'Streaming').  beams / token_topk /
+        nbest: the prefix beam search on the stream, as EBranchformerEngine.stream takes them."""
         if self.training:
             raise RuntimeError("stream() is an inference call: put the model in eval mode first (model.eval())")
         dev = device if device is not None else next(self.parameters()).device
         if torch.device(dev).type != "cuda":
             raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
-        return self._get_engine(dev).stream(batch, chunk_frames, max_frames)
+        return self._get_engine(dev).stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
 
     def forward(
         self,

@@ -669,6 +669,119 @@ def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=No
     return out
 
 
+class CtcBeamStream:
+    """CTC prefix beam search on a stream (csrc/ctc_beam_stream.hip states the semantics): ctc_beam_decode's walk for `batch` streams in lock-step, suspended between
+    calls.  After every `feed` the beam is bit for bit the beam ctc_beam_decode holds after the same frames of the concatenated logits, however they were split.
+
+        st = ops.CtcBeamStream(B, max_frames, beams=10, blank=V, pad_id=0)
+        out = st.feed(logits)                      # (B, T_call, V+1) f32|bf16; T_call = 0 is allowed
+        out = st.feed(logits, n_valid, final=True) # the last rows: n_valid (B) of them count per stream
+
+    feed -> dict(committed (B, max_frames) int32, committed_frames (B, max_frames) int32, n_committed (B) int32, n_new (B) int32): the tokens every hypothesis of the beam
+    begins with — they can no longer change —, the frame at which each entered the beam, how many there are and how many this call appended.  These four are the
+    object's own buffers: the next call updates them in place.  With partial=True, and always with final=True, also tokens (B, nbest, max_frames) `dtype`, n_tokens,
+    scores[, frames] as ctc_beam_decode returns them; after final=True committed[:n_committed] is hypothesis 0.  Without them a call does no backtrace.
+    mi_ctc_beam_cut on the call's rows, then mi_ctc_beam_stream_walk: two launches, no host synchronisation.  The object counts T_call per call as the frames walked
+    (an upper bound when n_valid is given: the counts stay on the device) and refuses, before any launch, a call that could pass max_frames."""
+
+    def __init__(self, batch, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False):
+        ints = lambda *v: all(isinstance(x, int) and not isinstance(x, bool) for x in v)
+        if not ints(batch, max_frames, beams, nbest, blank):
+            raise TypeError("CtcBeamStream: batch, max_frames, beams, nbest and blank are ints")
+        if token_topk is not None and not ints(token_topk):
+            raise TypeError("CtcBeamStream: token_topk is an int or None")
+        if batch < 1 or max_frames < 1:
+            raise ValueError(f"CtcBeamStream: at least one stream and one frame, got batch={batch}, max_frames={max_frames}")
+        if not 1 <= beams <= 64:
+            raise ValueError(f"CtcBeamStream: beams must be in 1..64, got {beams}")
+        if not 1 <= nbest <= beams:
+            raise ValueError(f"CtcBeamStream: nbest must be in 1..beams, got {nbest} with {beams} beams")
+        if token_topk is not None and not 1 <= token_topk <= 64:
+            raise ValueError(f"CtcBeamStream: token_topk must be in 1..64, got {token_topk}")
+        if blank < 0:
+            raise ValueError(f"CtcBeamStream: blank {blank} is negative")
+        if dtype not in (torch.int32, torch.int64):
+            raise TypeError("CtcBeamStream: token dtype int32 or int64")
+        self.B, self.max_frames, self.beams, self.token_topk, self.nbest = batch, max_frames, beams, token_topk, nbest
+        self.blank, self.pad_id, self.dtype, self.return_frames = blank, int(pad_id), dtype, bool(return_frames)
+        self.state_bytes = int(_lib.lib().mi_ctc_beam_stream_state_bytes(batch, max_frames, beams))
+        if self.state_bytes == 0:
+            raise ValueError(f"CtcBeamStream: {max_frames} frames x {beams} beams is beyond the node table (max_frames * beams < 2^22 - 2)")
+        self.walked = 0                            # host upper bound of the frames any stream has walked
+        self.finished = False
+        self.V1 = None
+        self._state = None
+
+    def _allocate(self, dev):
+        B, M = self.B, self.max_frames
+        self._state = torch.empty((self.state_bytes,), device=dev, dtype=torch.uint8)
+        self.committed = torch.empty((B, M), device=dev, dtype=torch.int32)
+        self.committed_frames = torch.empty((B, M), device=dev, dtype=torch.int32)
+        self.n_committed = torch.empty((B,), device=dev, dtype=torch.int32)
+        self.n_new = torch.empty((B,), device=dev, dtype=torch.int32)
+        self._reset_device()
+
+    def _reset_device(self):
+        rc = _lib.lib().mi_ctc_beam_stream_reset(self._state.data_ptr(), self.state_bytes, self.B, self.max_frames, self.beams, _stream())
+        _lib.check(rc, "mi_ctc_beam_stream_reset")
+        self.committed.fill_(self.pad_id)
+        self.committed_frames.fill_(-1)
+        self.n_committed.zero_()
+        self.n_new.zero_()
+
+    def reset(self):
+        """every stream back to its start: nothing walked, nothing committed"""
+        self.walked = 0
+        self.finished = False
+        if self._state is not None:
+            self._reset_device()
+
+    def feed(self, logits, n_valid=None, *, final=False, partial=False):
+        if self.finished:
+            raise RuntimeError("CtcBeamStream.feed: the streams are finished (final=True was fed); reset() starts new ones")
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 3 or logits.dtype not in (torch.float32, BF16):
+            raise TypeError("CtcBeamStream.feed: (B, T_call, V+1) fp32 / bf16 logits")
+        B, T, V1 = logits.shape
+        if B != self.B or V1 < 2 or self.blank >= V1 or (self.V1 is not None and V1 != self.V1):
+            raise ValueError(f"CtcBeamStream.feed: logits of ({self.B}, T_call, {self.V1 or 'V+1'}) with blank {self.blank} inside, got {tuple(logits.shape)}")
+        if n_valid is not None and not isinstance(n_valid, torch.Tensor):
+            n_valid = torch.tensor([int(v) for v in n_valid], dtype=torch.int32)
+        if n_valid is not None and tuple(n_valid.shape) != (B,):
+            raise ValueError(f"CtcBeamStream.feed: n_valid: expected shape ({B},), got {tuple(n_valid.shape)}")
+        if self.walked + T > self.max_frames:
+            raise RuntimeError(f"CtcBeamStream.feed: {self.walked} + {T} frames exceed max_frames={self.max_frames}")
+        _req(logits)
+        dev = logits.device
+        if T and logits.stride(2) != 1:
+            logits = logits.contiguous()
+        K = min(self.beams, V1 - 1) if self.token_topk is None else self.token_topk
+        n_valid = _lengths_i32(n_valid, B, dev)
+        if self._state is None:
+            self._allocate(dev)
+        cut = ctc_beam_cut(logits, self.blank, K, n_valid) if T else dict(lse=None, lp_blank=None, lp=None, ids=None)
+        want = bool(final or partial)
+        nb, M = self.nbest, self.max_frames
+        tokens = torch.empty((B, nb, M), device=dev, dtype=self.dtype) if want else None
+        n = torch.empty((B, nb), device=dev, dtype=torch.int32) if want else None
+        scores = torch.empty((B, nb), device=dev, dtype=torch.float32) if want else None
+        frames = torch.empty((B, nb, M), device=dev, dtype=torch.int32) if want and self.return_frames else None
+        rc = _lib.lib().mi_ctc_beam_stream_walk(logits.data_ptr() if T else None, logits.stride(1) if T else 0, logits.stride(0) if T else 0,
+                                                0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(n_valid), self.blank, self.pad_id, self.beams, K, nb,
+                                                _p(cut["lse"]), _p(cut["lp_blank"]), _p(cut["lp"]), _p(cut["ids"]), self._state.data_ptr(), self.state_bytes, M, int(bool(final)),
+                                                self.committed.data_ptr(), self.committed_frames.data_ptr(), self.n_committed.data_ptr(), self.n_new.data_ptr(),
+                                                _p(tokens), int(self.dtype == torch.int64), _p(n), _p(scores), _p(frames), _stream())
+        _lib.check(rc, "mi_ctc_beam_stream_walk")
+        self.V1 = V1
+        self.walked += T
+        self.finished = bool(final)
+        out = dict(committed=self.committed, committed_frames=self.committed_frames, n_committed=self.n_committed, n_new=self.n_new)
+        if want:
+            out.update(tokens=tokens, n_tokens=n, scores=scores)
+            if self.return_frames:
+                out["frames"] = frames
+        return out
+
+
 def ctc_loss(logits, labels, in_len, *, reduction="mean", zero_infinity=False, lse=None):
     """logits (B,T,V+1) f32|bf16 (blank = last class), labels (B,U) int64 (<0 = padding), in_len (B) int32.
     Returns (loss scalar tensor | per-utterance nll for reduction='none', nll (B), tgt_len (B))."""

@@ -7,6 +7,9 @@
 Concatenated over the calls, stream b's logits are those of `engine.forward` on that utterance alone (rounding points of the un-folded layer).  A layer of the
 reference's causal model still looks r = (merge_conv_kernel - 1) / 2 frames ahead (depthwise_conv_fusion keeps its symmetric padding), so frame t becomes final only
 once the front end has produced frame t + L*r: `plan` gives the per-layer row ranges of a step, the device never reports a count back.
+
+    stream = engine.stream(B, C, 1500, beams=10, nbest=4)      # also walks the CTC prefix beam search over the emitted frames (ops.CtcBeamStream)
+    out["beam"]                         # per step: committed / committed_frames (B, max_frames) int32 then -1, n_committed, n_new (B); at finish also the n-best
 """
 from __future__ import annotations
 
@@ -47,7 +50,7 @@ def plan(n_feat: int, C: int, L: int, r: int, finish: bool, n_prev: int | None =
 class EncoderStream:
     """State of B streams advanced in lock-step through a causal encoder + CTC head (mi_ebf_stream_step).  Created by `EBranchformerEngine.stream`."""
 
-    def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int):
+    def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
         c = engine.cfg
         if not c.get("is_causal", False):
             raise ValueError("stream(): the model is not causal (is_causal=False): its layers see the whole utterance, there is nothing to stream")
@@ -72,6 +75,13 @@ class EncoderStream:
         self.finished = False
         self._state = None
         self._cs = None
+        self.beam = None                                # beams=W: the prefix beam search walks the emitted frames too (ops.CtcBeamStream)
+        if beams is not None:
+            from . import ops
+            self.beam = ops.CtcBeamStream(self.B, self.max_frames, beams=beams, token_topk=token_topk, nbest=nbest, blank=c["vocab_size"], pad_id=-1, dtype=torch.int32,
+                                          return_frames=True)
+        elif token_topk is not None or nbest != 1:
+            raise ValueError("stream(): token_topk and nbest belong to beams=")
 
     # ------------------------------------------------------------------ state
     def state_bytes(self) -> int:
@@ -118,9 +128,11 @@ class EncoderStream:
         self.finished = False
         if self._state is not None:
             self._reset_device()
+        if self.beam is not None:
+            self.beam.reset()
 
     # ------------------------------------------------------------------ steps
-    def _step(self, feats, n_now, finish, ends):
+    def _step(self, feats, n_now, finish, ends, partial=False):
         rows = plan(n_now, self.C, self.L, self.r, finish, n_prev=self.n_feat)
         if rows[0][1] > self.max_frames:
             raise RuntimeError(f"EncoderStream: {rows[0][1]} encoder frames exceed max_frames={self.max_frames}")
@@ -140,25 +152,33 @@ class EncoderStream:
         rc = _lib.lib().mi_ebf_stream_step(C.byref(cs), e._table, self.C, self.max_frames, p(self._pos), self._state.data_ptr(), self._state.numel(), feats.data_ptr(),
                                            flat, p(ends), p(lbuf), p(best), p(ids), p(n_ids), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "mi_ebf_stream_step")
+        out = dict(logits=lbuf[..., :V1], n_out=n_out, total=self.total + n_out, ids=ids, n_ids=n_ids, best=best, rows=rows)
+        if self.beam is not None:                       # the step's fp32 logits as they lie in the padded buffer; in finish, rows past a stream's end do not count
+            out["beam"] = self.beam.feed(out["logits"], None if ends is None else ends - self.total, final=finish, partial=partial)
         self.n_feat = n_now
         self.total += n_out
-        return dict(logits=lbuf[..., :V1], n_out=n_out, total=self.total, ids=ids, n_ids=n_ids, best=best, rows=rows)
+        return out
 
     def _check_open(self, what):
         if self.finished:
             raise RuntimeError(f"EncoderStream.{what}: the streams are finished; reset() starts new ones")
 
-    def feed(self, feats: torch.Tensor) -> dict:
-        """one whole chunk: feats (B, 4*C, F) fp32 -> the frames that became final: dict(logits (B, n_out, V+1) fp32, n_out, total, ids, n_ids, best)"""
+    def feed(self, feats: torch.Tensor, *, partial: bool = False) -> dict:
+        """one whole chunk: feats (B, 4*C, F) fp32 -> the frames that became final: dict(logits (B, n_out, V+1) fp32, n_out, total, ids, n_ids, best).  A stream created
+        with beams= adds "beam": ops.CtcBeamStream.feed's dict over these frames — the committed tokens (pad -1) and counts, with partial=True also the n-best so far."""
         self._check_open("feed")
+        if partial and self.beam is None:
+            raise ValueError("EncoderStream.feed: partial=True asks for the beam search's n-best: create the stream with beams=")
         want = (self.B, SUBSAMPLING * self.C, self.F)
         if tuple(feats.shape) != want:
             raise ValueError(f"EncoderStream.feed: a chunk is {want} (batch, 4 * chunk_frames, features), got {tuple(feats.shape)}; the last, shorter piece goes to finish()")
-        return self._step(feats.to(torch.float32).contiguous(), self.n_feat + SUBSAMPLING * self.C, False, None)
+        return self._step(feats.to(torch.float32).contiguous(), self.n_feat + SUBSAMPLING * self.C, False, None, partial)
 
     def finish(self, tail: torch.Tensor | None = None, tail_lengths=None) -> dict:
         """the last 0 .. 4*C frames of every stream (tail (B, n, F), n <= 4*C; tail_lengths (B): valid frames of each stream, default n) and the flush: every frame
-        still inside the lookahead becomes final.  Adds n_valid (B): how many of the n_out rows are frames of stream b, and totals (B) = out_frames(frames of stream b)."""
+        still inside the lookahead becomes final.  Adds n_valid (B): how many of the n_out rows are frames of stream b, and totals (B) = out_frames(frames of stream b).
+        With beams=, "beam" holds the full n-best of every stream (tokens (B, nbest, max_frames) int32 then -1, n_tokens, scores, frames) and its committed buffers, which
+        now equal hypothesis 0."""
         self._check_open("finish")
         B, W = self.B, SUBSAMPLING * self.C
         n = 0 if tail is None else int(tail.shape[1])

@@ -274,6 +274,27 @@ int mi_ctc_beam_cut(const void* logits, long ld_row, long ld_batch, int dtype, i
 int mi_ctc_beam_walk(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, long pad_id, int W, int K, int nbest,
                      const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* workspace, size_t workspace_bytes, void* tokens,
                      int tokens_dtype, int* n_tokens, float* scores, int* frames, mi_stream_t stream);
+/* ---- CTC prefix beam search on a stream (csrc/ctc_beam_stream.hip, whose header states the semantics): the walk above suspended between calls.  After every call the
+ * beam is bit for bit the beam mi_ctc_beam_walk holds after the same number of frames of the concatenated logits, for every partition of the frames into calls.
+ * mi_ctc_beam_stream_state_bytes: bytes of the state of B streams of at most max_frames frames with W hypotheses: per stream a 16-word header, the beam (7 x 64 words),
+ * the node arena (1 + max_frames W nodes of 16 B) and the node table (the power of two >= 2 (1 + max_frames W) 64-bit words).  Host arithmetic; 0 for arguments the
+ * walk refuses.
+ * mi_ctc_beam_stream_reset: every stream back to its start (the empty hypothesis, score 0; nothing walked, nothing committed; the node table zeroed — the walk never
+ * clears it).  state: 16-B aligned, state_bytes >= the above.
+ * mi_ctc_beam_stream_walk: walks the n_valid[b] (clamped to [0, T_call]; T_call when null) first rows of this call's logits (B, T_call, V1) (dtype, strides, blank, W,
+ * K as mi_ctc_beam_walk; lse / lp_blank / cut_lp / cut_id: mi_ctc_beam_cut's tables for THESE rows).  T_call = 0 is a call without frames (logits and tables may be
+ * null).  A stream never walks past max_frames frames.  Then the committed prefix — the longest common prefix of all hypotheses of the beam; with final = 1 the whole
+ * best hypothesis — is appended to committed / committed_frames (B, max_frames) int32 (token, and the frame at which its prefix entered the beam); n_committed (B) its
+ * length, n_new (B) the tokens this call appended.  tokens not null (required with final = 1): the nbest best as mi_ctc_beam_walk writes them, rows max_frames wide
+ * (tokens (B, nbest, max_frames), n_tokens, scores (B, nbest), frames nullable); null: no backtrace.  No float atomics: bit-identical run to run; a stream's result
+ * does not depend on the rest of the batch.  MI_ERR_ARG before any launch as mi_ctc_beam_walk, and for final outside {0, 1}, final without tokens, a state that is too
+ * small or not 16-B aligned; MI_ERR_UNSUPPORTED: V1 > 2^20 or max_frames W >= 2^22 - 2. */
+size_t mi_ctc_beam_stream_state_bytes(int B, int max_frames, int W);
+int mi_ctc_beam_stream_reset(void* state, size_t state_bytes, int B, int max_frames, int W, mi_stream_t stream);
+int mi_ctc_beam_stream_walk(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T_call, int V1, const int* n_valid, int blank, long pad_id, int W, int K,
+                            int nbest, const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* state, size_t state_bytes, int max_frames,
+                            int final, int* committed, int* committed_frames, int* n_committed, int* n_new, void* tokens, int tokens_dtype, int* n_tokens,
+                            float* scores, int* frames, mi_stream_t stream);
 /* ---- CTC forced alignment (csrc/ctc_align.hip, whose header states the exact semantics): the best (Viterbi) path of a given transcript, one launch, one block per
  * utterance.  Arguments as mi_ctc_loss_fwd: logits (B, T, V1) fp32 (dtype 0) / bf16 (1) with element strides (ld_b, ld_t), lse (B*T) the rows' log-sum-exp, labels
  * (B, U) int64 (negative entries are padding wherever they stand), in_len (B) int32 clamped to [0, T].  Out: path (B, T) int32 = the class of every frame t < n_b on
