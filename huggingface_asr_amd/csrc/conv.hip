@@ -366,18 +366,28 @@ __global__ __launch_bounds__(256) void dwconv_time_kernel(DwArgs p) {
 }
 
 // Fast form for the reference's kernel size 31, dilation 1.  A block owns 64 channels x 64 time steps (4 blocks per CU; 128 steps at 2 per CU was 1 % slower end to end): the (64+30) x 64
-// input tile (16-B global loads, LayerNorm applied on the way in), the gate operand x_r and the result tile all live in
-// LDS, every thread keeps a 46-sample window + the 31 taps of its channel in registers and produces 16 consecutive
-// outputs (77 LDS reads per 496 FMAs), and the result leaves as 16-B-per-lane rows.
+// input tile (16-B global loads, LayerNorm applied on the way in) and the block's 64 x 31 taps live in LDS (32 000 B: 5 blocks per CU),
+// every thread keeps a 46-sample window + the 31 taps of its channel in registers and produces 16 consecutive
+// outputs (77 LDS reads per 496 FMAs), and the result leaves as 16-B-per-lane rows.  The kernels are bound by the instructions a wave
+// issues per tile (profiles/r08_a, r08_b), so nothing but the FMAs sits between the first and the last tap, no LDS access is narrower
+// than 4 bytes, and the gate operand x_r stays in the registers of the thread that loaded it.
 constexpr int DWF_K = 31, DWF_TT = 64, DWF_CT = 64, DWF_ROWS = DWF_TT + DWF_K - 1, DWF_PER = DWF_TT / 4;
-constexpr int DWF_WS = DWF_CT + 1, DWF_WBUF = (DWF_K * DWF_WS + 3) / 4 * 4;     // weight rows padded to 65 floats; buffer rounded so `io` stays 16-B aligned
 
-template <bool CSGU>
+// ACT is the CSGU activation (DwArgs::act) as a template parameter: the 16 x 31 FMA body is straight-line code and an instance carries only its own activation.
+template <int ACT>
+__device__ __forceinline__ float dw_act(float v) {
+    if (ACT == 1) return gelu_erf(v);
+    if (ACT == 2) return fmaxf(v, 0.f);
+    if (ACT == 3) return v / (1.f + __expf(-v));
+    return v;
+}
+
+template <bool CSGU, int ACT>
 __global__ __launch_bounds__(256) void dwconv31_kernel(DwArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* tile = reinterpret_cast<float*>(smem);                          // [DWF_ROWS][64] fp32
-    float* sw = tile + DWF_ROWS * DWF_CT;                                  // [31][DWF_WS]: tap-major, row stride 65 (conflict-free transposed fill)
-    bf16_t* io = reinterpret_cast<bf16_t*>(sw + DWF_WBUF);                 // [128][64] bf16: x_r in, result out
+    float* sw = tile + DWF_ROWS * DWF_CT;                                  // [64][31]: the slab as it lies in memory.  The fill is a linear copy (no index arithmetic) and the
+                                                                           // tap phase reads with a lane stride of 31 words: odd, so the 32 lanes of a half wave hit 32 banks
     const int c0 = blockIdx.x * DWF_CT, t0 = blockIdx.y * DWF_TT, b = blockIdx.z;
     const int tid = threadIdx.x;
     // the block's 64 x 31 taps are one contiguous run of the (C, 31) weight: read it linearly (coalesced), all passes in flight together
@@ -385,8 +395,8 @@ __global__ __launch_bounds__(256) void dwconv31_kernel(DwArgs p) {
     float wv[NPW];
 #pragma unroll
     for (int q = 0; q < NPW; ++q) wv[q] = p.w[(long)c0 * DWF_K + min(tid + q * 256, DWF_K * DWF_CT - 1)];
-    // Fill: every global load of the block (5 passes of the conv input, their row statistics, 4 passes of the gate operand, the LayerNorm
-    // affine) is issued before the first one is consumed — one memory round trip per block instead of one per pass; the block has only
+    // Fill: every global load of the block (the passes of the conv input, their row statistics, the passes of the gate operand, the LayerNorm
+    // affine, the bias) is issued before the first one is consumed — one memory round trip per block instead of one per pass; the block has only
     // one or two companions on its CU, so a pass-by-pass load -> wait -> ds_write loop leaves the memory pipe idle most of the time.
     constexpr int NPI = (DWF_ROWS * (DWF_CT / 8) + 255) / 256, NPO = DWF_TT * (DWF_CT / 8) / 256;
     const int ch = tid & 7;                                                // 256 % 8 == 0: a thread keeps its 16-B channel chunk in every pass
@@ -413,11 +423,13 @@ __global__ __launch_bounds__(256) void dwconv31_kernel(DwArgs p) {
             vio[q] = *reinterpret_cast<const bf16x8*>(p.mul + ((long)b * p.T + min(t, p.T - 1)) * p.ld_mul + c0 + ch * 8);   // rows past T: never stored
         }
     }
+    const int tx = tid & 63, ty = tid >> 6;                                // the tap phase's mapping: channel, group of 16 time steps
+    const float bias = p.bias ? p.bias[c0 + tx] : 0.f;                     // with the other loads: no memory round trip between the fill and the taps
     __builtin_amdgcn_sched_barrier(0);                                     // keep the loads above in front of their uses below
 #pragma unroll
     for (int q = 0; q < NPW; ++q) {
         const int i = tid + q * 256;
-        if (i < DWF_K * DWF_CT) sw[(i % DWF_K) * DWF_WS + i / DWF_K] = wv[q];
+        if (i < DWF_K * DWF_CT) sw[i] = wv[q];
     }
 #pragma unroll
     for (int q = 0; q < NPI; ++q) {
@@ -440,46 +452,38 @@ __global__ __launch_bounds__(256) void dwconv31_kernel(DwArgs p) {
             *reinterpret_cast<f32x4*>(tile + r * DWF_CT + ch * 8 + 4) = hi;
         }
     }
-    if (CSGU) {
-#pragma unroll
-        for (int q = 0; q < NPO; ++q) {
-            const int r = (tid + q * 256) >> 3;
-            *reinterpret_cast<bf16x8*>(io + r * DWF_CT + ch * 8) = vio[q];
-        }
-    }
     __syncthreads();
-    const int tx = tid & 63, ty = tid >> 6;
-    const int c = c0 + tx;
     float wk[DWF_K];
 #pragma unroll
-    for (int k = 0; k < DWF_K; ++k) wk[k] = sw[k * DWF_WS + tx];
+    for (int k = 0; k < DWF_K; ++k) wk[k] = sw[tx * DWF_K + k];
     float win[DWF_PER + DWF_K - 1];
 #pragma unroll
     for (int i = 0; i < DWF_PER + DWF_K - 1; ++i) win[i] = tile[(ty * DWF_PER + i) * DWF_CT + tx];
-    const float bias = p.bias ? p.bias[c] : 0.f;
+    float res[DWF_PER];                                                    // fp32: act(conv + bias) (CSGU) or centre + conv + bias (MERGE)
 #pragma unroll
     for (int j = 0; j < DWF_PER; ++j) {
         float acc = bias;
 #pragma unroll
         for (int k = 0; k < DWF_K; ++k) acc = fmaf(wk[k], win[j + k], acc);
-        const int rl = ty * DWF_PER + j;
-        float o;
-        if (CSGU) {
-            if (p.act == 1) acc = gelu_erf(acc);
-            else if (p.act == 2) acc = fmaxf(acc, 0.f);
-            else if (p.act == 3) acc = acc / (1.f + __expf(-acc));
-            o = bf2f(io[rl * DWF_CT + tx]) * acc;
-        } else {
-            o = win[j + (DWF_K - 1) / 2] + acc;
-        }
-        io[rl * DWF_CT + tx] = f2bf(o);
+        res[j] = CSGU ? dw_act<ACT>(acc) : win[j + (DWF_K - 1) / 2] + acc;
     }
+    // The results change mapping, (channel, 16 time steps) -> (row, 8-channel chunk), through rows 0 .. 63 of the input tile as fp32 (4-byte stores, 16-byte loads):
+    // every wave has consumed its window by now, and the thread that stores (row, chunk) is the one that loaded x_r for it at the fill and still holds it.
     __syncthreads();
-    for (int id = tid; id < DWF_TT * (DWF_CT / 8); id += 256) {
-        const int r = id >> 3, ch = id & 7;
-        const int t = t0 + r;
-        if (t < p.T)
-            *reinterpret_cast<bf16x8*>(p.out + ((long)b * p.T + t) * p.ld_out + c0 + ch * 8) = *reinterpret_cast<const bf16x8*>(io + r * DWF_CT + ch * 8);
+#pragma unroll
+    for (int j = 0; j < DWF_PER; ++j) tile[(ty * DWF_PER + j) * DWF_CT + tx] = res[j];
+    __syncthreads();
+    int id0 = tid;
+    asm volatile("" : "+v"(id0));                                          // the store addresses are worked out here, not held in registers across the taps
+#pragma unroll
+    for (int q = 0; q < NPO; ++q) {
+        const int r = (id0 + q * 256) >> 3, ch = id0 & 7, t = t0 + r;
+        const f32x4 lo = *reinterpret_cast<const f32x4*>(tile + r * DWF_CT + ch * 8), hi = *reinterpret_cast<const f32x4*>(tile + r * DWF_CT + ch * 8 + 4);
+        const float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = f2bf(CSGU ? bf2f(vio[q][j]) * v[j] : v[j]);
+        if (t < p.T) *reinterpret_cast<bf16x8*>(p.out + ((long)b * p.T + t) * p.ld_out + c0 + ch * 8) = o;
     }
 }
 
@@ -583,9 +587,12 @@ static int dw_launch(const DwArgs& a, bool csgu, hipStream_t stream) {
                       (!csgu || ((a.ld_mul % 8) == 0 && (((uintptr_t)a.mul) & 15) == 0)) && (!csgu || (((uintptr_t)a.gamma | (uintptr_t)a.beta) & 15) == 0);
     if (fast) {
         dim3 gridf(a.C / DWF_CT, cdiv(a.T, DWF_TT), a.B);
-        const size_t ldsf = (size_t)(DWF_ROWS * DWF_CT + DWF_WBUF) * sizeof(float) + (size_t)DWF_TT * DWF_CT * sizeof(bf16_t);
-        if (csgu) hipLaunchKernelGGL(dwconv31_kernel<true>, gridf, dim3(256), ldsf, stream, a);
-        else hipLaunchKernelGGL(dwconv31_kernel<false>, gridf, dim3(256), ldsf, stream, a);
+        const size_t ldsf = (size_t)(DWF_ROWS * DWF_CT + DWF_K * DWF_CT) * sizeof(float);
+        if (!csgu) hipLaunchKernelGGL((dwconv31_kernel<false, 0>), gridf, dim3(256), ldsf, stream, a);
+        else if (a.act == 1) hipLaunchKernelGGL((dwconv31_kernel<true, 1>), gridf, dim3(256), ldsf, stream, a);
+        else if (a.act == 2) hipLaunchKernelGGL((dwconv31_kernel<true, 2>), gridf, dim3(256), ldsf, stream, a);
+        else if (a.act == 3) hipLaunchKernelGGL((dwconv31_kernel<true, 3>), gridf, dim3(256), ldsf, stream, a);
+        else hipLaunchKernelGGL((dwconv31_kernel<true, 0>), gridf, dim3(256), ldsf, stream, a);      // any other value: identity, as dwconv_time_kernel reads it
         MI_CHECK_LAUNCH();
         return MI_OK;
     }
