@@ -223,6 +223,16 @@ SIGNATURES = {
     "mi_ebf_stream_state_bytes": [C.POINTER(EbfConfig), i32, i32],
     "mi_ebf_stream_reset": [C.POINTER(EbfConfig), vp, i32, i32, vp, vp, sz, vp],
     "mi_ebf_stream_step": [C.POINTER(EbfConfig), vp, i32, i32, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp],
+    # streaming session pool: the per-slot forms (csrc/stream_pool.hip)
+    "mi_copy_rows_slots": [vp, i64, i64, i32, i32, vp, i64, i64, i32, i32, vp, vp, i32, i32, vp],
+    "mi_attention_chunk_slots_bf16": [vp, i64, vp, i64, vp, i64, i64, i32, i32, vp, i64, vp, vp, vp, i64, vp, vp, i32, i32, i32, f32, i32, vp],
+    "mi_dwconv_stream_slots_bf16": [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp, vp] + [i32] * 8 + [vp],
+    "mi_rotary_slots_bf16": [vp, i64, vp, i64, vp, vp, i32, vp, vp, i32, i32, i32, vp],
+    "mi_ctc_collapse_slots": [vp, i32, vp, i32, vp, vp, vp, vp, i32, vp],
+    "mi_ebf_stream_slot_pieces": [C.POINTER(EbfConfig), i32, i32, vp, i32],
+    "mi_ebf_stream_reset_slot": [C.POINTER(EbfConfig), i32, i32, vp, sz, i32, vp],
+    "mi_ebf_stream_slots_table": [C.POINTER(EbfConfig), i32, i32, vp, i32, vp, i32],
+    "mi_ebf_stream_step_slots": [C.POINTER(EbfConfig), vp, i32, i32, vp, vp, sz, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
     # two-pass joint decoding (csrc/rescore.hip)
     "mi_rescore_pack": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp],
     "mi_rows_nll_f32": [vp, i64, vp, vp, i32, vp, i32, vp],

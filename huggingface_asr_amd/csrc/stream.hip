@@ -5,7 +5,7 @@
 // Semantics (normative)
 //  * A stream batch is B streams advanced in lock-step.  A step takes (B, 4*C, F) fp32 feature frames; C = the chunk size in encoder frames, fixed when the state is
 //    created, 4 = the product of the conv strides.  The last step (`finish`) takes 0 .. 4*C valid frames per stream (the rest zero) and flushes.  A stream may end only
-//    inside that last step; independent start / end times per slot are out of scope.
+//    inside that last step; slots that start, idle and end on their own are the session pool's (stream_pool.hip: the same state, per-slot forms of the kernels below).
 //  * After n feature frames the front end has produced a_0 = out_frames(n) frames; n = 4k gives k (causal geometry: conv1 frame i reads input 2i-2 .. 2i, conv2 the
 //    same over conv1).  State: the last two input frames and the last two conv1 output frames per stream, zero at stream start — a zero history is exactly the left
 //    padding of CausalConv2d (streaming_modules.py:31-55).
@@ -29,11 +29,9 @@
 //  * A step returns logits (B, n_out, V+1) for the newly final frames and the CTC greedy tokens newly emitted (the collapse carries the last class across steps).
 //    Row counts come from the caller's plan (host): `rows` holds (lo, hi) of every layer's input and of the emitted rows; no host round trip inside a step.
 //  * No atomics; a stream's result does not depend on the rest of the batch (every kernel here works per stream, the GEMMs per row).
-#include "ebf_layout.hpp"
+#include "stream_common.hpp"
 
 namespace {
-
-constexpr float LEPS = 1e-5f;      // nn.LayerNorm default of the layers (encoder.hip)
 
 // ------------------------------------------------------------------------------------------------ rows between compact buffers, caches and rings
 // dst[b][(dst_row0 + i) % dst_mod][:W] = src[b][(src_row0 + i) % src_mod][:W] for i < n (mod 0: no wrap); W, the row strides (ld) and batch strides (bs) in 4-byte words
@@ -66,304 +64,46 @@ int copy_rows(const void* src, long src_bs, int src_row0, int src_mod, void* dst
     return copy_rows_ld(src, src_bs, W, src_row0, src_mod, dst, dst_bs, W, dst_row0, dst_mod, n, W, B, st);
 }
 
-// ------------------------------------------------------------------------------------------------ chunk attention
-// One wave per (stream, head, query); a block holds four consecutive queries.  Query i of the n_q new rows stands at absolute frame n_k - n_q + i and sees keys
-// j <= that frame of the (B, Lmax, .) cache.  Scores in fp32 over bf16 operands ((q + u), (q + v) rounded to bf16 as the full kernels' A operands are); the
-// un-normalised probabilities are rounded to bf16 for the PV product and the normaliser is summed from the un-rounded ones, as in the full kernels.  Those kernels
-// walk the keys in tiles of 32 and exponentiate against a running reference m (any m gives the same quotient, but bf16(2^(s - m)) depends on it), so the rounding of a
-// probability depends on the walk.  `ref` selects whose walk the rounding follows, which is what keeps a streamed layer closest to the full forward's:
-//   0  one reference, the row maximum (no tiling)
-//   1  attn_kernel's (mi_attention_bf16, head size 16): m = the maximum of all tiles so far, natural-log domain
-//   2  attn_lds_kernel's (four waves; head size 64 with relative positions): exp2 domain, m moves to max(m, tile maximum) only when that exceeds m + 11
-//   3  attn8_kernel's (eight waves; every other 64 / 128 case): as 2, but the even and the odd tiles are two walks with a reference each
-// (the full kernels move m for all 32 queries of a wave when one of them asks; that coupling between queries is not reproduced.)
-struct AttnArgs {
-    const bf16_t* q; long ldq;
-    const bf16_t* k; const bf16_t* v; long ldkv, kv_bs;
-    const bf16_t* pos; long ldp;             // (>= n_k, .) projected sinusoids by distance, or null
-    const float* u; const float* vb;
-    bf16_t* out; long ldo;
-    int n_q, n_k, H, nkp, ntp, ref;          // nkp: n_k rounded up to 4 (a wave's score row); ntp: tiles of 32 keys + 1, rounded up to 4
-    float scale;
-};
-
-template <int HD>
-__device__ __forceinline__ float dot_row(const float* __restrict__ a, const bf16_t* __restrict__ row) {
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < HD; c += 8) {
-        const bf16x8 kv = *reinterpret_cast<const bf16x8*>(row + c);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s = fmaf(a[c + e], bf2f(kv[e]), s);
-    }
-    return s;
-}
-
+// ------------------------------------------------------------------------------------------------ the lock-step forms of the shared bodies (stream_common.hpp)
+// chunk attention: one wave per (stream, head, query); a block holds four consecutive queries.  Query i of the n_q new rows stands at absolute frame n_k - n_q + i.
 template <int HD>
 __global__ __launch_bounds__(256) void attn_chunk_kernel(AttnArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float* sc = reinterpret_cast<float*>(smem) + (size_t)wave * (p.nkp + 2 * HD + 2 * p.ntp);
-    float* qu = sc + p.nkp;
-    float* qv = qu + HD;
-    float* tm = qv + HD;                       // tile maxima
-    float* mr = tm + p.ntp;                    // the reference each tile is exponentiated against; [ntile] = the largest of them
     const int h = blockIdx.y, b = blockIdx.z;
     const int iq = blockIdx.x * 4 + wave;
     const bool live = iq < p.n_q;
     const int i = live ? iq : p.n_q - 1;
     const bf16_t* qrow = p.q + ((long)b * p.n_q + i) * p.ldq + h * HD;
-    for (int c = lane; c < HD; c += 64) {
-        const float qf = bf2f(qrow[c]);
-        qu[c] = p.pos ? bf2f(f2bf(qf + p.u[h * HD + c])) : qf;
-        qv[c] = p.pos ? bf2f(f2bf(qf + p.vb[h * HD + c])) : 0.f;
-    }
-    __syncthreads();
     const int ia = p.n_k - p.n_q + i;          // absolute frame of the query = index of its last key
-    const int nkeys = ia + 1;
-    const bf16_t* kb = p.k + (long)b * p.kv_bs + h * HD;
-    const bf16_t* vbp = p.v + (long)b * p.kv_bs + h * HD;
-    const bool e2 = p.ref >= 2;                // exp2 domain: the score carries scale * log2(e)
-    const float sc2 = e2 ? p.scale * 1.4426950408889634f : p.scale;
-    for (int j = lane; j < nkeys; j += 64) {
-        float s = dot_row<HD>(qu, kb + (long)j * p.ldkv);
-        if (p.pos) s += dot_row<HD>(qv, p.pos + (long)(ia - j) * p.ldp + h * HD);
-        sc[j] = s * sc2;
-    }
-    __syncthreads();
-    const int ntile = (nkeys + 31) >> 5;
-    for (int t = lane; t < ntile; t += 64) {
-        float mx = -INFINITY;
-        const int je = min(32 * t + 32, nkeys);
-        for (int j = 32 * t; j < je; ++j) mx = fmaxf(mx, sc[j]);
-        tm[t] = mx;
-    }
-    __syncthreads();
-    if (lane == 0) {                           // the walk(s) over the tiles: a few dozen steps
-        float m0 = -1e30f, m1 = -1e30f, top = -1e30f;
-        if (p.ref == 0)
-            for (int t = 0; t < ntile; ++t) m0 = fmaxf(m0, tm[t]);
-        for (int t = 0; t < ntile; ++t) {
-            float& m = (p.ref == 3 && (t & 1)) ? m1 : m0;
-            if (p.ref == 1) m = fmaxf(m, tm[t]);
-            else if (p.ref >= 2 && tm[t] > m + 11.f) m = fmaxf(m, tm[t]);
-            mr[t] = m;
-            top = fmaxf(top, m);
-        }
-        mr[ntile] = top;
-    }
-    __syncthreads();
-    const float top = mr[ntile];
-    float l = 0.f;
-    for (int j = lane; j < nkeys; j += 64) {
-        const float m = mr[j >> 5];
-        float e, w;
-        if (e2) { e = __builtin_amdgcn_exp2f(sc[j] - m); w = __builtin_amdgcn_exp2f(m - top); }
-        else if (p.ref == 1) { e = __expf(sc[j] - m); w = __expf(m - top); }
-        else { e = expf(sc[j] - m); w = 1.f; }
-        l += e * w;                            // the walk's accumulators are rescaled in fp32 when its reference moves: the weight of an older tile
-        sc[j] = bf2f(f2bf(e)) * w;
-    }
-    l = wave_sum(l);
-    __syncthreads();
-    // PV: a group of LPG lanes owns the head's columns (DPL per lane), the 64 / LPG groups split the keys and are folded in a fixed order
-    constexpr int DPL = HD > 64 ? HD / 64 : 1, LPG = HD / DPL, G = 64 / LPG;
-    const int g = lane / LPG, cl = lane % LPG;
-    float acc[DPL];
-#pragma unroll
-    for (int e = 0; e < DPL; ++e) acc[e] = 0.f;
-    for (int j = g; j < nkeys; j += G) {
-        const float pj = sc[j];
-        const bf16_t* vr = vbp + (long)j * p.ldkv;
-#pragma unroll
-        for (int e = 0; e < DPL; ++e) acc[e] = fmaf(pj, bf2f(vr[cl + e * LPG]), acc[e]);
-    }
-#pragma unroll
-    for (int o = LPG; o < 64; o <<= 1)
-#pragma unroll
-        for (int e = 0; e < DPL; ++e) acc[e] += __shfl_xor(acc[e], o, 64);
-    if (live && g == 0) {
-        bf16_t* orow = p.out + ((long)b * p.n_q + iq) * p.ldo + h * HD;
-#pragma unroll
-        for (int e = 0; e < DPL; ++e) orow[cl + e * LPG] = f2bf(acc[e] / l);
-    }
+    bf16_t* orow = live ? p.out + ((long)b * p.n_q + iq) * p.ldo + h * HD : nullptr;
+    attn_chunk_row<HD>(p, sc, qrow, p.k + (long)b * p.kv_bs + h * HD, p.v + (long)b * p.kv_bs + h * HD, ia, orow, h, lane);
 }
 
-// ------------------------------------------------------------------------------------------------ stateful depthwise conv over time
-// A block owns 64 channels of one stream for ALL rows of the call (a depthwise conv never mixes channels), so it may read its slice of the ring, compute, and — after
-// a block barrier — overwrite that slice with the call's last rows: no other block reads or writes those channels.  The ring holds rows [p - Hr, p) at slot t % Hr.
-// mode 0 CSGU: out = x_r * act(bias + sum_k w_k LN(x_g)[t - left + k dil]),  LN from the given (mean, rstd) of each row and gamma / beta; the ring keeps the raw rows
-//              and a per-channel-tile copy of their statistics.      mode 2 conv-only: the same without act and gate (csgu_use_linear_after_conv).
-// mode 1 MERGE: out = m[t] + bias + sum_k w_k m[t - left + k],  rows at or beyond end[b] (when given) and rows not yet fed count as zero.
-// The sum runs from the bias through the taps k = 0 .. K-1 in order, as dwconv_time_kernel's (conv.hip).
-struct DwsArgs {
-    const bf16_t* in; long ld_in;            // the call's new rows [p, p + n_new), compact (B, n_new, .)
-    const bf16_t* mul; long ld_mul;          // CSGU: x_r of the output rows
-    const float* stats;                      // CSGU / conv-only: (B * n_new, 2)
-    const float* gamma; const float* beta; const float* w; const float* bias;
-    bf16_t* ring; float* ring_stats;         // (B, Hr, C) ; (B, ceil(C / 64), Hr, 2)
-    const int* end;                          // (B) or null
-    bf16_t* out; long ld_out;                // rows [o0, o0 + n_out), compact (B, n_out, .)
-    int B, C, K, dil, left, Hr, p, n_new, o0, n_out, mode, act;
-};
-
+// stateful depthwise conv: a block owns 64 channels of one stream; every stream of the batch stands at the same p
 __global__ __launch_bounds__(256) void dwconv_stream_kernel(DwsArgs a) {
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int b = blockIdx.y, ct = blockIdx.x, c = ct * 64 + tx;
-    const bool cok = c < a.C;
+    const int b = blockIdx.y, ct = blockIdx.x;
     const bool ln = a.mode != 1;
-    const int endb = a.end ? a.end[b] : 0x7fffffff;
-    const int hi = a.p + a.n_new;
-    const bf16_t* nin = a.in + (long)b * a.n_new * a.ld_in;
-    const float* nst = ln ? a.stats + (long)b * a.n_new * 2 : nullptr;
-    bf16_t* ring = a.ring + (long)b * a.Hr * a.C;
-    float* rst = ln ? a.ring_stats + ((long)b * gridDim.x + ct) * a.Hr * 2 : nullptr;
-    float g = 1.f, be = 0.f, bias = 0.f;
-    if (cok) {
-        if (ln) { g = a.gamma[c]; be = a.beta[c]; }
-        if (a.bias) bias = a.bias[c];
-    }
-    auto fetch = [&](int t) -> float {
-        if (t < 0 || t >= hi || t >= endb || t < a.p - a.Hr) return 0.f;       // zero padding is applied to the conv INPUT (post-LN)
-        float v, mean, rstd;
-        if (t >= a.p) {
-            v = bf2f(nin[(long)(t - a.p) * a.ld_in + c]);
-            if (ln) { mean = nst[2 * (t - a.p)]; rstd = nst[2 * (t - a.p) + 1]; }
-        } else {
-            const int s = t % a.Hr;
-            v = bf2f(ring[(long)s * a.C + c]);
-            if (ln) { mean = rst[2 * s]; rstd = rst[2 * s + 1]; }
-        }
-        return ln ? (v - mean) * rstd * g + be : v;
-    };
-    if (cok) {
-        const float* wc = a.w + (long)c * a.K;
-        for (int j = ty; j < a.n_out; j += 4) {
-            const int t = a.o0 + j;
-            float acc = bias;
-            for (int k = 0; k < a.K; ++k) acc = fmaf(wc[k], fetch(t - a.left + k * a.dil), acc);
-            const long orow = (long)b * a.n_out + j;
-            float o;
-            if (a.mode == 1) {
-                o = fetch(t) + acc;
-            } else if (a.mode == 0) {
-                if (a.act == 1) acc = gelu_erf(acc);
-                else if (a.act == 2) acc = fmaxf(acc, 0.f);
-                else if (a.act == 3) acc = acc / (1.f + __expf(-acc));
-                o = bf2f(a.mul[orow * a.ld_mul + c]) * acc;
-            } else {
-                o = acc;
-            }
-            a.out[orow * a.ld_out + c] = f2bf(o);
-        }
-    }
-    __syncthreads();
-    // advance the ring: the last min(n_new, Hr) rows of the call
-    const int t0 = a.n_new > a.Hr ? hi - a.Hr : a.p;
-    for (int t = t0 + ty; t < hi; t += 4) {
-        const int s = t % a.Hr;
-        if (cok) ring[(long)s * a.C + c] = nin[(long)(t - a.p) * a.ld_in + c];
-        if (ln && tx < 2) rst[2 * s + tx] = nst[2 * (t - a.p) + tx];
-    }
+    DwsStream s;
+    s.nin = a.in + (long)b * a.n_new * a.ld_in;
+    s.nst = ln ? a.stats + (long)b * a.n_new * 2 : nullptr;
+    s.ring = a.ring + (long)b * a.Hr * a.C;
+    s.rst = ln ? a.ring_stats + ((long)b * gridDim.x + ct) * a.Hr * 2 : nullptr;
+    s.mul = a.mul ? a.mul + (long)b * a.n_out * a.ld_mul : nullptr;
+    s.out = a.out + (long)b * a.n_out * a.ld_out;
+    s.end = a.end ? a.end[b] : 0x7fffffff;
+    s.p = a.p; s.n_new = a.n_new; s.o0 = a.o0; s.n_out = a.n_out;
+    dwconv_stream_body(a, s, ct);
 }
 
-// ------------------------------------------------------------------------------------------------ CTC collapse with a carried class
-// best (B, T) int32: frame t < n_b of stream b is kept iff best != blank and best != the class before it, which for t = 0 is prev[b] (the last class of the
-// previous call; -1 at stream start).  ids (B, T) int32: the kept classes in order, then -1; n_ids (B); prev[b] becomes the class of frame n_b - 1.  One wave per stream.
+// CTC collapse with a carried class: best (B, T) int32, frames t < n_b of stream b count; ids (B, T); one wave per stream
 __global__ __launch_bounds__(64) void ctc_collapse_stream_kernel(const int* __restrict__ best, int T, const int* __restrict__ n_valid, int offset, int blank,
                                                                  int* __restrict__ prev, int* __restrict__ ids, int* __restrict__ n_ids) {
-    const int b = blockIdx.x, lane = threadIdx.x;
+    const int b = blockIdx.x;
     int n = n_valid ? n_valid[b] - offset : T;
     n = n < 0 ? 0 : (n > T ? T : n);
-    const int* row = best + (long)b * T;
-    int* out = ids + (long)b * T;
-    const int carried = prev[b];
-    int count = 0;
-    for (int base = 0; base < n; base += 64) {
-        const int t = base + lane;
-        bool keep = false;
-        int c = blank;
-        if (t < n) {
-            c = row[t];
-            const int before = t == 0 ? carried : row[t - 1];
-            keep = c != blank && c != before;
-        }
-        const unsigned long long mask = __ballot(keep);
-        if (keep) out[count + __popcll(mask & ((1ull << lane) - 1ull))] = c;
-        count += __popcll(mask);
-    }
-    for (int t = count + lane; t < T; t += 64) out[t] = -1;
-    if (lane == 0) {
-        n_ids[b] = count;
-        if (n > 0) prev[b] = row[n - 1];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ the driver's state
-struct Geo {
-    int B, C, Lmax, L, d, I, H, hd, F, F1, F2, C1, C2, V1, r, Hc, dil, Kc, Km, N, ctiles;
-    long ldl;
-};
-
-bool geometry(const mi_ebf_config* c, int C, int Lmax, Geo& g) {
-    if (!c || c->B <= 0 || c->H <= 0 || c->L <= 0 || c->d <= 0 || (c->d % c->H) || (c->I % 2) || C <= 0 || Lmax <= 0) return false;
-    if (c->K != 3 || c->stride != 2 || c->pad != 1 || !c->is_causal || c->T != 4 * C) return false;      // the front-end state (two rows per conv) is that of 3 x 3 / stride 2
-    if (c->merge_kernel < 1 || !(c->merge_kernel & 1) || c->csgu_kernel < 1 || !(c->csgu_kernel & 1)) return false;
-    g.B = c->B; g.C = C; g.Lmax = Lmax; g.L = c->L; g.d = c->d; g.I = c->I; g.H = c->H; g.hd = c->d / c->H; g.F = c->F;
-    g.F1 = conv_out(c->F, 3, 2, 2); g.F2 = conv_out(g.F1, 3, 2, 2); g.C1 = c->C1; g.C2 = c->C2; g.V1 = c->V + 1;
-    g.Km = c->merge_kernel; g.r = (g.Km - 1) / 2; g.Kc = c->csgu_kernel; g.dil = (g.Kc - 1) / 2; g.Hc = (g.Kc - 1) * g.dil;
-    g.N = C + g.L * g.r;                     // most rows a layer takes or emits in one step (the flush)
-    g.ctiles = (g.I / 2 + 63) / 64;
-    g.ldl = c->logits_ld > 0 ? c->logits_ld : g.V1;
-    return g.F2 > 0;
-}
-
-struct LayerState { bf16_t *kv, *csgu, *cat; float *csgu_stats, *pend; };
-struct St {
-    float* x_hist; bf16_t* c1_hist; int* prev; bf16_t* posp; LayerState* ls;      // ls: host array of L entries
-    size_t persistent;                                                            // bytes reset() clears
-    float *featcat, *feo, *fp, *x, *xo, *res, *stats;
-    bf16_t *act1n, *act1c, *act2, *a0, *a1, *a2, *a1r, *h, *qk, *ctx, *cat, *m2, *s, *cv, *lin, *hid;
-    size_t bytes;
-};
-
-St carve_state(const mi_ebf_config& c, const Geo& g, void* base, LayerState* ls) {
-    Carver k{(char*)base, 0};
-    auto bf = [&](size_t n) { return (bf16_t*)k.take(n * 2 + 16); };
-    auto f32 = [&](size_t n) { return (float*)k.take(n * 4 + 16); };
-    St s;
-    const size_t B = g.B, d = g.d, I = g.I;
-    s.x_hist = f32(B * 2 * g.F);
-    s.c1_hist = bf(B * 2 * g.F1 * g.C1);
-    s.prev = (int*)k.take(B * 4);
-    s.ls = ls;
-    for (int l = 0; l < g.L; ++l) {
-        LayerState t;
-        t.kv = bf(B * g.Lmax * 2 * d);
-        t.csgu = bf(B * g.Hc * (I / 2));
-        t.csgu_stats = f32(B * g.ctiles * g.Hc * 2);
-        t.cat = bf(B * 2 * g.r * 2 * d);
-        t.pend = f32(B * (size_t)(g.r + g.N) * d);
-        if (ls) ls[l] = t;
-    }
-    s.persistent = k.off;
-    s.posp = c.pos_type == 1 ? bf((size_t)g.L * g.Lmax * d) : nullptr;
-    const size_t M = B * g.N, Mc = B * g.C;
-    s.featcat = f32(B * (4 * g.C + 2) * g.F);
-    s.act1n = bf(B * 2 * g.C * g.F1 * g.C1); s.act1c = bf(B * (2 * g.C + 2) * g.F1 * g.C1); s.act2 = bf(Mc * g.F2 * g.C2);
-    s.feo = f32(Mc * d); s.fp = f32(Mc * d);
-    s.x = f32(M * d); s.xo = f32(M * d); s.res = f32(M * d); s.stats = f32(M * 2);
-    s.a0 = bf(M * d); s.a1 = bf(M * d); s.a2 = bf(M * d); s.a1r = bf(M * d);
-    s.h = bf(M * I); s.qk = bf(M * 3 * d); s.ctx = bf(M * d); s.cat = bf(M * 2 * d); s.m2 = bf(M * 2 * d); s.s = bf(M * (I / 2));
-    s.cv = s.lin = nullptr;
-    if (c.csgu_linear) { s.cv = bf(M * (I / 2)); s.lin = bf(M * (I / 2)); }
-    s.hid = bf(M * d);
-    s.bytes = k.off;
-    return s;
-}
-
-bool supported(const mi_ebf_config& c, const Geo& g) {
-    return !c.extra_layers && !c.layer_mixing && !c.context_mode && (g.hd == 16 || g.hd == 64 || g.hd == 128) && g.Lmax <= 8192 && g.L <= 64;
+    ctc_collapse_row(best + (long)b * T, n, T, blank, prev + b, ids + (long)b * T, n_ids + b, threadIdx.x);
 }
 
 }  // namespace

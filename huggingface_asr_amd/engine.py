@@ -379,6 +379,14 @@ class EBranchformerEngine:
         from .streaming import EncoderStream
         return EncoderStream(self, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
 
+    def stream_pool(self, slots: int, chunk_frames: int, max_frames: int, *, beams=None):
+        """Streaming inference for sessions that start, idle and end on their own: -> streaming.StreamPool of `slots` slots over one state.  `open()` gives a free slot;
+        `step(feed={slot: chunk}, finish={slot: tail})` advances the named slots — one set of launches over the rows of all of them —, leaves the others untouched and
+        frees the finished ones.  A session's logits and ids are bit for bit those of `stream(1, chunk_frames, max_frames)` fed the same pieces, whatever the other slots
+        do (csrc/stream_pool.hip; DESIGN.md §4 'Session pool').  Refusals as `stream`'s; beams= raises NotImplementedError."""
+        from .streaming import StreamPool
+        return StreamPool(self, slots, chunk_frames, max_frames, beams=beams)
+
     def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
         """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
         Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also

@@ -328,6 +328,16 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
             raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
         return self._get_engine(dev).stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
 
+    def stream_pool(self, slots: int, chunk_frames: int, max_frames: int, device=None, *, beams=None):
+        """Streaming inference for sessions that start, idle and end on their own (eval mode only): -> streaming.StreamPool over this model's weights, as
+        EBranchformerEngine.stream_pool describes it (DESIGN.md §4 'Session pool')."""
+        if self.training:
+            raise RuntimeError("stream_pool() is an inference call: put the model in eval mode first (model.eval())")
+        dev = device if device is not None else next(self.parameters()).device
+        if torch.device(dev).type != "cuda":
+            raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
+        return self._get_engine(dev).stream_pool(slots, chunk_frames, max_frames, beams=beams)
+
     def forward(
         self,
         input_values: Optional[torch.Tensor],

@@ -947,3 +947,89 @@ def ctc_collapse_stream(best, blank, prev, n_valid=None, offset=0):
     rc = _lib.lib().mi_ctc_collapse_stream(best.data_ptr(), B, T, _p(n_valid), int(offset), int(blank), prev.data_ptr(), ids.data_ptr(), n.data_ptr(), _stream())
     _lib.check(rc, "mi_ctc_collapse_stream")
     return ids, n
+
+
+# ---------------------------------------------------------------------------------------------------- streaming session pool: the per-slot forms (csrc/stream_pool.hip)
+def slot_table(entries, width, device):
+    """entries: rows of `width` ints, one per active slot -> (host, device) int32 tensors of the same words: the C entries check the first and hand the second to the kernel"""
+    host = torch.tensor(entries, dtype=torch.int32).reshape(-1, width).contiguous()
+    return host, host.to(device)
+
+
+NO_END = 0x7FFFFFFF          # a dwconv entry's `end` of a slot that does not finish
+
+
+def copy_rows_slots(src, dst, entries, W=None):
+    """rows between (slots, rows, width) tensors of 4-byte elements (fp32 / int32; last dim contiguous), `dst` written in place.  entries: per active slot (src slot, src
+    row, src modulus, dst slot, dst row, dst modulus, rows); a modulus of 0 does not wrap.  W: elements of a row copied (default: the narrower width).  mi_copy_rows_slots."""
+    _req(src); _req(dst)
+    if src.element_size() != 4 or dst.element_size() != 4 or src.dim() != 3 or dst.dim() != 3 or src.stride(2) != 1 or dst.stride(2) != 1:
+        raise ValueError("copy_rows_slots: (slots, rows, width) tensors of 4-byte elements, last dim contiguous")
+    W = min(src.shape[2], dst.shape[2]) if W is None else int(W)
+    th, td = slot_table(entries, 7, src.device)
+    rc = _lib.lib().mi_copy_rows_slots(src.data_ptr(), src.stride(0), src.stride(1), src.shape[0], src.shape[1], dst.data_ptr(), dst.stride(0), dst.stride(1), dst.shape[0],
+                                       dst.shape[1], th.data_ptr(), td.data_ptr(), th.shape[0], W, _stream())
+    _lib.check(rc, "mi_copy_rows_slots")
+    return dst
+
+
+def attention_chunk_slots(q, k_cache, v_cache, entries, H, *, pos=None, bias_u=None, bias_v=None, scale=None, ref=0):
+    """attention_chunk per slot: q (sum n_q, d) bf16 compact; k_cache / v_cache (slots, Lmax, d) row views of one cache; entries: per active slot (first query row, n_q,
+    n_k, slot), the first rows the prefix sums of n_q.  -> (sum n_q, d) bf16.  mi_attention_chunk_slots_bf16."""
+    _req(q, BF16); _req(k_cache, BF16); _req(v_cache, BF16)
+    q = q.contiguous()
+    n, d = q.shape
+    if k_cache.stride() != v_cache.stride() or k_cache.stride(2) != 1:
+        raise ValueError("attention_chunk_slots: k_cache and v_cache must be row views with equal strides")
+    hd = d // H
+    out = torch.empty((n, d), device=q.device, dtype=BF16)
+    th, td = slot_table(entries, 4, q.device)
+    rc = _lib.lib().mi_attention_chunk_slots_bf16(q.data_ptr(), d, k_cache.data_ptr(), k_cache.stride(1), v_cache.data_ptr(), v_cache.stride(1), k_cache.stride(0),
+                                                  k_cache.shape[0], k_cache.shape[1], _p(pos), 0 if pos is None else pos.stride(0), _p(bias_u), _p(bias_v), out.data_ptr(), d,
+                                                  th.data_ptr(), td.data_ptr(), th.shape[0], H, hd, float(scale if scale is not None else 1.0 / math.sqrt(hd)), int(ref), _stream())
+    _lib.check(rc, "mi_attention_chunk_slots_bf16")
+    return out
+
+
+def dwconv_stream_slots(x, w, bias, ring, entries, n_out_total, *, mode, K, dil=1, left, ring_stats=None, stats=None, gamma=None, beta=None, mul=None, act=0):
+    """dwconv_stream per slot: x (sum n_new, C) bf16 compact (last dim contiguous, any row stride); ring (slots, Hr, C) advanced in place; entries: per active slot (slot,
+    first in row, first out row, p, n_new, o0, n_out, end or NO_END).  -> (n_out_total, C) bf16 compact.  mi_dwconv_stream_slots_bf16."""
+    _req(x, BF16); _req(ring, BF16)
+    Cc = x.shape[1]
+    Hr = ring.shape[1]
+    out = torch.empty((n_out_total, Cc), device=x.device, dtype=BF16)
+    th, td = slot_table(entries, 8, x.device)
+    rc = _lib.lib().mi_dwconv_stream_slots_bf16(x.data_ptr(), x.stride(0), _p(mul), 0 if mul is None else mul.stride(0), _p(stats), _p(gamma), _p(beta), w.data_ptr(), _p(bias),
+                                                ring.data_ptr() if Hr else 0, _p(ring_stats), ring.shape[0], out.data_ptr(), Cc, th.data_ptr(), td.data_ptr(), th.shape[0],
+                                                Cc, int(K), int(dil), int(left), Hr, DWCONV_STREAM_MODES[mode], int(act), _stream())
+    _lib.check(rc, "mi_dwconv_stream_slots_bf16")
+    return out
+
+
+def rotary_slots(x, cos, sin, entries, H):
+    """rotary with per-slot positions: x (rows, d) bf16 compact; cos / sin (tmax, hd) fp32; entries: per active slot (first row, rows, p): row i of the slot stands at
+    position p + i.  -> (rows, d) bf16 (rows no entry names are not written).  mi_rotary_slots_bf16."""
+    _req(x, BF16)
+    M, d = x.shape
+    out = torch.zeros_like(x)
+    th, td = slot_table(entries, 3, x.device)
+    rc = _lib.lib().mi_rotary_slots_bf16(x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0), cos.data_ptr(), sin.data_ptr(), cos.shape[0], th.data_ptr(), td.data_ptr(),
+                                         th.shape[0], H, d // H, _stream())
+    _lib.check(rc, "mi_rotary_slots_bf16")
+    return out
+
+
+def ctc_collapse_slots(best, blank, prev, entries):
+    """ctc_collapse_stream per slot: best (frames) int32 compact; prev (slots) int32 the carried classes, updated in place; entries: per active slot (slot, first frame,
+    frames).  -> (ids (frames) int32: an entry's new tokens then -1 in its places, n_ids (entries) int32).  mi_ctc_collapse_slots."""
+    _req(best, torch.int32); _req(prev, torch.int32)
+    best = best.contiguous()
+    th, td = slot_table(entries, 3, best.device)
+    if best.numel() == 0:
+        raise ValueError("ctc_collapse_slots: no frames")
+    ids = torch.full((best.numel(),), -1, device=best.device, dtype=torch.int32)
+    n = torch.empty((th.shape[0],), device=best.device, dtype=torch.int32)
+    rc = _lib.lib().mi_ctc_collapse_slots(best.data_ptr(), int(blank), prev.data_ptr(), prev.numel(), ids.data_ptr(), n.data_ptr(), th.data_ptr(), td.data_ptr(),
+                                          th.shape[0], _stream())
+    _lib.check(rc, "mi_ctc_collapse_slots")
+    return ids, n

@@ -10,6 +10,12 @@ once the front end has produced frame t + L*r: `plan` gives the per-layer row ra
 
     stream = engine.stream(B, C, 1500, beams=10, nbest=4)      # also walks the CTC prefix beam search over the emitted frames (ops.CtcBeamStream)
     out["beam"]                         # per step: committed / committed_frames (B, max_frames) int32 then -1, n_committed, n_new (B); at finish also the n-best
+
+Sessions that start, idle and end on their own share one state as a pool of slots (csrc/stream_pool.hip; `StreamPool`, `pool_table` below):
+
+    pool = engine.stream_pool(slots=S, chunk_frames=C, max_frames=1500)
+    sid = pool.open()                   # a free slot, started on the device without touching the others
+    out = pool.step(feed={sid: chunk (4*C, F)}, finish={other: tail (0..4*C, F) or None})      # -> {slot: dict(logits (n_out, V+1), ids, n_ids, n_out, total, final)}
 """
 from __future__ import annotations
 
@@ -47,24 +53,30 @@ def plan(n_feat: int, C: int, L: int, r: int, finish: bool, n_prev: int | None =
     return list(zip(before, after))
 
 
+def _check_streamable(engine, n, chunk_frames, max_frames, what, count):
+    """the refusals of `engine.stream` / `engine.stream_pool`, before any launch -> engine.cfg"""
+    c = engine.cfg
+    if not c.get("is_causal", False):
+        raise ValueError(f"{what}: the model is not causal (is_causal=False): its layers see the whole utterance, there is nothing to stream")
+    if engine.precision != "bf16":
+        raise NotImplementedError(f"{what}: precision='fp32' has no streaming path: use the default precision='bf16'")
+    if engine.mix or engine.extra:
+        raise NotImplementedError(f"{what}: the BEST-RQ fine-tuning head (finetune_with_layer_mixing / finetune_with_additional_layer) has no streaming path")
+    if (c["conv_kernel"][0], c["conv_stride"][0], c["conv_padding"][0]) != (3, 2, 1):
+        raise NotImplementedError(f"{what}: the front-end state is that of the 3 x 3 / stride 2 / padding 1 Conv2d sub-sampling")
+    hd = c["hidden_size"] // c["num_attention_heads"]
+    if hd not in (16, 64, 128):
+        raise NotImplementedError(f"{what}: head size {hd} (mi_attention_chunk_bf16 takes 16, 64, 128)")
+    if n < 1 or chunk_frames < 1 or max_frames < 1 or max_frames > 8192:
+        raise ValueError(f"{what}: {count}, chunk_frames >= 1 and 1 <= max_frames <= 8192")
+    return c
+
+
 class EncoderStream:
     """State of B streams advanced in lock-step through a causal encoder + CTC head (mi_ebf_stream_step).  Created by `EBranchformerEngine.stream`."""
 
     def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
-        c = engine.cfg
-        if not c.get("is_causal", False):
-            raise ValueError("stream(): the model is not causal (is_causal=False): its layers see the whole utterance, there is nothing to stream")
-        if engine.precision != "bf16":
-            raise NotImplementedError("stream(): precision='fp32' has no streaming path: use the default precision='bf16'")
-        if engine.mix or engine.extra:
-            raise NotImplementedError("stream(): the BEST-RQ fine-tuning head (finetune_with_layer_mixing / finetune_with_additional_layer) has no streaming path")
-        if (c["conv_kernel"][0], c["conv_stride"][0], c["conv_padding"][0]) != (3, 2, 1):
-            raise NotImplementedError("stream(): the front-end state is that of the 3 x 3 / stride 2 / padding 1 Conv2d sub-sampling")
-        hd = c["hidden_size"] // c["num_attention_heads"]
-        if hd not in (16, 64, 128):
-            raise NotImplementedError(f"stream(): head size {hd} (mi_attention_chunk_bf16 takes 16, 64, 128)")
-        if batch < 1 or chunk_frames < 1 or max_frames < 1 or max_frames > 8192:
-            raise ValueError("stream(): batch, chunk_frames >= 1 and 1 <= max_frames <= 8192")
+        c = _check_streamable(engine, batch, chunk_frames, max_frames, "stream()", "batch")
         self.engine, self.B, self.C, self.max_frames = engine, int(batch), int(chunk_frames), int(max_frames)
         self.L = c["num_hidden_layers"]
         self.r = (c.get("merge_conv_kernel", 31) - 1) // 2
@@ -200,4 +212,179 @@ class EncoderStream:
         self.finished = True
         out["totals"] = torch.tensor(ends, dtype=torch.int32)
         out["n_valid"] = out["totals"] - base
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------- session pool (csrc/stream_pool.hip states the semantics)
+def pool_table(actions, C: int, L: int, r: int):
+    """The descriptor records of one pool step.  actions: the active slots in order, each (slot, n_prev, n, finish) — the slot has had n_prev feature frames and now gets n
+    (a whole chunk of 4*C, or as `finish` a tail of 0 .. 4*C).  -> (records, totals): record i = [slot, end, lo_0, hi_0, off_0, .. lo_L, hi_L, off_L] with (lo_l, hi_l) =
+    plan(n_prev + n, C, L, r, finish, n_prev=n_prev)[l] of that slot alone (in a finish the frontiers are its own end), off_l the sum of the earlier records' hi_l - lo_l
+    (the slot's first row in the step's compact buffers), end = the slot's frame count when it finishes, else -1; totals[l] = the rows of all records at entry l.
+    Pure host arithmetic."""
+    totals = [0] * (L + 1)
+    records = []
+    for slot, n_prev, n, finish in actions:
+        rows = plan(n_prev + n, C, L, r, bool(finish), n_prev=n_prev)
+        rec = [int(slot), rows[0][1] if finish else -1]
+        for l, (lo, hi) in enumerate(rows):
+            rec += [lo, hi, totals[l]]
+            totals[l] += hi - lo
+        records.append(rec)
+    return records, totals
+
+
+class StreamPool:
+    """S slots over one stream state, each a session with a position of its own: `open` a slot, `step` any subset of the open slots — each feeds a chunk or finishes, the
+    others stay idle and untouched —, a finished slot is free again.  Created by `EBranchformerEngine.stream_pool`.
+
+        pool = engine.stream_pool(slots=16, chunk_frames=C, max_frames=1500)
+        sid = pool.open()
+        out = pool.step(feed={sid: chunk (4*C, F)}, finish={other: tail (0..4*C, F) or None})      # -> {sid: dict(logits (n_out, V+1) fp32, ids, n_ids, total, final)}
+
+    Concatenated over its calls, a session's logits and ids are those of `engine.stream(1, C, max_frames)` fed the same pieces, whatever the other slots do."""
+
+    def __init__(self, engine, slots: int, chunk_frames: int, max_frames: int, *, beams=None):
+        c = _check_streamable(engine, slots, chunk_frames, max_frames, "stream_pool()", "slots")
+        if beams is not None:
+            raise NotImplementedError("stream_pool(): beams= is not implemented for the pool (the streaming beam search advances its streams in lock-step): use "
+                                      "engine.stream(1, ..., beams=) per session")
+        self.engine, self.S, self.C, self.max_frames = engine, int(slots), int(chunk_frames), int(max_frames)
+        self.L = c["num_hidden_layers"]
+        self.r = (c.get("merge_conv_kernel", 31) - 1) // 2
+        self.F = c.get("num_fbanks", 80)
+        self.lookahead = self.L * self.r
+        self.is_open = [False] * self.S
+        self.n_feat = [0] * self.S                      # feature frames the slot's session has had
+        self.total = [0] * self.S                       # frames it has emitted
+        self._state = None
+        self._cs = None
+
+    # ------------------------------------------------------------------ state
+    def _config(self):
+        if self._cs is None:
+            cs = self.engine._config_struct(self.S, SUBSAMPLING * self.C, self.F)
+            cs.ln_fold = cs.wide_tiles = cs.branch_overlap = 0
+            cs.logits_f32 = 1
+            self._cs = cs
+        return self._cs
+
+    def state_bytes(self) -> int:
+        return int(_lib.lib().mi_ebf_stream_state_bytes(C.byref(self._config()), self.C, self.max_frames))
+
+    def _ensure_state(self):
+        e = self.engine
+        if e._table is None:
+            raise RuntimeError("StreamPool: load_state_dict() on the engine first")
+        if self._state is not None and self._version == e.weights_version:
+            return
+        if self._state is not None and any(self.is_open):
+            raise RuntimeError("StreamPool: the engine's weights changed while sessions were open")
+        c, dev = e.cfg, e.device
+        nbytes = self.state_bytes()
+        if nbytes == 0:
+            raise RuntimeError("mi_ebf_stream_state_bytes refused the configuration")
+        self._state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        d, H = c["hidden_size"], c["num_attention_heads"]
+        ptype = c.get("position_embeddings_type", "relative")
+        self._pos = None
+        if ptype == "relative":
+            self._pos = relative_position_table(self.max_frames, d)[: self.max_frames].flip(0).to(dev).to(torch.bfloat16).contiguous()
+        elif ptype == "rotary":
+            cos, sin = rotary_tables(self.max_frames, d // H, c.get("rotary_embedding_base", 10000))
+            self._pos = torch.cat([cos.reshape(-1), sin.reshape(-1)]).to(dev).contiguous()
+        self._version = e.weights_version
+        rc = _lib.lib().mi_ebf_stream_reset(C.byref(self._config()), e._table, self.C, self.max_frames, None if self._pos is None else self._pos.data_ptr(),
+                                            self._state.data_ptr(), self._state.numel(), torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "mi_ebf_stream_reset")
+
+    # ------------------------------------------------------------------ sessions
+    def open(self) -> int:
+        """-> a free slot, started: zero histories and rings, no carried class (a per-slot reset on the device, enqueued on the current stream)"""
+        free = [s for s in range(self.S) if not self.is_open[s]]
+        if not free:
+            raise RuntimeError(f"StreamPool.open: all {self.S} slots hold open sessions")
+        sid = free[0]
+        if self.engine._table is not None and torch.device(self.engine.device).type == "cuda":      # else: no state yet — it is created whole, every slot at a stream start
+            self._ensure_state()
+            rc = _lib.lib().mi_ebf_stream_reset_slot(C.byref(self._config()), self.C, self.max_frames, self._state.data_ptr(), self._state.numel(), sid,
+                                                     torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "mi_ebf_stream_reset_slot")
+        self.is_open[sid] = True
+        self.n_feat[sid] = self.total[sid] = 0
+        return sid
+
+    def actions(self, feed=None, finish=None):
+        """the checked actions of a step, ordered by slot -> [(slot, n_prev, n, finish, tensor or None)]"""
+        feed, finish = dict(feed or {}), dict(finish or {})
+        W = SUBSAMPLING * self.C
+        acts = []
+        for sid in sorted(set(feed) | set(finish)):
+            if sid in feed and sid in finish:
+                raise ValueError(f"StreamPool.step: slot {sid} is named in both feed and finish")
+            if not isinstance(sid, int) or not 0 <= sid < self.S or not self.is_open[sid]:
+                raise RuntimeError(f"StreamPool.step: slot {sid} holds no open session (free or finished): open() starts one")
+            if sid in feed:
+                x = feed[sid]
+                if x is None or tuple(x.shape) != (W, self.F):
+                    raise ValueError(f"StreamPool.step: a chunk is ({W}, {self.F}) (4 * chunk_frames, features), got {None if x is None else tuple(x.shape)}; the last, "
+                                     "shorter piece goes to finish=")
+                n = W
+            else:
+                x = finish[sid]
+                n = 0 if x is None else int(x.shape[0])
+                if x is not None and (x.dim() != 2 or x.shape[1] != self.F or n > W):
+                    raise ValueError(f"StreamPool.step: the tail is (0..{W}, {self.F}), got {tuple(x.shape)}")
+            if causal_out_frames(self.n_feat[sid] + n) > self.max_frames:
+                raise RuntimeError(f"StreamPool: {causal_out_frames(self.n_feat[sid] + n)} encoder frames of slot {sid} exceed max_frames={self.max_frames}")
+            acts.append((sid, self.n_feat[sid], n, sid in finish, x))
+        return acts
+
+    def _advance(self, acts, records):
+        """host bookkeeping after a step -> per slot (n_out, total, final)"""
+        res = {}
+        for (sid, n_prev, n, fin, _), rec in zip(acts, records):
+            n_out = rec[-2] - rec[-3]
+            self.n_feat[sid] = n_prev + n
+            self.total[sid] += n_out
+            res[sid] = (n_out, self.total[sid], fin)
+            if fin:
+                self.is_open[sid] = False
+        return res
+
+    def step(self, feed=None, finish=None) -> dict:
+        """feed {slot: chunk (4*C, F)}, finish {slot: tail (0..4*C, F) or None}; every other slot is idle.  -> {slot: dict(logits (n_out, V+1) fp32, ids (n_out) int32 =
+        the greedy tokens newly emitted then -1, n_ids (0-d int32), n_out, total, final)} for the named slots.  A finished slot is free after the call."""
+        acts = self.actions(feed, finish)
+        if not acts:
+            return {}
+        e = self.engine
+        if not torch.device(e.device).type == "cuda" or any(a[4] is not None and not a[4].is_cuda for a in acts):
+            raise RuntimeError("StreamPool needs device tensors (no CPU fallback)")
+        self._ensure_state()
+        dev, cs, lib = e.device, self._config(), _lib.lib()
+        W, A, V1 = SUBSAMPLING * self.C, len(acts), e.cfg["vocab_size"] + 1
+        records, totals = pool_table([a[:4] for a in acts], self.C, self.L, self.r)
+        zero = lambda n: torch.zeros((n, self.F), dtype=torch.float32, device=dev)
+        feats = torch.stack([x.to(torch.float32) if n == W else (zero(W) if n == 0 else torch.cat([x.to(torch.float32), zero(W - n)])) for _, _, n, _, x in acts])   # a tail zero-padded
+        rec = torch.tensor(records, dtype=torch.int32)
+        words = lib.mi_ebf_stream_slots_table(C.byref(cs), self.C, self.max_frames, rec.data_ptr(), A, None, 0)
+        _lib.check(min(words, 0), "mi_ebf_stream_slots_table")
+        host = torch.empty((words,), dtype=torch.int32, pin_memory=True)
+        _lib.check(min(lib.mi_ebf_stream_slots_table(C.byref(cs), self.C, self.max_frames, rec.data_ptr(), A, host.data_ptr(), words), 0), "mi_ebf_stream_slots_table")
+        table = host.to(dev, non_blocking=True)         # the step's one host-to-device transfer
+        n_out = totals[-1]
+        lbuf = torch.empty((n_out, cs.logits_ld), dtype=torch.float32, device=dev)
+        best = torch.empty((n_out,), dtype=torch.int32, device=dev)
+        ids = torch.empty((n_out,), dtype=torch.int32, device=dev)
+        n_ids = torch.zeros((A,), dtype=torch.int32, device=dev)
+        p = lambda t: None if t is None or t.numel() == 0 else t.data_ptr()
+        rc = lib.mi_ebf_stream_step_slots(C.byref(cs), e._table, self.C, self.max_frames, p(self._pos), self._state.data_ptr(), self._state.numel(), feats.data_ptr(),
+                                          rec.data_ptr(), A, table.data_ptr(), words, p(lbuf), p(best), p(ids), n_ids.data_ptr(),
+                                          torch.cuda.current_stream().cuda_stream)
+        _lib.check(rc, "mi_ebf_stream_step_slots")
+        out = {}
+        for i, (sid, (n, total, fin)) in enumerate(self._advance(acts, records).items()):
+            off = records[i][-1]
+            out[sid] = dict(logits=lbuf[off:off + n, :V1], ids=ids[off:off + n], n_ids=n_ids[i], best=best[off:off + n], n_out=n, total=total, final=fin)
         return out

@@ -791,6 +791,47 @@ int mi_ebf_stream_reset(const mi_ebf_config* cfg, const void* const* weights, in
 int mi_ebf_stream_step(const mi_ebf_config* cfg, const void* const* weights, int chunk_frames, int max_frames, const void* pos_table, void* state, size_t state_bytes,
                        const float* feats, const int* rows, const int* ends, float* logits, int* best, int* ids, int* n_ids, mi_stream_t stream);
 
+/* ---- streaming session pool: S slots over one stream state (cfg.B = S), each with a position of its own; in a step a slot feeds a chunk, finishes or is idle, and is
+ * reusable after it finishes (csrc/stream_pool.hip, whose header states the exact semantics).  The per-slot forms of the five kernels above that hold per-stream position
+ * take a table of per-slot descriptors — twice: tab_host is checked (MI_ERR_ARG), tab_dev holds the same words on the device and is what the kernel reads.  Rows of the
+ * active slots lie compactly one after another; the caches, rings and carried classes are indexed by slot.  No atomics.  DESIGN.md §4 'Session pool'. */
+/* copy table, 7 ints per entry: src slot, src row, src modulus (0: no wrap), dst slot, dst row, dst modulus, rows.  src (src_slots, src_rows, src_ld), dst likewise; W
+ * 4-byte words of a row are copied; strides in 4-byte words. */
+int mi_copy_rows_slots(const void* src, long src_bs, long src_ld, int src_slots, int src_rows, void* dst, long dst_bs, long dst_ld, int dst_slots, int dst_rows,
+                       const int* tab_host, const int* tab_dev, int A, int W, mi_stream_t stream);
+/* mi_attention_chunk_bf16 per slot; 4 ints per entry: first query row (the prefix sum of the n_q before it), n_q, n_k, slot.  q / out (sum n_q, .) compact; k / v the
+ * (slots, kv_rows, .) cache.  The grid runs over the total queries, the LDS is sized by the largest n_k. */
+int mi_attention_chunk_slots_bf16(const void* q, long ldq, const void* k, long ldk, const void* v, long ldv, long kv_bstride, int slots, int kv_rows, const void* pos, long ldp,
+                                  const float* bias_u, const float* bias_v, void* out, long ldo, const int* tab_host, const int* tab_dev, int A, int H, int hd, float scale,
+                                  int ref, mi_stream_t stream);
+/* mi_dwconv_stream_bf16 per slot; 8 ints per entry: slot, first in row, first out row, p, n_new, o0, n_out, end (0x7fffffff: none).  in / stats / mul / out compact; ring
+ * (slots, Hr, C), ring_stats (slots, ceil(C/64), Hr, 2).  Only a slot with an end may read past its fed rows as zero. */
+int mi_dwconv_stream_slots_bf16(const void* in, long ld_in, const void* mul, long ld_mul, const float* stats, const float* gamma, const float* beta, const float* w,
+                                const float* bias, void* ring, float* ring_stats, int slots, void* out, long ld_out, const int* tab_host, const int* tab_dev, int A,
+                                int C, int K, int dil, int left, int Hr, int mode, int act, mi_stream_t stream);
+/* mi_rotary_bf16 with the position of a row = its slot's p + its index within the slot; 3 ints per entry: first row, rows, p.  cos_t / sin_t (tmax, hd) fp32. */
+int mi_rotary_slots_bf16(const void* x, long ldx, void* out, long ldo, const float* cos_t, const float* sin_t, int tmax, const int* tab_host, const int* tab_dev,
+                         int A, int H, int hd, mi_stream_t stream);
+/* mi_ctc_collapse_stream per slot; 3 ints per entry: slot, first frame, frames.  best / ids compact, prev (slots), n_ids (A); an entry of zero frames keeps its carried class. */
+int mi_ctc_collapse_slots(const int* best, int blank, int* prev, int slots, int* ids, int* n_ids, const int* tab_host, const int* tab_dev, int A, mi_stream_t stream);
+/* the pool's driver.  State: mi_ebf_stream_state_bytes with cfg.B = slots, started once by mi_ebf_stream_reset.
+ * mi_ebf_stream_slot_pieces: (offset, bytes of one slot's slice) of the 3 + 5 L persistent pieces (x_hist, c1_hist, prev; per layer kv, csgu, csgu_stats, cat, pend);
+ *   -> their number (out may be null).  Host only.
+ * mi_ebf_stream_reset_slot: one slot back to a stream start — its slices zero, its carried class -1 — in one launch on `stream`; no other slot is written.
+ * records (HOST), A x (2 + 3 (L + 1)) ints: slot, end (the slot's own end when it finishes, else -1), then (lo, hi, off) of the slot's input rows of layer 0 .. L-1 and
+ *   of the rows it emits: streaming.plan of the slot's own history, off = the sum of the earlier records' hi - lo at that layer.
+ * mi_ebf_stream_slots_table: the records, checked, expanded into the words the step's kernels read -> their count (table null: only counted).  Host only; the caller
+ *   uploads them, the step's one host-to-device transfer.
+ * mi_ebf_stream_step_slots: feats (A, 4*chunk_frames, F) fp32 (a tail zero-padded); table: those words on the DEVICE.  Outputs compact in record order: logits
+ *   (sum n_out, logits_ld) fp32, best / ids (sum n_out) int32 (ids: a record's new tokens then -1 in its n_out places), n_ids (A).  Attention is the per-slot chunk kernel
+ *   everywhere (without a relative term at head sizes 64 / 128 with ref 3). */
+int mi_ebf_stream_slot_pieces(const mi_ebf_config* cfg, int chunk_frames, int max_frames, long* out, int capacity);
+int mi_ebf_stream_reset_slot(const mi_ebf_config* cfg, int chunk_frames, int max_frames, void* state, size_t state_bytes, int slot, mi_stream_t stream);
+int mi_ebf_stream_slots_table(const mi_ebf_config* cfg, int chunk_frames, int max_frames, const int* records, int A, int* table, int capacity);
+int mi_ebf_stream_step_slots(const mi_ebf_config* cfg, const void* const* weights, int chunk_frames, int max_frames, const void* pos_table, void* state, size_t state_bytes,
+                             const float* feats, const int* records, int A, const int* table, int table_len, float* logits, int* best, int* ids, int* n_ids,
+                             mi_stream_t stream);
+
 /* ---- precision = "fp32" inference mode (csrc/gemm_f32.hip, csrc/encoder_f32.hip): the encoder + CTC head with every operand, activation and weight in fp32 — what the
  * reference's decode recipes (no --bf16) compute.  Opt-in; nothing above changes.  DESIGN.md §4 'fp32 inference mode'. */
 /* C (M,N) = resid + alpha * act(A (M,K) · W (N,K)^T + bias), all fp32, row-major with leading dimensions; act 0 none / 1 erf-GELU (exact erff) / 2 gelu_new (exact tanhf); bias, resid nullable,
