@@ -233,6 +233,10 @@ SIGNATURES = {
     "mi_ebf_stream_reset_slot": [C.POINTER(EbfConfig), i32, i32, vp, sz, i32, vp],
     "mi_ebf_stream_slots_table": [C.POINTER(EbfConfig), i32, i32, vp, i32, vp, i32],
     "mi_ebf_stream_step_slots": [C.POINTER(EbfConfig), vp, i32, i32, vp, vp, sz, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp],
+    # streaming from audio: the stateful log-mel front end (csrc/fbank_stream.hip)
+    "mi_fbank_stream_state_bytes": [i32, i32, i32],
+    "mi_fbank_stream_push": [vp, sz, i32, i32, i32, vp, i64, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f64, f64, vp],
+    "mi_fbank_stream_pop": [vp, sz, i32, i32, i32, vp, vp, i32, vp, i32, vp],
     # two-pass joint decoding (csrc/rescore.hip)
     "mi_rescore_pack": [vp, i32, vp, vp, i32, i32, i32, i32, i32, i64, i64, i64, vp, vp, vp, vp],
     "mi_rows_nll_f32": [vp, i64, vp, vp, i32, vp, i32, vp],
@@ -265,7 +269,7 @@ def lib():
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
                                           "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes", "mi_ctc_beam_stream_state_bytes", "mi_ctc_align_workspace_bytes",
-                                          "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes", "mi_ebf_stream_state_bytes", "mi_linear_rows_f32_workspace_bytes", "mi_decoder_step_f32_workspace_bytes") else i32
+                                          "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes", "mi_ebf_stream_state_bytes", "mi_linear_rows_f32_workspace_bytes", "mi_decoder_step_f32_workspace_bytes", "mi_fbank_stream_state_bytes") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None
         h.mi_profile_reset.argtypes = []; h.mi_profile_reset.restype = None

@@ -21,7 +21,8 @@ SOURCES = ["gemm_bf16.hip", "gemm_glds.hip", "gemm_8p.hip", "norm.hip", "conv.hi
            "train_ops.hip", "gemm_tn.hip", "bgemm.hip", "attn_bwd.hip", "attn_bwd_fused.hip", "conv_bwd.hip", "loss_bwd.hip", "mix_loss.hip", "dropout.hip", "bestrq.hip", "specaug.hip", "speed.hip",
            "gemm_f32.hip", "encoder_f32.hip", "decoder_f32.hip",      # precision = "fp32" inference mode
            "rescore.hip",
-           "stream.hip", "ctc_beam_stream.hip", "stream_pool.hip"]                    # streaming inference of the causal encoder; the prefix beam search on a stream
+           "stream.hip", "ctc_beam_stream.hip", "stream_pool.hip",                    # streaming inference of the causal encoder; the prefix beam search on a stream
+           "fbank_stream.hip"]                                                        # ... from audio: the stateful log-mel front end
 # -packed-fp32-ops (device side only): no v_pk_{add,mul,fma}_f32 in any kernel.  A wave executing packed-f32 VALU ops next to the LDS-DMA GEMM's
 # waves on one CU (kernels from two streams) lost the low-half product on 16 lanes in ~3 % of launches (tools/dbg/README.md); without packed
 # ops the same pairing ran clean, and beside MFMAs they are slower than their scalar pairs anyway (MI355X_MICROARCH.md, fillers table).

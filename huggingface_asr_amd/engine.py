@@ -387,6 +387,24 @@ class EBranchformerEngine:
         from .streaming import StreamPool
         return StreamPool(self, slots, chunk_frames, max_frames, beams=beams)
 
+    def audio_stream(self, batch: int, chunk_frames: int, max_frames: int, *, normalize=None, global_means=None, global_stds=None, beams=None, token_topk=None, nbest=1,
+                     max_push_samples=None, tables=None):
+        """`stream` fed audio: -> streaming.AudioStream.  `push(samples (B, n))` takes fp32 samples in [-1, 1] or int16 PCM in pieces of any size, `finish(tail, lengths)`
+        ends the streams; the stateful log-mel front end (csrc/fbank_stream.hip) gives, bit for bit, the features of fbank_gpu on the whole utterance with normalize=None
+        or "global" (global_means / global_stds (F)), so the logits are those of `stream` fed these features in the pieces streaming.audio_pieces names.  Refusals as
+        `stream`'s; normalize="utterance" raises NotImplementedError (utterance CMVN needs the whole utterance).  DESIGN.md §4 'Audio in'."""
+        from .streaming import AudioStream
+        return AudioStream(self, batch, chunk_frames, max_frames, normalize=normalize, global_means=global_means, global_stds=global_stds, beams=beams,
+                           token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, tables=tables)
+
+    def audio_pool(self, slots: int, chunk_frames: int, max_frames: int, *, normalize=None, global_means=None, global_stds=None, beams=None, max_push_samples=None,
+                   tables=None):
+        """`stream_pool` fed audio: -> streaming.AudioPool.  `open()` starts a session, `push(audio={sid: samples}, finish={sid: tail or None})` takes any sizes for
+        any subset of the open slots and returns {sid: [the dicts of the steps the slot took]}.  Refusals as `stream_pool`'s (beams= included) and `audio_stream`'s."""
+        from .streaming import AudioPool
+        return AudioPool(self, slots, chunk_frames, max_frames, normalize=normalize, global_means=global_means, global_stds=global_stds, beams=beams,
+                         max_push_samples=max_push_samples, tables=tables)
+
     def forward(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, want_hidden=True, want_logits=True, slot=0, want_all_hidden=False):
         """feats (B,T,F) fp32 device tensor; feat_lengths (B) int32 (= attention_mask.sum(-1)) or None.
         Returns dict(logits (B,T2,V+1), last_hidden (B,T2,d) fp32, inner_len, outer_len int32 (B)); with want_all_hidden also

@@ -338,6 +338,28 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
             raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
         return self._get_engine(dev).stream_pool(slots, chunk_frames, max_frames, beams=beams)
 
+    def _audio_engine(self, feature_extractor, device, what):
+        from .streaming import extractor_settings
+        if self.training:
+            raise RuntimeError(f"{what} is an inference call: put the model in eval mode first (model.eval())")
+        settings = extractor_settings(feature_extractor, self.config.num_fbanks)        # the refusals that need no device
+        dev = device if device is not None else next(self.parameters()).device
+        if torch.device(dev).type != "cuda":
+            raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
+        return self._get_engine(dev), settings
+
+    def audio_stream(self, feature_extractor, batch: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, token_topk=None, nbest=1, max_push_samples=None):
+        """`stream` fed audio (eval mode only): -> streaming.AudioStream.  feature_size, norm_type and the global statistics are read from the project's
+        `CustomFeatureExtractor`; an extractor with utterance CMVN is refused (NotImplementedError: it needs the whole utterance), one whose feature_size is not
+        config.num_fbanks too (ValueError).  The streamed features are those of `feature_extractor.extract_on_device(wave, default_transform=False)`."""
+        eng, settings = self._audio_engine(feature_extractor, device, "audio_stream()")
+        return eng.audio_stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, **settings)
+
+    def audio_pool(self, feature_extractor, slots: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, max_push_samples=None):
+        """`stream_pool` fed audio (eval mode only): -> streaming.AudioPool; the extractor is read as `audio_stream` reads it."""
+        eng, settings = self._audio_engine(feature_extractor, device, "audio_pool()")
+        return eng.audio_pool(slots, chunk_frames, max_frames, beams=beams, max_push_samples=max_push_samples, **settings)
+
     def forward(
         self,
         input_values: Optional[torch.Tensor],

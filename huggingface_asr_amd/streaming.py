@@ -16,6 +16,11 @@ Sessions that start, idle and end on their own share one state as a pool of slot
     pool = engine.stream_pool(slots=S, chunk_frames=C, max_frames=1500)
     sid = pool.open()                   # a free slot, started on the device without touching the others
     out = pool.step(feed={sid: chunk (4*C, F)}, finish={other: tail (0..4*C, F) or None})      # -> {slot: dict(logits (n_out, V+1), ids, n_ids, n_out, total, final)}
+
+Both take audio instead of feature frames through the stateful log-mel front end (csrc/fbank_stream.hip; `AudioStream`, `AudioPool`, `audio_pieces` below):
+
+    pool = engine.audio_pool(slots=S, chunk_frames=C, max_frames=1500, normalize="global", global_means=m, global_stds=s)
+    out = pool.push(audio={sid: samples (n) fp32 / int16, any n}, finish={other: tail or None})  # -> {slot: [the dicts of the steps the slot took]}
 """
 from __future__ import annotations
 
@@ -335,10 +340,13 @@ class StreamPool:
                 n = 0 if x is None else int(x.shape[0])
                 if x is not None and (x.dim() != 2 or x.shape[1] != self.F or n > W):
                     raise ValueError(f"StreamPool.step: the tail is (0..{W}, {self.F}), got {tuple(x.shape)}")
-            if causal_out_frames(self.n_feat[sid] + n) > self.max_frames:
-                raise RuntimeError(f"StreamPool: {causal_out_frames(self.n_feat[sid] + n)} encoder frames of slot {sid} exceed max_frames={self.max_frames}")
+            self._check_room(sid, self.n_feat[sid] + n)
             acts.append((sid, self.n_feat[sid], n, sid in finish, x))
         return acts
+
+    def _check_room(self, sid, n_feat):
+        if causal_out_frames(n_feat) > self.max_frames:
+            raise RuntimeError(f"StreamPool: {causal_out_frames(n_feat)} encoder frames of slot {sid} exceed max_frames={self.max_frames}")
 
     def _advance(self, acts, records):
         """host bookkeeping after a step -> per slot (n_out, total, final)"""
@@ -361,12 +369,21 @@ class StreamPool:
         e = self.engine
         if not torch.device(e.device).type == "cuda" or any(a[4] is not None and not a[4].is_cuda for a in acts):
             raise RuntimeError("StreamPool needs device tensors (no CPU fallback)")
+        dev, W = e.device, SUBSAMPLING * self.C
+        zero = lambda n: torch.zeros((n, self.F), dtype=torch.float32, device=dev)
+        feats = torch.stack([x.to(torch.float32) if n == W else (zero(W) if n == 0 else torch.cat([x.to(torch.float32), zero(W - n)])) for _, _, n, _, x in acts])   # a tail zero-padded
+        return self._run(acts, feats)
+
+    def _run(self, acts, feats) -> dict:
+        """the step of checked actions [(slot, n_prev, n, finish, _)] on their compact chunks feats (A, 4*C, F) fp32, tails zero-padded (AudioPool hands over
+        fbank.FbankStream.pop's buffer as it is)"""
+        e = self.engine
+        if not torch.device(e.device).type == "cuda":
+            raise RuntimeError("StreamPool needs device tensors (no CPU fallback)")
         self._ensure_state()
         dev, cs, lib = e.device, self._config(), _lib.lib()
         W, A, V1 = SUBSAMPLING * self.C, len(acts), e.cfg["vocab_size"] + 1
         records, totals = pool_table([a[:4] for a in acts], self.C, self.L, self.r)
-        zero = lambda n: torch.zeros((n, self.F), dtype=torch.float32, device=dev)
-        feats = torch.stack([x.to(torch.float32) if n == W else (zero(W) if n == 0 else torch.cat([x.to(torch.float32), zero(W - n)])) for _, _, n, _, x in acts])   # a tail zero-padded
         rec = torch.tensor(records, dtype=torch.int32)
         words = lib.mi_ebf_stream_slots_table(C.byref(cs), self.C, self.max_frames, rec.data_ptr(), A, None, 0)
         _lib.check(min(words, 0), "mi_ebf_stream_slots_table")
@@ -387,4 +404,229 @@ class StreamPool:
         for i, (sid, (n, total, fin)) in enumerate(self._advance(acts, records).items()):
             off = records[i][-1]
             out[sid] = dict(logits=lbuf[off:off + n, :V1], ids=ids[off:off + n], n_ids=n_ids[i], best=best[off:off + n], n_out=n, total=total, final=fin)
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------- audio in (csrc/fbank_stream.hip states the front end's semantics)
+SAMPLE_RATE, HOP_SAMPLES = 16000, 160
+
+
+def seconds(frame: int) -> float:
+    """start time of encoder frame `frame` in its session's audio: a frame is 4 feature frames of 160 samples at 16 kHz"""
+    return frame * SUBSAMPLING * HOP_SAMPLES / SAMPLE_RATE
+
+
+def audio_pieces(n_prev: int, n_new, fed: int, C: int, finish: bool = False) -> list:
+    """The steps that a push of n_new samples brings about in a stream that has had n_prev samples and has fed `fed` of its feature frames to the encoder:
+    -> [(lo, hi, finish)], the feature frames [lo, hi) of each step in order.  Pure host arithmetic; AudioStream and AudioPool run exactly these steps, and a stream
+    fed features directly in these pieces gives the same bits.
+      * a stream that goes on feeds one whole chunk of 4*C frames for as long as it holds that many unfed frames (fbank.num_frames(n_prev + n_new) - fed of them);
+      * a stream that finishes with R unfed frames feeds k = max(0, ceil(R / 4C) - 1) whole chunks and finishes with the remaining 0 .. 4*C frames (R > 0: 1 .. 4*C);
+      * lock-step streams end inside one call: n_new is then the list of every stream's last sample count (finish only), k is taken from the largest R_b, the finish
+        step's hi is the list of every stream's end, and min R_b >= 4*C*k is required — else ValueError: a stream that ends more than a chunk before another cannot
+        share its steps; the session pool (audio_pool) lets every session end on its own."""
+    from .fbank import num_frames
+    W = SUBSAMPLING * C
+    lock = not isinstance(n_new, int)
+    news = [int(v) for v in n_new] if lock else [n_new]
+    if lock and not finish:
+        raise ValueError("audio_pieces: per-stream sample counts belong to the finishing call (lock-step streams are pushed equal counts before it)")
+    if n_prev < 0 or fed < 0 or fed % W or not news or min(news) < 0:
+        raise ValueError(f"audio_pieces: counts >= 0 and whole chunks fed, got n_prev={n_prev}, n_new={n_new}, fed={fed}")
+    ready = [num_frames(n_prev + n) - fed for n in news]
+    if min(ready) < 0:
+        raise ValueError(f"audio_pieces: {fed} frames fed, but {n_prev} + {min(news)} samples hold only {min(ready) + fed}")
+    k = max(0, -(-max(ready) // W) - 1) if finish else ready[0] // W
+    if min(ready) < W * k:
+        raise ValueError(f"audio_pieces: lock-step streams end inside one call, but they hold {ready} unfed frames: the longest still feeds {k} whole chunk(s) of {W} "
+                         f"frames that the shortest does not have.  Sessions of lengths this far apart belong in the session pool (audio_pool), where each ends on its own")
+    steps = [(fed + i * W, fed + (i + 1) * W, False) for i in range(k)]
+    if finish:
+        ends = [fed + R for R in ready]
+        steps.append((fed + k * W, ends if lock else ends[0], True))
+    return steps
+
+
+def extractor_settings(feature_extractor, num_fbanks: int) -> dict:
+    """what a `CustomFeatureExtractor` asks of the streaming front end -> dict(normalize, global_means, global_stds, tables); refuses what cannot stream"""
+    fe = feature_extractor
+    if getattr(fe, "norm_type", None) == "utterance" and getattr(fe, "do_ceptral_normalize", False):
+        raise NotImplementedError("audio streaming: the feature extractor normalises per utterance (norm_type='utterance' with do_ceptral_normalize): utterance CMVN needs "
+                                  "the whole utterance, so it cannot stream; global statistics (norm_type='global') or no normalisation stream exactly")
+    if fe.feature_size != num_fbanks:
+        raise ValueError(f"audio streaming: the feature extractor gives feature_size={fe.feature_size} values per frame, the model takes num_fbanks={num_fbanks}")
+    if getattr(fe, "norm_type", None) == "global":
+        return dict(normalize="global", global_means=fe.global_means, global_stds=fe.global_stds, tables=fe._get_tables())
+    return dict(normalize=None, tables=fe._get_tables())
+
+
+def _front_end(engine, slots, C, F, normalize, global_means, global_stds, max_push_samples, tables, what):
+    from .fbank import FbankStream, FbankTables
+    tables = FbankTables(F) if tables is None else tables
+    if tables.num_mel != F:
+        raise ValueError(f"{what}: the filterbank gives {tables.num_mel} values per frame (feature_size), the model takes num_fbanks={F}")
+    W = SUBSAMPLING * C
+    return FbankStream(slots, W, 2 * W * HOP_SAMPLES if max_push_samples is None else max_push_samples, tables, normalize=normalize, global_means=global_means,
+                       global_stds=global_stds, device=engine.device)
+
+
+def _drive(fb, flat, spans, queues, run, lockstep=False):
+    """Pushes spans {slot: (offset, n)} of `flat` in pieces of at most fb.max_push samples — one launch per piece for all slots — and after each piece calls
+    run({slot: (lo, hi, finish)}) for as long as some slot's next step (queues: audio_pieces' lists) has its frames; a finish step waits for the slot's last sample.
+    lockstep: only when every slot is due.  The ring never overruns: a slot holds at most 4*C unfed frames before a piece."""
+    done = {s: 0 for s in spans}
+    if torch.device(fb.device).type == "cuda":
+        flat = flat.to(fb.device)                       # a host tensor is copied once, by torch, not once per piece
+    while True:
+        piece = {s: (off + done[s], min(fb.max_push, n - done[s])) for s, (off, n) in spans.items() if n > done[s]}
+        if piece:
+            fb.push_flat(flat, piece)
+            for s, (_, n) in piece.items():
+                done[s] += n
+        while True:
+            due = {s: q[0] for s, q in queues.items() if q and q[0][1] <= fb.frames(s) and (not q[0][2] or done[s] == spans[s][1])}
+            if not due or (lockstep and len(due) < sum(1 for q in queues.values() if q)):
+                break
+            run(due)
+            for s in due:
+                queues[s].pop(0)
+        if not piece:
+            return
+
+
+class AudioStream:
+    """`EncoderStream` fed audio: B lock-step streams take samples in pieces of any size (the same count for all), the stateful log-mel front end (fbank.FbankStream)
+    turns them into the features `fbank_gpu` gives for the whole utterance — bit for bit — and the wrapped stream is fed the chunks `audio_pieces` names.  Created by
+    `EBranchformerEngine.audio_stream`.
+
+        s = engine.audio_stream(B, C, 1500, normalize="global", global_means=m, global_stds=sd)
+        outs = s.push(samples (B, n))                   # fp32 in [-1, 1] or int16 PCM, host or device, any n >= 0 -> the feed() dicts of the steps it ran (maybe none)
+        outs = s.finish(tail (B, n) or None, lengths)   # -> the step dicts, the last one finish()'s
+
+    The reference's dataloader-side `default_transform` (strip leading / trailing zero samples, pad to 8000) is an utterance-level step and no part of a stream: the
+    offline equivalent of a streamed session is `extract_on_device(..., default_transform=False)`."""
+
+    def __init__(self, engine, batch, chunk_frames, max_frames, *, normalize=None, global_means=None, global_stds=None, beams=None, token_topk=None, nbest=1,
+                 max_push_samples=None, tables=None):
+        self.stream = EncoderStream(engine, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
+        self.B, self.C = self.stream.B, self.stream.C
+        self.fb = _front_end(engine, self.B, self.C, self.stream.F, normalize, global_means, global_stds, max_push_samples, tables, "audio_stream()")
+        self.n = 0                                      # samples every stream has had
+        for b in range(self.B):
+            self.fb.open(b)
+
+    seconds = staticmethod(seconds)
+
+    def reset(self):
+        self.stream.reset()
+        self.n = 0
+        for b in range(self.B):
+            self.fb.open(b)
+
+    def _samples(self, x, what):
+        from .fbank import check_samples
+        check_samples(x, what)
+        if x.dim() != 2 or x.shape[0] != self.B:
+            raise ValueError(f"{what}: audio is ({self.B}, n) samples, the same n for every stream, got {tuple(x.shape)}")
+        return x.contiguous()
+
+    def _room(self, n_samples):
+        from .fbank import num_frames
+        if causal_out_frames(num_frames(n_samples)) > self.stream.max_frames:
+            raise RuntimeError(f"AudioStream: {causal_out_frames(num_frames(n_samples))} encoder frames exceed max_frames={self.stream.max_frames}")
+
+    def _run(self, flat, n, lens, steps):
+        W, outs = SUBSAMPLING * self.C, []
+        queues = {b: [(lo, hi[b] if isinstance(hi, list) else hi, fin) for lo, hi, fin in steps] for b in range(self.B)}
+
+        def run(due):
+            lo, _, fin = due[0]
+            if not fin:
+                outs.append(self.stream.feed(self.fb.pop([(b, W) for b in range(self.B)])))
+            else:
+                tails = [due[b][1] - lo for b in range(self.B)]
+                feats = self.fb.pop([(b, tails[b]) for b in range(self.B)])
+                outs.append(self.stream.finish(feats[:, :max(tails)], tails))
+        _drive(self.fb, flat, {b: (b * n, lens[b]) for b in range(self.B)}, queues, run, lockstep=True)
+        return outs
+
+    def push(self, samples: torch.Tensor) -> list:
+        """samples (B, n), any n >= 0 -> the feed() dicts of the whole chunks that became ready, in order (an empty list when none did)"""
+        self.stream._check_open("feed")
+        samples = self._samples(samples, "AudioStream.push")
+        n = int(samples.shape[1])
+        self._room(self.n + n)
+        steps = audio_pieces(self.n, n, self.stream.n_feat, self.C)
+        outs = self._run(samples.reshape(-1), n, [n] * self.B, steps)
+        self.n += n
+        return outs
+
+    def finish(self, tail: torch.Tensor | None = None, tail_lengths=None) -> list:
+        """the last samples of every stream (tail (B, n) or None; tail_lengths (B): valid samples of each stream, default n) and the flush -> the dicts of the steps:
+        whole chunks first (feed()'s), then finish()'s.  Streams whose ends lie more than a chunk apart raise ValueError before any launch (audio_pieces)."""
+        self.stream._check_open("finish")
+        if tail is None:
+            tail = torch.zeros((self.B, 0), dtype=torch.float32)
+        tail = self._samples(tail, "AudioStream.finish")
+        n = int(tail.shape[1])
+        lens = [n] * self.B if tail_lengths is None else [int(v) for v in (tail_lengths.tolist() if isinstance(tail_lengths, torch.Tensor) else tail_lengths)]
+        if len(lens) != self.B or min(lens) < 0 or max(lens) > n:
+            raise ValueError(f"AudioStream.finish: tail_lengths must be {self.B} counts in 0..{n}")
+        self._room(self.n + max(lens))
+        steps = audio_pieces(self.n, lens, self.stream.n_feat, self.C, finish=True)
+        return self._run(tail.reshape(-1), n, lens, steps)
+
+
+class AudioPool:
+    """`StreamPool` fed audio: sessions that start and end on their own push samples in pieces of any size.  Created by `EBranchformerEngine.audio_pool`.
+
+        pool = engine.audio_pool(S, C, 1500, normalize="global", global_means=m, global_stds=sd)
+        sid = pool.open()
+        out = pool.push(audio={sid: samples (n)}, finish={other: tail (n) or None})     # -> {sid: [StreamPool.step's dicts of the steps the slot took, maybe none]}
+
+    One push launch covers all named slots; `StreamPool`'s step then runs as often as some slot has a step due (`audio_pieces`), each time over exactly the slots that
+    are due, their chunks gathered by one pop.  A session's logits and ids are bit for bit those of `engine.stream(1, ...)` fed `fbank_gpu`'s features of its whole
+    audio in the same pieces."""
+
+    def __init__(self, engine, slots, chunk_frames, max_frames, *, normalize=None, global_means=None, global_stds=None, beams=None, max_push_samples=None, tables=None):
+        self.pool = StreamPool(engine, slots, chunk_frames, max_frames, beams=beams)
+        self.S, self.C = self.pool.S, self.pool.C
+        self.fb = _front_end(engine, self.S, self.C, self.pool.F, normalize, global_means, global_stds, max_push_samples, tables, "audio_pool()")
+
+    seconds = staticmethod(seconds)
+
+    def open(self) -> int:
+        sid = self.pool.open()
+        self.fb.open(sid)
+        return sid
+
+    def push(self, audio=None, finish=None) -> dict:
+        from .fbank import num_frames
+        audio, finish = dict(audio or {}), dict(finish or {})
+        pieces = {}
+        for sid in sorted(set(audio) | set(finish)):
+            if sid in audio and sid in finish:
+                raise ValueError(f"AudioPool.push: slot {sid} is named in both audio and finish")
+            if not isinstance(sid, int) or not 0 <= sid < self.S or not self.pool.is_open[sid]:
+                raise RuntimeError(f"AudioPool.push: slot {sid} holds no open session (free or finished): open() starts one")
+            pieces[sid] = audio[sid] if sid in audio else finish[sid]
+        if not pieces:
+            return {}
+        given = [x for x in pieces.values() if x is not None]
+        none = torch.zeros(0, dtype=given[0].dtype if given and isinstance(given[0], torch.Tensor) else torch.float32)      # a missing tail takes the call's dtype
+        pieces = {sid: none if x is None else x for sid, x in pieces.items()}
+        flat, spans = self.fb.flatten(pieces, "AudioPool.push")
+        queues = {}
+        for sid, (_, n) in spans.items():
+            self.pool._check_room(sid, num_frames(self.fb.n[sid] + n))
+            queues[sid] = audio_pieces(self.fb.n[sid], n, self.pool.n_feat[sid], self.C, finish=sid in finish)
+        out = {sid: [] for sid in pieces}
+
+        def run(due):
+            sids = sorted(due)
+            acts = [(sid, self.pool.n_feat[sid], due[sid][1] - due[sid][0], due[sid][2], None) for sid in sids]
+            res = self.pool._run(acts, self.fb.pop([(a[0], a[2]) for a in acts]))
+            for sid in sids:
+                out[sid].append(res[sid])
+        _drive(self.fb, flat, spans, queues, run)
         return out

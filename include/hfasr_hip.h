@@ -832,6 +832,25 @@ int mi_ebf_stream_step_slots(const mi_ebf_config* cfg, const void* const* weight
                              const float* feats, const int* records, int A, const int* table, int table_len, float* logits, int* best, int* ids, int* n_ids,
                              mi_stream_t stream);
 
+/* ---- streaming from audio: the stateful log-mel front end of the streams and the pool (csrc/fbank_stream.hip, whose header states the exact semantics).  S slots, each
+ * a carry of at most 399 samples (two buffers, a ping-pong the host chooses) and a ring of fifo_frames feature frames; state = [carry (S, 2, 400) | fifo (S, R, nmel)] fp32.
+ * Every count and position is the caller's host arithmetic; no call synchronises or reads device memory.  Pushed in pieces of any size, a session's frames are bit for
+ * bit mi_fbank_f64's (then mi_cmvn_global's) of its whole audio.  Records come twice as the pool's tables do: rec_host is checked, rec_dev is what the kernel reads.
+ * mi_fbank_stream_state_bytes: S * (2 * 400 + R * nmel) * 4; 0 when refused (a count < 1, nmel > 127).  Host only.
+ * mi_fbank_stream_push: one launch.  samples: n_samples values, fp32 in [-1, 1] (sample_dtype 0) or int16 PCM (1: (float)s / 32768.0f, exact).  Record (8 ints): slot,
+ *   N_prev, n_new, offset of the new samples in `samples`, ring write position, frames held by the ring, current carry buffer (0 / 1), 0.  Frames T(N_prev) ..
+ *   T(N_prev + n_new) - 1 (T(N) = N < 400 ? 0 : 1 + (N - 400) / 160) go to the ring, with normalize 1 as (x - means[f]) / stds[f]; the new carry, samples [160 T(N), N),
+ *   goes to the other carry buffer.  n_new = 0: the slot is untouched.  Tables, mel_floor, preemph as mi_fbank_f64's.
+ * mi_fbank_stream_pop: one launch.  Record (3 ints): slot, ring read position, n <= rows.  out (A, rows, nmel) fp32: the n frames, then zero rows.
+ * MI_ERR_ARG before any launch: a slot out of range or named twice, a ring overrun, positions outside the ring, samples outside the buffer, nmel > 127, normalize 1
+ * without tables, a state too small. */
+size_t mi_fbank_stream_state_bytes(int slots, int fifo_frames, int nmel);
+int mi_fbank_stream_push(void* state, size_t state_bytes, int slots, int fifo_frames, int nmel, const void* samples, long n_samples, int sample_dtype,
+                         const int* rec_host, const int* rec_dev, int A, const double* window, const double* twiddle, const double* mel_t, const int* mel_lo,
+                         const int* mel_hi, const float* means, const float* stds, int normalize, double mel_floor, double preemph, mi_stream_t stream);
+int mi_fbank_stream_pop(const void* state, size_t state_bytes, int slots, int fifo_frames, int nmel, const int* rec_host, const int* rec_dev, int A, float* out,
+                        int rows, mi_stream_t stream);
+
 /* ---- precision = "fp32" inference mode (csrc/gemm_f32.hip, csrc/encoder_f32.hip): the encoder + CTC head with every operand, activation and weight in fp32 — what the
  * reference's decode recipes (no --bf16) compute.  Opt-in; nothing above changes.  DESIGN.md §4 'fp32 inference mode'. */
 /* C (M,N) = resid + alpha * act(A (M,K) · W (N,K)^T + bias), all fp32, row-major with leading dimensions; act 0 none / 1 erf-GELU (exact erff) / 2 gelu_new (exact tanhf); bias, resid nullable,
