@@ -84,6 +84,8 @@ SIGNATURES = {
     "mi_ctc_beam_stream_state_bytes": [i32, i32, i32],
     "mi_ctc_beam_stream_reset": [vp, sz, i32, i32, i32, vp],
     "mi_ctc_beam_stream_walk": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
+    "mi_ctc_beam_stream_reset_slot": [vp, sz, i32, i32, i32, i32, vp],
+    "mi_ctc_beam_stream_walk_slots": [vp, i64, i32, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp],
     "mi_ctc_align_workspace_bytes": [i32, i32, i32],
     "mi_ctc_align": [vp, i64, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp],
     "mi_gemm_argmax_workspace_floats": [i32, i32],

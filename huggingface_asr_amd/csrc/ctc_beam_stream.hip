@@ -32,9 +32,11 @@
 //     [0, T_call] and to the frames left below max_frames, so the arena can never be overrun (the host refuses such a call first).  T_call = 0 is a call without
 //     frames (the logits and tables may be null): it recomputes the counts and, with final = 1, closes the stream.
 //   Limits: those of the one-shot walk with T = max_frames; max_frames W < 2^22 - 2, else MI_ERR_UNSUPPORTED; argument errors MI_ERR_ARG before any launch.
+//   The per-slot form for a session pool — the same state with B = slots, every slot with rows, `final` and start of its own — is csrc/ctc_beam_pool.hip
+//   (mi_ctc_beam_stream_reset_slot, mi_ctc_beam_stream_walk_slots); a call's body is ONE definition for both, ctc_beam_stream_body.hpp.
 //
-// ---- ctc_stream_beam_kernel: one block per stream, 256 threads when W (min(K, V1 - 1) + 1) <= 1024, else 1024, as the one-shot launch.  The beam is loaded from the
-// state into LDS slot 0 (the ping-pong parity is not state), the call's frames are walked with ctc_walk_step.hpp's frame step — the one-shot kernel's own — and the
+// ---- ctc_stream_beam_kernel: one block per stream, 256 threads when W (min(K, V1 - 1) + 1) <= 1024, else 1024, as the one-shot launch.  The body of a call
+// is ctc_beam_stream_body.hpp's stream_beam_call, here with (b, b T, n_valid[b], final, b).  The beam is loaded from the state into LDS slot 0 (the ping-pong parity is not state), the call's frames are walked with ctc_walk_step.hpp's frame step — the one-shot kernel's own — and the
 // beam is spilled back.  Table accesses stay agent-scope atomics; the kernel boundary orders them, the arena and the state between calls.  Committed prefix: wave 0,
 // one lane per hypothesis; each lane climbs its chain to the minimum length, then all lanes climb together (ballot) until their nodes agree; lane 0 appends the tokens
 // between the old committed node and the new one.  All hypotheses descend from the old committed node, so the work is bounded by the un-committed tail, not by the
@@ -44,123 +46,37 @@
 //   ctc_stream_beam_kernel   256 or 1024 threads, <= 128 VGPRs, 44576 B of LDS (the one-shot walk's: candidate keys, merge flags, the two beams); no scratch
 #include "common.hpp"
 #include "radix_select.hpp"
-#include "ctc_walk_step.hpp"
+#include "ctc_beam_stream_body.hpp"
 #include "../../include/hfasr_hip.h"
 
 namespace {
 
-constexpr int HDR_WORDS = 16;                                          // n, node count, frames walked, committed node, committed length; the rest is spare
-enum { H_N = 0, H_NODES = 1, H_FRAMES = 2, H_CNODE = 3, H_CLEN = 4 };
-
 struct StreamArgs {
-    const void* x; long ld_t, ld_b; int dtype;
-    int B, T, V1;                                                      // T: the rows of this call
+    StreamState st; StreamIo io;
+    long ld_b;
+    int B, T;                                                          // T: the rows of this call
     const int* n_valid;
-    long pad_id;
-    int W, K, nbest;
-    const float* lse; const float* lpb; const float* cut_lp; const int* cut_id;
-    int* hdr; Beam* beam;                                              // per stream: HDR_WORDS words; one Beam
-    int4* arena; long arena_stride;                                    // per stream: 1 + max_frames W nodes (parent, token, frame, length)
-    u64* table; long table_stride;                                     // per stream: the (parent node, token) -> node table, all of it in use
-    int max_frames, final;
-    int* committed; int* committed_frames; int* n_committed; int* n_new;
-    void* tokens; int* n_tokens; float* scores; int* frames;           // tokens null: no backtrace
+    int final;
 };
 
-__global__ __launch_bounds__(64) void ctc_stream_reset_kernel(int* hdr, Beam* beam, int4* arena, long arena_stride, int B) {
+__global__ __launch_bounds__(64) void ctc_stream_reset_kernel(StreamState st, int B) {
     const int b = blockIdx.x * 64 + threadIdx.x;
-    if (b >= B) return;
-    int* h = hdr + (long)b * HDR_WORDS;
-    h[H_N] = 1; h[H_NODES] = 1; h[H_FRAMES] = 0; h[H_CNODE] = 0; h[H_CLEN] = 0;
-    Beam& s = beam[b];
-    s.pb[0] = 0.f; s.pnb[0] = NEG_INF; s.sc[0] = 0.f; s.node[0] = 0; s.last[0] = -1; s.parent[0] = -1; s.len[0] = 0;
-    arena[(long)b * arena_stride] = make_int4(-1, -1, -1, 0);
+    if (b < B) stream_start(st, b);
 }
 
 template <typename TOK>
 __global__ __launch_bounds__(1024) void ctc_stream_beam_kernel(StreamArgs p) {
     __shared__ WalkLds L;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int W = p.W, T = p.T, nbest = p.nbest, MF = p.max_frames;
-    int* hdr = p.hdr + (long)b * HDR_WORDS;
-    Beam* st = p.beam + b;
-    int4* arena = p.arena + (long)b * p.arena_stride;
-    u64* table = p.table + (long)b * p.table_stride;
-    const int n0 = min(max(hdr[H_N], 0), W), t0 = min(max(hdr[H_FRAMES], 0), MF);
-    const int cnode = hdr[H_CNODE], clen = min(max(hdr[H_CLEN], 0), MF);
-    int n_call = p.n_valid ? min(max(p.n_valid[b], 0), T) : T;
-    n_call = min(n_call, MF - t0);                                     // never past the arena: 1 + max_frames W nodes
-
-    // ---- the beam, into slot 0
-    if (tid < CB_MAXW) {
-        Beam& s = L.beams[0];
-        s.pb[tid] = st->pb[tid]; s.pnb[tid] = st->pnb[tid]; s.sc[tid] = st->sc[tid];
-        s.node[tid] = st->node[tid]; s.last[tid] = st->last[tid]; s.parent[tid] = st->parent[tid]; s.len[tid] = st->len[tid];
-    }
-    if (tid == 0) L.n_nodes[0] = hdr[H_NODES];
-    __syncthreads();
-
-    // ---- this call's frames
-    const WalkIn q{p.x, p.dtype, W, p.K, min(p.K, p.V1 - 1), p.lse, p.lpb, p.cut_lp, p.cut_id, arena, p.arena_stride, table, (unsigned)p.table_stride};
-    int n = n0, cur = 0;
-    for (int t = 0; t < n_call && n > 0; ++t, cur ^= 1) n = walk_frame(L, q, cur, n, (long)b * T + t, (long)b * p.ld_b + (long)t * p.ld_t, t0 + t);
-    const Beam& s = L.beams[cur];
-
-    // ---- the committed prefix (wave 0; walk_frame's last barrier has published the beam and the nodes of this call)
-    if (tid < 64) {
-        int target = cnode, tlen = clen;                               // an empty beam commits nothing more
-        if (n > 0) {
-            if (p.final) {                                             // the rest of the best hypothesis
-                target = s.node[0]; tlen = s.len[0];
-            } else {
-                const bool mine = tid < n;
-                int nd = mine ? s.node[tid] : 0, len = mine ? s.len[tid] : 0x7FFFFFFF;
-                int lo = len;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) lo = min(lo, __shfl_xor(lo, o, 64));
-                for (int d = len; mine && d > lo && nd > 0; --d) nd = arena[nd < p.arena_stride ? nd : 0].x;
-                for (int d = lo; d > clen; --d) {                      // together, until every lane stands on the same node
-                    const int first = __shfl(nd, 0, 64);
-                    if (__ballot(mine && nd != first) == 0ull) break;
-                    if (mine && nd > 0) nd = arena[nd < p.arena_stride ? nd : 0].x;
-                    --lo;
-                }
-                target = __shfl(nd, 0, 64); tlen = lo;
-            }
-        }
-        tlen = min(max(tlen, clen), MF);
-        if (tid == 0) {
-            int nd = target;
-            for (int pos = tlen - 1; pos >= clen && nd > 0; --pos) {   // append positions clen .. tlen - 1
-                const int4 e = arena[nd < p.arena_stride ? nd : 0];
-                p.committed[(long)b * MF + pos] = e.y;
-                p.committed_frames[(long)b * MF + pos] = e.z;
-                nd = e.x;
-            }
-            p.n_committed[b] = tlen;
-            p.n_new[b] = tlen - clen;
-            hdr[H_N] = n; hdr[H_NODES] = L.n_nodes[cur]; hdr[H_FRAMES] = t0 + n_call; hdr[H_CNODE] = tlen > clen ? target : cnode; hdr[H_CLEN] = tlen;
-        }
-    }
-    // ---- the beam, back
-    if (tid < CB_MAXW) {
-        st->pb[tid] = s.pb[tid]; st->pnb[tid] = s.pnb[tid]; st->sc[tid] = s.sc[tid];
-        st->node[tid] = s.node[tid]; st->last[tid] = s.last[tid]; st->parent[tid] = s.parent[tid]; st->len[tid] = s.len[tid];
-    }
-    // ---- on request the n best, backtraced, in the one-shot entry's format (rows max_frames wide)
-    if (p.tokens)
-        walk_backtrace<TOK>(L, s, n, nbest, MF, arena, p.arena_stride, p.pad_id, (TOK*)p.tokens + (long)b * nbest * MF,
-                            p.frames ? p.frames + (long)b * nbest * MF : nullptr, p.n_tokens + (long)b * nbest, p.scores + (long)b * nbest);
+    const int b = blockIdx.x, T = p.T;
+    const int n_call = p.n_valid ? min(max(p.n_valid[b], 0), T) : T;
+    stream_beam_call<TOK>(L, p.st, p.io, b, (long)b * p.ld_b, (long)b * T, n_call, p.final, p.io.tokens ? b : -1);
 }
-
-bool stream_sizes_ok(int B, int max_frames, int W) { return B > 0 && max_frames > 0 && W >= 1 && W <= CB_MAXW && walk_sizes_ok(max_frames, W, 2); }
-size_t head_bytes(int B) { return (size_t)B * (HDR_WORDS * sizeof(int) + sizeof(Beam)); }
 
 }  // namespace
 
 extern "C" size_t mi_ctc_beam_stream_state_bytes(int B, int max_frames, int W) {
     if (!stream_sizes_ok(B, max_frames, W)) return 0;
-    return head_bytes(B) + align16((size_t)B * (1 + (size_t)max_frames * W) * sizeof(int4)) + (size_t)B * table_words(max_frames, W) * sizeof(u64);
+    return stream_head_bytes(B) + align16((size_t)B * (1 + (size_t)max_frames * W) * sizeof(int4)) + (size_t)B * table_words(max_frames, W) * sizeof(u64);
 }
 
 extern "C" int mi_ctc_beam_stream_reset(void* state, size_t state_bytes, int B, int max_frames, int W, hipStream_t stream) {
@@ -170,9 +86,7 @@ extern "C" int mi_ctc_beam_stream_reset(void* state, size_t state_bytes, int B, 
     const size_t need = mi_ctc_beam_stream_state_bytes(B, max_frames, W);
     if (state_bytes < need || (reinterpret_cast<uintptr_t>(state) & 15)) return MI_ERR_ARG;
     if (hipMemsetAsync(state, 0, need, stream) != hipSuccess) return MI_ERR_LAUNCH;
-    char* base = (char*)state;
-    hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, (int*)base, (Beam*)(base + (size_t)B * HDR_WORDS * sizeof(int)),
-                       (int4*)(base + head_bytes(B)), 1 + (long)max_frames * W, B);
+    hipLaunchKernelGGL(ctc_stream_reset_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, stream_state_at(state, B, max_frames, W), B);
     MI_CHECK_LAUNCH();
     return MI_OK;
 }
@@ -192,12 +106,10 @@ extern "C" int mi_ctc_beam_stream_walk(const void* logits, long ld_row, long ld_
     if (!walk_sizes_ok(max_frames, W, V1)) return MI_ERR_UNSUPPORTED;
     if ((long)B * T_call >= (1l << 31)) return MI_ERR_UNSUPPORTED;
     if (state_bytes < mi_ctc_beam_stream_state_bytes(B, max_frames, W) || (reinterpret_cast<uintptr_t>(state) & 15)) return MI_ERR_ARG;
-    const long nodes = 1 + (long)max_frames * W, words = table_words(max_frames, W);
-    char* base = (char*)state;
-    StreamArgs a{logits, ld_row, ld_batch, dtype, B, T_call, V1, n_valid, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id,
-                 (int*)base, (Beam*)(base + (size_t)B * HDR_WORDS * sizeof(int)), (int4*)(base + head_bytes(B)), nodes,
-                 (u64*)(base + head_bytes(B) + align16((size_t)B * nodes * sizeof(int4))), words, max_frames, final,
-                 committed, committed_frames, n_committed, n_new, tokens, n_tokens, scores, frames};
+    StreamArgs a{stream_state_at(state, B, max_frames, W),
+                 StreamIo{logits, ld_row, dtype, V1, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id, committed, committed_frames, n_committed, n_new, tokens, n_tokens,
+                          scores, frames},
+                 ld_batch, B, T_call, n_valid, final};
     const int Kk = K < V1 - 1 ? K : V1 - 1;
     const dim3 block(W * (Kk + 1) <= 1024 ? 256 : 1024);
     if (tokens_dtype == 0) hipLaunchKernelGGL(ctc_stream_beam_kernel<int>, dim3(B), block, 0, stream, a);

@@ -1,7 +1,8 @@
-// The frame step of the CTC prefix beam search, ONE definition for the two kernels that walk frames with it: ctc_walk_kernel (ctc_beam.hip, a whole utterance per
-// launch) and ctc_stream_beam_kernel (ctc_beam_stream.hip, the same walk suspended between launches).  ctc_beam.hip's header states the semantics; this file holds
-// the state (Beam), the block's LDS (WalkLds), the step (walk_frame) and the backtrace of the n best (walk_backtrace).  Both kernels must take the same decisions and
-// sum in the same order, bit for bit: whatever changes here changes both.
+// The frame step of the CTC prefix beam search, ONE definition for the kernels that walk frames with it: ctc_walk_kernel (ctc_beam.hip, a whole utterance per
+// launch) and, through ctc_beam_stream_body.hpp, ctc_stream_beam_kernel (ctc_beam_stream.hip, the same walk suspended between launches) and ctc_pool_beam_kernel
+// (ctc_beam_pool.hip, that per slot of a session pool).  ctc_beam.hip's header states the semantics; this file holds the state (Beam), the block's LDS (WalkLds), the
+// step (walk_frame) and the backtrace of the n best (walk_backtrace).  All of them must take the same decisions and sum in the same order, bit for bit: whatever
+// changes here changes all.
 #pragma once
 #include "common.hpp"
 #include "radix_select.hpp"

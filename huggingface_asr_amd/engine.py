@@ -383,7 +383,10 @@ class EBranchformerEngine:
         """Streaming inference for sessions that start, idle and end on their own: -> streaming.StreamPool of `slots` slots over one state.  `open()` gives a free slot;
         `step(feed={slot: chunk}, finish={slot: tail})` advances the named slots — one set of launches over the rows of all of them —, leaves the others untouched and
         frees the finished ones.  A session's logits and ids are bit for bit those of `stream(1, chunk_frames, max_frames)` fed the same pieces, whatever the other slots
-        do (csrc/stream_pool.hip; DESIGN.md §4 'Session pool').  Refusals as `stream`'s; beams= raises NotImplementedError."""
+        do (csrc/stream_pool.hip; DESIGN.md §4 'Session pool').  `.with_beams(W, token_topk=None, nbest=1)` on the pool, before the first open(), adds the prefix beam
+        search of `stream(beams=W)` per slot: every step dict gains "beam" (committed tokens per step; the n-best at finish or with step(..., partial=)), bit for bit
+        what `stream(1, chunk_frames, max_frames, beams=W)` gives for the same pieces (csrc/ctc_beam_pool.hip; DESIGN.md §4 'Beam search on the pool').  Refusals as
+        `stream`'s; the beams= keyword raises NotImplementedError and names `with_beams`."""
         from .streaming import StreamPool
         return StreamPool(self, slots, chunk_frames, max_frames, beams=beams)
 
@@ -400,7 +403,8 @@ class EBranchformerEngine:
     def audio_pool(self, slots: int, chunk_frames: int, max_frames: int, *, normalize=None, global_means=None, global_stds=None, beams=None, max_push_samples=None,
                    tables=None):
         """`stream_pool` fed audio: -> streaming.AudioPool.  `open()` starts a session, `push(audio={sid: samples}, finish={sid: tail or None})` takes any sizes for
-        any subset of the open slots and returns {sid: [the dicts of the steps the slot took]}.  Refusals as `stream_pool`'s (beams= included) and `audio_stream`'s."""
+        any subset of the open slots and returns {sid: [the dicts of the steps the slot took]}.  `.with_beams(W, ...)` as on `stream_pool`; `push(..., partial=)` then asks
+        for the n-best so far.  Refusals as `stream_pool`'s (the beams= keyword included) and `audio_stream`'s."""
         from .streaming import AudioPool
         return AudioPool(self, slots, chunk_frames, max_frames, normalize=normalize, global_means=global_means, global_stds=global_stds, beams=beams,
                          max_push_samples=max_push_samples, tables=tables)

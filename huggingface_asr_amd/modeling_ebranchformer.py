@@ -330,7 +330,8 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
 
     def stream_pool(self, slots: int, chunk_frames: int, max_frames: int, device=None, *, beams=None):
         """Streaming inference for sessions that start, idle and end on their own (eval mode only): -> streaming.StreamPool over this model's weights, as
-        EBranchformerEngine.stream_pool describes it (DESIGN.md §4 'Session pool')."""
+        EBranchformerEngine.stream_pool describes it (DESIGN.md §4 'Session pool'); `.with_beams(W, token_topk=None, nbest=1)` on it adds the CTC prefix beam search per
+        slot ('Beam search on the pool')."""
         if self.training:
             raise RuntimeError("stream_pool() is an inference call: put the model in eval mode first (model.eval())")
         dev = device if device is not None else next(self.parameters()).device
@@ -356,7 +357,7 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
         return eng.audio_stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, **settings)
 
     def audio_pool(self, feature_extractor, slots: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, max_push_samples=None):
-        """`stream_pool` fed audio (eval mode only): -> streaming.AudioPool; the extractor is read as `audio_stream` reads it."""
+        """`stream_pool` fed audio (eval mode only): -> streaming.AudioPool; the extractor is read as `audio_stream` reads it.  `.with_beams(W, ...)` as on `stream_pool`."""
         eng, settings = self._audio_engine(feature_extractor, device, "audio_pool()")
         return eng.audio_pool(slots, chunk_frames, max_frames, beams=beams, max_push_samples=max_push_samples, **settings)
 

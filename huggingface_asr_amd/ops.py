@@ -669,6 +669,27 @@ def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=No
     return out
 
 
+def _beam_stream_args(what, count_name, count_noun, count, max_frames, beams, token_topk, nbest, blank, dtype):
+    """the constructor checks of CtcBeamStream and CtcBeamPool: one table, one wording"""
+    ints = lambda *v: all(isinstance(x, int) and not isinstance(x, bool) for x in v)
+    if not ints(count, max_frames, beams, nbest, blank):
+        raise TypeError(f"{what}: {count_name}, max_frames, beams, nbest and blank are ints")
+    if token_topk is not None and not ints(token_topk):
+        raise TypeError(f"{what}: token_topk is an int or None")
+    if count < 1 or max_frames < 1:
+        raise ValueError(f"{what}: at least one {count_noun} and one frame, got {count_name}={count}, max_frames={max_frames}")
+    if not 1 <= beams <= 64:
+        raise ValueError(f"{what}: beams must be in 1..64, got {beams}")
+    if not 1 <= nbest <= beams:
+        raise ValueError(f"{what}: nbest must be in 1..beams, got {nbest} with {beams} beams")
+    if token_topk is not None and not 1 <= token_topk <= 64:
+        raise ValueError(f"{what}: token_topk must be in 1..64, got {token_topk}")
+    if blank < 0:
+        raise ValueError(f"{what}: blank {blank} is negative")
+    if dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"{what}: token dtype int32 or int64")
+
+
 class CtcBeamStream:
     """CTC prefix beam search on a stream (csrc/ctc_beam_stream.hip states the semantics): ctc_beam_decode's walk for `batch` streams in lock-step, suspended between
     calls.  After every `feed` the beam is bit for bit the beam ctc_beam_decode holds after the same frames of the concatenated logits, however they were split.
@@ -685,23 +706,7 @@ class CtcBeamStream:
     (an upper bound when n_valid is given: the counts stay on the device) and refuses, before any launch, a call that could pass max_frames."""
 
     def __init__(self, batch, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False):
-        ints = lambda *v: all(isinstance(x, int) and not isinstance(x, bool) for x in v)
-        if not ints(batch, max_frames, beams, nbest, blank):
-            raise TypeError("CtcBeamStream: batch, max_frames, beams, nbest and blank are ints")
-        if token_topk is not None and not ints(token_topk):
-            raise TypeError("CtcBeamStream: token_topk is an int or None")
-        if batch < 1 or max_frames < 1:
-            raise ValueError(f"CtcBeamStream: at least one stream and one frame, got batch={batch}, max_frames={max_frames}")
-        if not 1 <= beams <= 64:
-            raise ValueError(f"CtcBeamStream: beams must be in 1..64, got {beams}")
-        if not 1 <= nbest <= beams:
-            raise ValueError(f"CtcBeamStream: nbest must be in 1..beams, got {nbest} with {beams} beams")
-        if token_topk is not None and not 1 <= token_topk <= 64:
-            raise ValueError(f"CtcBeamStream: token_topk must be in 1..64, got {token_topk}")
-        if blank < 0:
-            raise ValueError(f"CtcBeamStream: blank {blank} is negative")
-        if dtype not in (torch.int32, torch.int64):
-            raise TypeError("CtcBeamStream: token dtype int32 or int64")
+        _beam_stream_args("CtcBeamStream", "batch", "stream", batch, max_frames, beams, token_topk, nbest, blank, dtype)
         self.B, self.max_frames, self.beams, self.token_topk, self.nbest = batch, max_frames, beams, token_topk, nbest
         self.blank, self.pad_id, self.dtype, self.return_frames = blank, int(pad_id), dtype, bool(return_frames)
         self.state_bytes = int(_lib.lib().mi_ctc_beam_stream_state_bytes(batch, max_frames, beams))
@@ -776,6 +781,137 @@ class CtcBeamStream:
         self.finished = bool(final)
         out = dict(committed=self.committed, committed_frames=self.committed_frames, n_committed=self.n_committed, n_new=self.n_new)
         if want:
+            out.update(tokens=tokens, n_tokens=n, scores=scores)
+            if self.return_frames:
+                out["frames"] = frames
+        return out
+
+
+class CtcBeamPool:
+    """CTC prefix beam search on the slots of a session pool (csrc/ctc_beam_pool.hip states the semantics): CtcBeamStream's walk per slot, every slot a session with
+    rows, an end and a start of its own.  A session's beam is bit for bit that of `CtcBeamStream(1, ...)` fed the same pieces, whatever the other slots do.
+
+        bp = ops.CtcBeamPool(slots, max_frames, beams=10, blank=V, pad_id=0)
+        bp.open(slot)                              # the slot back to a stream start; no other slot is touched
+        out = bp.step(logits, [(slot, row0, n, final, partial), ...])      # logits (rows, V+1) f32|bf16: the step's compact rows; a record's rows are [row0, row0 + n)
+
+    step -> dict(committed, committed_frames (slots, max_frames) int32, n_committed, n_new (slots) int32): the pool's own buffers, a row per slot, updated in place by
+    the next call that names the slot and cleared by its next `open`.  For the records with final or partial also tokens (R, nbest, max_frames) `dtype`, n_tokens,
+    scores (R, nbest)[, frames], compact in record order, and rows {slot: row}.  mi_ctc_beam_cut over the compact rows (skipped without rows), then
+    mi_ctc_beam_stream_walk_slots: at most two launches, no host synchronisation.  `walked[slot]` counts a session's frames exactly (every row of a record is valid);
+    a record that would pass max_frames, or names a slot that is not open or already final, is refused before any launch."""
+
+    REC_WORDS = 5
+
+    def __init__(self, slots, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False):
+        _beam_stream_args("CtcBeamPool", "slots", "slot", slots, max_frames, beams, token_topk, nbest, blank, dtype)
+        self.S, self.max_frames, self.beams, self.token_topk, self.nbest = slots, max_frames, beams, token_topk, nbest
+        self.blank, self.pad_id, self.dtype, self.return_frames = blank, int(pad_id), dtype, bool(return_frames)
+        self.state_bytes = int(_lib.lib().mi_ctc_beam_stream_state_bytes(slots, max_frames, beams))
+        if self.state_bytes == 0:
+            raise ValueError(f"CtcBeamPool: {max_frames} frames x {beams} beams is beyond the node table (max_frames * beams < 2^22 - 2)")
+        self.walked = [0] * slots                  # frames the slot's session has walked
+        self.is_open = [False] * slots             # opened and not yet final
+        self.V1 = None
+        self._state = None
+
+    def _allocate(self, dev):
+        """the state of all slots, every one at a stream start (a slot opened before this needs no reset of its own)"""
+        S, M = self.S, self.max_frames
+        self._state = torch.empty((self.state_bytes,), device=dev, dtype=torch.uint8)
+        self.committed = torch.full((S, M), self.pad_id, device=dev, dtype=torch.int32)
+        self.committed_frames = torch.full((S, M), -1, device=dev, dtype=torch.int32)
+        self.n_committed = torch.zeros((S,), device=dev, dtype=torch.int32)
+        self.n_new = torch.zeros((S,), device=dev, dtype=torch.int32)
+        rc = _lib.lib().mi_ctc_beam_stream_reset(self._state.data_ptr(), self.state_bytes, S, M, self.beams, _stream())
+        _lib.check(rc, "mi_ctc_beam_stream_reset")
+
+    def open(self, slot):
+        """the slot back to a stream start: its beam state (mi_ctc_beam_stream_reset_slot: one launch and a memset of the slot's node table), its committed row to pad,
+        committed_frames to -1, its counts to 0, walked[slot] = 0.  Before the first device step there is no state yet: it is then created with every slot at its start."""
+        if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.S:
+            raise ValueError(f"CtcBeamPool.open: slot {slot!r} outside [0, {self.S})")
+        if self._state is not None:
+            rc = _lib.lib().mi_ctc_beam_stream_reset_slot(self._state.data_ptr(), self.state_bytes, self.S, self.max_frames, self.beams, slot, _stream())
+            _lib.check(rc, "mi_ctc_beam_stream_reset_slot")
+            self.committed[slot].fill_(self.pad_id)
+            self.committed_frames[slot].fill_(-1)
+            self.n_committed[slot].zero_()
+            self.n_new[slot].zero_()
+        self.walked[slot] = 0
+        self.is_open[slot] = True
+
+    def records(self, records, rows):
+        """the checked records of a step -> (A x [slot, row0, n, final, out], rows {slot: out} of the records with final or partial); host arithmetic, nothing moves"""
+        recs, outs = [], {}
+        for r in records:
+            if len(r) != 5:
+                raise ValueError(f"CtcBeamPool.step: a record is (slot, row0, n, final, partial), got {r!r}")
+            slot, row0, n, final, partial = r
+            if not all(isinstance(v, int) and not isinstance(v, bool) for v in (slot, row0, n)):
+                raise TypeError(f"CtcBeamPool.step: slot, row0 and n are ints, got {r!r}")
+            if not 0 <= slot < self.S or not self.is_open[slot]:
+                raise RuntimeError(f"CtcBeamPool.step: slot {slot} holds no open beam (not opened, or already final): open() starts one")
+            if slot in (q[0] for q in recs):
+                raise ValueError(f"CtcBeamPool.step: slot {slot} is named twice")
+            if row0 < 0 or n < 0 or row0 + n > rows:
+                raise ValueError(f"CtcBeamPool.step: rows [{row0}, {row0} + {n}) of slot {slot} lie outside the {rows} rows of the logits")
+            if self.walked[slot] + n > self.max_frames:
+                raise RuntimeError(f"CtcBeamPool.step: {self.walked[slot]} + {n} frames of slot {slot} exceed max_frames={self.max_frames}")
+            out = -1
+            if final or partial:
+                out = outs[slot] = len(outs)
+            recs.append([slot, row0, n, int(bool(final)), out])
+        if not recs:
+            raise ValueError("CtcBeamPool.step: no records")
+        return recs, outs
+
+    def step(self, logits, records, *, records_dev=None):
+        """records_dev: the checked records (`self.records`) as 5 A int32 on the device, when the caller has uploaded them with a transfer of its own (StreamPool: they
+        ride behind the step's descriptor table); None: they are uploaded here from a pinned buffer."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype not in (torch.float32, BF16):
+            raise TypeError("CtcBeamPool.step: (rows, V+1) fp32 / bf16 logits")
+        rows, V1 = logits.shape
+        if V1 < 2 or self.blank >= V1 or (self.V1 is not None and V1 != self.V1):
+            raise ValueError(f"CtcBeamPool.step: logits of (rows, {self.V1 or 'V+1'}) with blank {self.blank} inside, got {tuple(logits.shape)}")
+        recs, outs = self.records(records, rows)
+        _req(logits)
+        dev = logits.device
+        if rows and logits.stride(1) != 1:
+            logits = logits.contiguous()
+        A, R, nb, M = len(recs), len(outs), self.nbest, self.max_frames
+        K = min(self.beams, V1 - 1) if self.token_topk is None else self.token_topk
+        host = torch.tensor(recs, dtype=torch.int32).reshape(-1)
+        if records_dev is None:
+            pinned = torch.empty((A * self.REC_WORDS,), dtype=torch.int32, pin_memory=True)
+            pinned.copy_(host)
+            records_dev = pinned.to(dev, non_blocking=True)
+        elif records_dev.dtype != torch.int32 or records_dev.numel() != A * self.REC_WORDS or not records_dev.is_cuda or not records_dev.is_contiguous():
+            raise ValueError(f"CtcBeamPool.step: records_dev holds the {A} x {self.REC_WORDS} int32 of the records on the device")
+        if self._state is None:
+            self._allocate(dev)
+        if rows:
+            cut = ctc_beam_cut(logits.unsqueeze(0), self.blank, K)
+            lse, lpb, lp, ids = cut["lse"], cut["lp_blank"], cut["lp"], cut["ids"]
+        else:
+            lse = lpb = lp = ids = None
+        tokens = torch.empty((R, nb, M), device=dev, dtype=self.dtype) if R else None
+        n = torch.empty((R, nb), device=dev, dtype=torch.int32) if R else None
+        scores = torch.empty((R, nb), device=dev, dtype=torch.float32) if R else None
+        frames = torch.empty((R, nb, M), device=dev, dtype=torch.int32) if R and self.return_frames else None
+        rc = _lib.lib().mi_ctc_beam_stream_walk_slots(logits.data_ptr() if rows else None, logits.stride(0) if rows else 0, 0 if logits.dtype == torch.float32 else 1, rows, V1,
+                                                      self.blank, self.pad_id, self.beams, K, nb, _p(lse), _p(lpb), _p(lp), _p(ids), self._state.data_ptr(), self.state_bytes,
+                                                      self.S, M, host.data_ptr(), A, records_dev.data_ptr(), self.committed.data_ptr(), self.committed_frames.data_ptr(),
+                                                      self.n_committed.data_ptr(), self.n_new.data_ptr(), _p(tokens), int(self.dtype == torch.int64), _p(n), _p(scores),
+                                                      _p(frames), R, _stream())
+        _lib.check(rc, "mi_ctc_beam_stream_walk_slots")
+        self.V1 = V1
+        for slot, _, cnt, final, _ in recs:
+            self.walked[slot] += cnt
+            if final:
+                self.is_open[slot] = False
+        out = dict(committed=self.committed, committed_frames=self.committed_frames, n_committed=self.n_committed, n_new=self.n_new, rows=outs)
+        if R:
             out.update(tokens=tokens, n_tokens=n, scores=scores)
             if self.return_frames:
                 out["frames"] = frames

@@ -17,6 +17,11 @@ Sessions that start, idle and end on their own share one state as a pool of slot
     sid = pool.open()                   # a free slot, started on the device without touching the others
     out = pool.step(feed={sid: chunk (4*C, F)}, finish={other: tail (0..4*C, F) or None})      # -> {slot: dict(logits (n_out, V+1), ids, n_ids, n_out, total, final)}
 
+The pool walks the same prefix beam search per slot once it is switched on (csrc/ctc_beam_pool.hip; ops.CtcBeamPool), for audio pools too:
+
+    pool = engine.stream_pool(S, C, 1500).with_beams(10, nbest=4)         # before the first open()
+    out[sid]["beam"]                    # per step: committed / committed_frames (max_frames) int32 then -1, n_committed, n_new; at finish or with partial= also the n-best
+
 Both take audio instead of feature frames through the stateful log-mel front end (csrc/fbank_stream.hip; `AudioStream`, `AudioPool`, `audio_pieces` below):
 
     pool = engine.audio_pool(slots=S, chunk_frames=C, max_frames=1500, normalize="global", global_means=m, global_stds=s)
@@ -252,8 +257,8 @@ class StreamPool:
     def __init__(self, engine, slots: int, chunk_frames: int, max_frames: int, *, beams=None):
         c = _check_streamable(engine, slots, chunk_frames, max_frames, "stream_pool()", "slots")
         if beams is not None:
-            raise NotImplementedError("stream_pool(): beams= is not implemented for the pool (the streaming beam search advances its streams in lock-step): use "
-                                      "engine.stream(1, ..., beams=) per session")
+            raise NotImplementedError("stream_pool(): beams= is not a constructor keyword of the pool: the prefix beam search per slot is switched on by a method, "
+                                      "stream_pool(...).with_beams(beams, token_topk=None, nbest=1), before the first session is opened")
         self.engine, self.S, self.C, self.max_frames = engine, int(slots), int(chunk_frames), int(max_frames)
         self.L = c["num_hidden_layers"]
         self.r = (c.get("merge_conv_kernel", 31) - 1) // 2
@@ -264,6 +269,21 @@ class StreamPool:
         self.total = [0] * self.S                       # frames it has emitted
         self._state = None
         self._cs = None
+        self.beam = None                                # with_beams(): the prefix beam search walks every slot's emitted frames too (ops.CtcBeamPool)
+
+    def with_beams(self, beams, *, token_topk=None, nbest=1):
+        """Switches on the CTC prefix beam search per slot (ops.CtcBeamPool, csrc/ctc_beam_pool.hip) -> the pool itself.  Every session then walks `beams` (1..64)
+        hypotheses over the `token_topk` best classes of the frames it emits, as `engine.stream(1, C, max_frames, beams=, token_topk=, nbest=)` would for the same
+        pieces — bit for bit —, and `step` adds "beam" to every named slot's dict.  Allowed only while no session is open (RuntimeError); the checks are those of
+        `engine.stream(beams=)` (ValueError / TypeError; max_frames * beams < 2^22 - 2).  Nothing is allocated before the first device step.  Per step the beam adds
+        two kernels (the token cut over the step's compact logits and one walk block per named slot), one small copy (the step's counts) and no transfer: its records
+        ride behind the descriptor table."""
+        if any(self.is_open):
+            raise RuntimeError("StreamPool.with_beams: sessions are open; the beam search is switched on before the first open()")
+        from . import ops
+        self.beam = ops.CtcBeamPool(self.S, self.max_frames, beams=beams, token_topk=token_topk, nbest=nbest, blank=self.engine.cfg["vocab_size"], pad_id=-1,
+                                    dtype=torch.int32, return_frames=True)
+        return self
 
     # ------------------------------------------------------------------ state
     def _config(self):
@@ -305,7 +325,8 @@ class StreamPool:
 
     # ------------------------------------------------------------------ sessions
     def open(self) -> int:
-        """-> a free slot, started: zero histories and rings, no carried class (a per-slot reset on the device, enqueued on the current stream)"""
+        """-> a free slot, started: zero histories and rings, no carried class (a per-slot reset on the device, enqueued on the current stream); after with_beams()
+        also the slot's beam at its start and its committed row cleared"""
         free = [s for s in range(self.S) if not self.is_open[s]]
         if not free:
             raise RuntimeError(f"StreamPool.open: all {self.S} slots hold open sessions")
@@ -315,6 +336,8 @@ class StreamPool:
             rc = _lib.lib().mi_ebf_stream_reset_slot(C.byref(self._config()), self.C, self.max_frames, self._state.data_ptr(), self._state.numel(), sid,
                                                      torch.cuda.current_stream().cuda_stream)
             _lib.check(rc, "mi_ebf_stream_reset_slot")
+        if self.beam is not None:
+            self.beam.open(sid)
         self.is_open[sid] = True
         self.n_feat[sid] = self.total[sid] = 0
         return sid
@@ -360,9 +383,30 @@ class StreamPool:
                 self.is_open[sid] = False
         return res
 
-    def step(self, feed=None, finish=None) -> dict:
+    def _partial(self, partial, what):
+        """`partial` of step / push -> None (nobody), True (every named slot) or the set of slot ids"""
+        if partial is None or partial is False:
+            return None
+        if self.beam is None:
+            raise ValueError(f"{what}: partial asks for the beam search's n-best: switch it on with with_beams() first")
+        if partial is True:
+            return True
+        if isinstance(partial, (str, bytes, torch.Tensor)) or not hasattr(partial, "__iter__"):
+            raise TypeError(f"{what}: partial is True or a collection of slot ids")
+        ids = set(partial)
+        if not all(isinstance(v, int) and not isinstance(v, bool) and 0 <= v < self.S for v in ids):
+            raise ValueError(f"{what}: partial names slots in [0, {self.S}), got {sorted(ids, key=repr)}")
+        return ids
+
+    def step(self, feed=None, finish=None, partial=False) -> dict:
         """feed {slot: chunk (4*C, F)}, finish {slot: tail (0..4*C, F) or None}; every other slot is idle.  -> {slot: dict(logits (n_out, V+1) fp32, ids (n_out) int32 =
-        the greedy tokens newly emitted then -1, n_ids (0-d int32), n_out, total, final)} for the named slots.  A finished slot is free after the call."""
+        the greedy tokens newly emitted then -1, n_ids (0-d int32), n_out, total, final)} for the named slots.  A finished slot is free after the call.
+        After with_beams() every named slot's dict also holds "beam": dict(committed (max_frames) int32 then -1, committed_frames, n_committed, n_new (0-d int32)) — the
+        tokens every hypothesis of the slot's beam begins with, the frame each entered at, how many there are and how many this step appended.  committed and
+        committed_frames are VIEWS of the pool's row for that slot: append-only during a session — the first n_committed entries of a step never change, later steps
+        write behind them — and reset by the slot's next session (open()), so copy what must outlive that.  The two counts are the step's own.  For a finishing slot, and for those `partial` names (True: every named slot; or a collection of slot ids), "beam" also holds the n-best: tokens (nbest, max_frames)
+        int32 then -1, n_tokens (nbest), scores (nbest) fp32, frames (nbest, max_frames); after a finish committed[:n_committed] is hypothesis 0."""
+        partial = self._partial(partial, "StreamPool.step")
         acts = self.actions(feed, finish)
         if not acts:
             return {}
@@ -372,11 +416,11 @@ class StreamPool:
         dev, W = e.device, SUBSAMPLING * self.C
         zero = lambda n: torch.zeros((n, self.F), dtype=torch.float32, device=dev)
         feats = torch.stack([x.to(torch.float32) if n == W else (zero(W) if n == 0 else torch.cat([x.to(torch.float32), zero(W - n)])) for _, _, n, _, x in acts])   # a tail zero-padded
-        return self._run(acts, feats)
+        return self._run(acts, feats, partial)
 
-    def _run(self, acts, feats) -> dict:
+    def _run(self, acts, feats, partial=None) -> dict:
         """the step of checked actions [(slot, n_prev, n, finish, _)] on their compact chunks feats (A, 4*C, F) fp32, tails zero-padded (AudioPool hands over
-        fbank.FbankStream.pop's buffer as it is)"""
+        fbank.FbankStream.pop's buffer as it is); partial: `_partial`'s None, True or set of slots"""
         e = self.engine
         if not torch.device(e.device).type == "cuda":
             raise RuntimeError("StreamPool needs device tensors (no CPU fallback)")
@@ -387,10 +431,18 @@ class StreamPool:
         rec = torch.tensor(records, dtype=torch.int32)
         words = lib.mi_ebf_stream_slots_table(C.byref(cs), self.C, self.max_frames, rec.data_ptr(), A, None, 0)
         _lib.check(min(words, 0), "mi_ebf_stream_slots_table")
-        host = torch.empty((words,), dtype=torch.int32, pin_memory=True)
-        _lib.check(min(lib.mi_ebf_stream_slots_table(C.byref(cs), self.C, self.max_frames, rec.data_ptr(), A, host.data_ptr(), words), 0), "mi_ebf_stream_slots_table")
-        table = host.to(dev, non_blocking=True)         # the step's one host-to-device transfer
         n_out = totals[-1]
+        brecs = None
+        if self.beam is not None:                       # a slot's rows in the step's compact logits: (off_L, hi_L - lo_L) of its record; checked before any launch
+            wanted = lambda sid: partial is True or (partial is not None and sid in partial)
+            beam_in = [(a[0], r[-1], r[-2] - r[-3], bool(a[3]), wanted(a[0])) for a, r in zip(acts, records)]
+            brecs, _ = self.beam.records(beam_in, n_out)
+        extra = 0 if brecs is None else A * self.beam.REC_WORDS
+        host = torch.empty((words + extra,), dtype=torch.int32, pin_memory=True)
+        _lib.check(min(lib.mi_ebf_stream_slots_table(C.byref(cs), self.C, self.max_frames, rec.data_ptr(), A, host.data_ptr(), words), 0), "mi_ebf_stream_slots_table")
+        if extra:
+            host[words:] = torch.tensor(brecs, dtype=torch.int32).reshape(-1)      # the beam's records ride behind the table
+        table = host.to(dev, non_blocking=True)         # the step's one host-to-device transfer
         lbuf = torch.empty((n_out, cs.logits_ld), dtype=torch.float32, device=dev)
         best = torch.empty((n_out,), dtype=torch.int32, device=dev)
         ids = torch.empty((n_out,), dtype=torch.int32, device=dev)
@@ -400,10 +452,18 @@ class StreamPool:
                                           rec.data_ptr(), A, table.data_ptr(), words, p(lbuf), p(best), p(ids), n_ids.data_ptr(),
                                           torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "mi_ebf_stream_step_slots")
+        bout = None if self.beam is None else self.beam.step(lbuf[:, :V1], beam_in, records_dev=table[words:])
+        counts = None if bout is None else torch.stack((bout["n_committed"], bout["n_new"]))      # this step's own copy: a push may run several steps before it returns
         out = {}
         for i, (sid, (n, total, fin)) in enumerate(self._advance(acts, records).items()):
             off = records[i][-1]
             out[sid] = dict(logits=lbuf[off:off + n, :V1], ids=ids[off:off + n], n_ids=n_ids[i], best=best[off:off + n], n_out=n, total=total, final=fin)
+            if bout is not None:
+                b = dict(committed=bout["committed"][sid], committed_frames=bout["committed_frames"][sid], n_committed=counts[0, sid], n_new=counts[1, sid])
+                if sid in bout["rows"]:
+                    row = bout["rows"][sid]
+                    b.update(tokens=bout["tokens"][row], n_tokens=bout["n_tokens"][row], scores=bout["scores"][row], frames=bout["frames"][row])
+                out[sid]["beam"] = b
         return out
 
 
@@ -595,13 +655,21 @@ class AudioPool:
 
     seconds = staticmethod(seconds)
 
+    def with_beams(self, beams, *, token_topk=None, nbest=1):
+        """`StreamPool.with_beams` on the wrapped pool -> this pool: every step dict of a slot then holds "beam"; `push(..., partial=)` asks for the n-best so far"""
+        self.pool.with_beams(beams, token_topk=token_topk, nbest=nbest)
+        return self
+
     def open(self) -> int:
         sid = self.pool.open()
         self.fb.open(sid)
         return sid
 
-    def push(self, audio=None, finish=None) -> dict:
+    def push(self, audio=None, finish=None, partial=False) -> dict:
+        """audio {slot: samples (n)}, finish {slot: tail (n) or None} -> {slot: [StreamPool.step's dicts of the steps the slot took]}.  partial (after with_beams():
+        True or a collection of slot ids) goes to every step the push runs: those slots' "beam" dicts then hold the n-best so far."""
         from .fbank import num_frames
+        partial = self.pool._partial(partial, "AudioPool.push")
         audio, finish = dict(audio or {}), dict(finish or {})
         pieces = {}
         for sid in sorted(set(audio) | set(finish)):
@@ -625,7 +693,7 @@ class AudioPool:
         def run(due):
             sids = sorted(due)
             acts = [(sid, self.pool.n_feat[sid], due[sid][1] - due[sid][0], due[sid][2], None) for sid in sids]
-            res = self.pool._run(acts, self.fb.pop([(a[0], a[2]) for a in acts]))
+            res = self.pool._run(acts, self.fb.pop([(a[0], a[2]) for a in acts]), partial)
             for sid in sids:
                 out[sid].append(res[sid])
         _drive(self.fb, flat, spans, queues, run)

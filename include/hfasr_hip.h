@@ -295,6 +295,26 @@ int mi_ctc_beam_stream_walk(const void* logits, long ld_row, long ld_batch, int 
                             int nbest, const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* state, size_t state_bytes, int max_frames,
                             int final, int* committed, int* committed_frames, int* n_committed, int* n_new, void* tokens, int tokens_dtype, int* n_tokens,
                             float* scores, int* frames, mi_stream_t stream);
+/* ---- ... on the slots of a session pool (csrc/ctc_beam_pool.hip, whose header states the semantics): the beam stream above per slot, each slot with rows, an end and
+ * a start of its own.  State: mi_ctc_beam_stream_state_bytes(S, max_frames, W), started once by mi_ctc_beam_stream_reset.
+ * mi_ctc_beam_stream_reset_slot: one slot back to a stream start, enqueued on `stream`, no synchronisation: its header, start beam and arena root are written and its
+ * node table — and nothing else — is zeroed: a memset of 8 table_words(max_frames, W) bytes per call (256 KiB at max_frames = 1500, W = 10; 2 MiB at W = 64).  No
+ * other slot is written.  MI_ERR_ARG: slot outside [0, S), and what mi_ctc_beam_stream_reset refuses.
+ * mi_ctc_beam_stream_walk_slots: A records of five ints [slot, row0, n, final, out], given twice as the pool's tables are: records_host is checked, records_dev (the
+ * same ints on the DEVICE) is read by the kernel.  logits (rows, V1) compact with row stride ld_row; lse / lp_blank / cut_lp / cut_id: mi_ctc_beam_cut's tables over
+ * those rows (B = 1, T = rows, ld_batch = 0); rows = 0: all five may be null.  A record walks rows [row0, row0 + n) as the next frames of its slot (never past
+ * max_frames; n = 0 leaves the beam as read), then appends the committed prefix — with final = 1 the rest of the best hypothesis — to row `slot` of committed /
+ * committed_frames (S, max_frames) and writes n_committed / n_new (S) at `slot`.  out >= 0: the nbest best are backtraced into row `out` of tokens (R, nbest,
+ * max_frames) int32 (tokens_dtype 0) / int64 (1), n_tokens / scores (R, nbest), frames (R, nbest, max_frames; nullable); out = -1: no backtrace.  Nothing of a slot
+ * that no record names is read or written.  No float atomics; a slot's result does not depend on the other records, their order or its slot index.
+ * MI_ERR_ARG before any launch: a slot outside [0, S) or named twice; row0 / n negative or row0 + n > rows; final outside {0, 1}; out outside [-1, R) or used twice;
+ * final = 1 with out = -1; A outside 1..S; R outside 0..A; R > 0 without tokens / n_tokens / scores; and whatever mi_ctc_beam_stream_walk refuses.
+ * MI_ERR_UNSUPPORTED as mi_ctc_beam_stream_walk. */
+int mi_ctc_beam_stream_reset_slot(void* state, size_t state_bytes, int S, int max_frames, int W, int slot, mi_stream_t stream);
+int mi_ctc_beam_stream_walk_slots(const void* logits, long ld_row, int dtype, int rows, int V1, int blank, long pad_id, int W, int K, int nbest, const float* lse,
+                                  const float* lp_blank, const float* cut_lp, const int* cut_id, void* state, size_t state_bytes, int S, int max_frames,
+                                  const int* records_host, int A, const int* records_dev, int* committed, int* committed_frames, int* n_committed, int* n_new,
+                                  void* tokens, int tokens_dtype, int* n_tokens, float* scores, int* frames, int R, mi_stream_t stream);
 /* ---- CTC forced alignment (csrc/ctc_align.hip, whose header states the exact semantics): the best (Viterbi) path of a given transcript, one launch, one block per
  * utterance.  Arguments as mi_ctc_loss_fwd: logits (B, T, V1) fp32 (dtype 0) / bf16 (1) with element strides (ld_b, ld_t), lse (B*T) the rows' log-sum-exp, labels
  * (B, U) int64 (negative entries are padding wherever they stand), in_len (B) int32 clamped to [0, T].  Out: path (B, T) int32 = the class of every frame t < n_b on
