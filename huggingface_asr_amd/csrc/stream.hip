@@ -29,7 +29,9 @@
 //  * A step returns logits (B, n_out, V+1) for the newly final frames and the CTC greedy tokens newly emitted (the collapse carries the last class across steps).
 //    Row counts come from the caller's plan (host): `rows` holds (lo, hi) of every layer's input and of the emitted rows; no host round trip inside a step.
 //  * No atomics; a stream's result does not depend on the rest of the batch (every kernel here works per stream, the GEMMs per row).
-#include "stream_common.hpp"
+// The launch sequence of a step is stream_step.hpp's body, the one the session pool runs too: this file holds the lock-step kernels, their entries and the policy
+// (LockStep) through which that body works at the batch-wide position of the step's plan.  The plan is checked by plan_ok (stream_common.hpp), as a pool's records are.
+#include "stream_step.hpp"
 
 namespace {
 
@@ -105,6 +107,38 @@ __global__ __launch_bounds__(64) void ctc_collapse_stream_kernel(const int* __re
     n = n < 0 ? 0 : (n > T ? T : n);
     ctc_collapse_row(best + (long)b * T, n, T, blank, prev + b, ids + (long)b * T, n_ids + b, threadIdx.x);
 }
+
+// Where B streams in lock-step stand (stream_step.hpp's policy): every stream at the same rows, those of the step's plan; ends (B) on the device in the last step
+struct LockStep {
+    int B, L; const int* plan; const int* ends; hipStream_t st;
+    int lo(int l) const { return plan[2 * l]; }
+    int hi(int l) const { return plan[2 * l + 1]; }
+    int n(int l) const { return hi(l) - lo(l); }
+    int streams() const { return B; }
+    int rows(int l) const { return B * n(l); }
+    int history_in_front(const void* hist, void* cat, int n_new, int W) const { return copy_rows(hist, 2L * W, 0, 0, cat, (long)(n_new + 2) * W, 0, 0, 2, W, B, st); }
+    int new_rows_behind(int, const void* src, void* cat, int n_new, int W) const { return copy_rows(src, (long)n_new * W, 0, 0, cat, (long)(n_new + 2) * W, 2, 0, n_new, W, B, st); }
+    int history_back(int, const void* cat, int n_new, void* hist, int W) const { return copy_rows(cat, (long)(n_new + 2) * W, n_new, 0, hist, 2L * W, 0, 0, 2, W, B, st); }
+    int first_frames(const float* fp, float* x, int C, int d) const { return copy_rows(fp, (long)C * d, 0, 0, x, (long)n(0) * d, 0, 0, n(0), d, B, st); }
+    int pending_in(int l, const float* x, float* pend, int Rp, int d) const { return copy_rows(x, (long)n(l) * d, 0, 0, pend, (long)Rp * d, lo(l), Rp, n(l), d, B, st); }
+    int pending_out(int l, const float* pend, float* res, int Rp, int d) const { return copy_rows(pend, (long)Rp * d, lo(l + 1), Rp, res, (long)n(l + 1) * d, 0, 0, n(l + 1), d, B, st); }
+    int kv_append(int l, const bf16_t* kv, bf16_t* cache, int Lmax, int d) const { return copy_rows_ld(kv, (long)n(l) * 3 * d / 2, 3 * d / 2, 0, 0, cache, (long)Lmax * d, d, lo(l), 0, n(l), d, B, st); }
+    int rotary(int l, const bf16_t* x, bf16_t* out, int d, const float* cs, const float* sn, int H, int hd) const { return mi_rotary_bf16(x, d, out, d, cs + (size_t)lo(l) * hd, sn + (size_t)lo(l) * hd, rows(l), n(l), H, hd, st); }
+    int attention(int l, const AttnArgs& a, int hd) const {
+        // without a relative term at head sizes 64 / 128 the full forward's own kernel takes a cache (Tk != T, the causal diagonal at the end): the same key tiles, the
+        // same MFMA sums per (query, key) — the streamed contexts are the full forward's bit for bit as long as no query of a wave moves the softmax reference late
+        if (!a.pos && hd != 16)
+            return mi_attention_qkv_bf16(a.q, a.ldq, a.k, a.ldkv, a.v, a.ldkv, nullptr, 0, nullptr, nullptr, nullptr, a.out, a.ldo, B, n(l), hi(l), a.kv_bs, a.H, hd, a.scale, 1, st);
+        return mi_attention_chunk_bf16(a.q, a.ldq, a.k, a.ldkv, a.v, a.ldkv, a.kv_bs, a.pos, a.ldp, a.u, a.vb, a.out, a.ldo, B, n(l), hi(l), a.H, hd, a.scale, a.ref, st);
+    }
+    int dwconv(const DwsArgs& a, const int* end, int p, int n_new, int o0, int n_out) const {
+        return mi_dwconv_stream_bf16(a.in, a.ld_in, a.mul, a.mul ? a.ld_mul : 0, a.stats, a.gamma, a.beta, a.w, a.bias, a.ring, a.ring_stats, end, a.out, a.ld_out, B, a.C, a.K,
+                                     a.dil, a.left, a.Hr, p, n_new, o0, n_out, a.mode, a.act, st);
+    }
+    int csgu_conv(int l, const DwsArgs& a) const { return dwconv(a, nullptr, lo(l), n(l), lo(l), n(l)); }
+    int merge_conv(int l, const DwsArgs& a) const { return dwconv(a, ends, lo(l), n(l), lo(l + 1), n(l + 1)); }
+    int collapse(const int* best, int blank, int* prev, int* ids, int* n_ids) const { return mi_ctc_collapse_stream(best, B, n(L), ends, lo(L), blank, prev, ids, n_ids, st); }
+};
 
 }  // namespace
 
@@ -199,10 +233,10 @@ extern "C" int mi_ebf_stream_reset(const mi_ebf_config* cfg, const void* const* 
     return MI_OK;
 }
 
-// One step of every layer.  feats (B, 4*C, F) fp32 (zero beyond a stream's valid frames in the last step); rows: HOST array of 2 * (L + 1) ints, (lo, hi) of the input
-// rows of layer 0 .. L-1 and of the rows the last layer emits (huggingface_asr_amd/streaming.py `plan`); ends (B) int32 on the device, the last step only: n_b, else null;
-// pos_table: rotary: fp32 [cos (max_frames, hd) | sin (max_frames, hd)], else unused.  Outputs for the n_out = rows[2L+1] - rows[2L] emitted frames: logits
-// (B, n_out, logits_ld) fp32, best (B, n_out) int32 per-frame classes, ids (B, n_out) int32 newly emitted tokens then -1, n_ids (B).  n_out = 0: nothing is written.
+// One step of every layer (stream_step.hpp).  feats (B, 4*C, F) fp32 (zero beyond a stream's valid frames in the last step); rows: HOST array of 2 * (L + 1) ints, (lo, hi)
+// of the input rows of layer 0 .. L-1 and of the rows the last layer emits (huggingface_asr_amd/streaming.py `plan`), checked; ends (B) int32 on the device, the last step
+// only: n_b, else null; pos_table: rotary: fp32 [cos (max_frames, hd) | sin (max_frames, hd)], else unused.  Outputs for the n_out = rows[2L+1] - rows[2L] emitted frames:
+// logits (B, n_out, logits_ld) fp32, best (B, n_out) int32 per-frame classes, ids (B, n_out) int32 newly emitted tokens then -1, n_ids (B).  n_out = 0: nothing is written.
 extern "C" int mi_ebf_stream_step(const mi_ebf_config* cfg, const void* const* weights, int chunk_frames, int max_frames, const void* pos_table, void* state,
                                   size_t state_bytes, const float* feats, const int* rows, const int* ends, float* logits, int* best, int* ids, int* n_ids, hipStream_t st) {
     MI_ENTER();
@@ -211,118 +245,8 @@ extern "C" int mi_ebf_stream_step(const mi_ebf_config* cfg, const void* const* w
     const mi_ebf_config& c = *cfg;
     if (!supported(c, g)) return MI_ERR_UNSUPPORTED;
     if (!c.logits_f32 || (c.pos_type == 2 && !pos_table) || c.pos_type < 0 || c.pos_type > 2) return MI_ERR_ARG;
-    LayerState ls[64];
-    const St s = carve_state(c, g, state, ls);
-    if (s.bytes > state_bytes) return MI_ERR_ARG;
-    const int B = g.B, C = g.C, d = g.d, I = g.I, L = g.L, r = g.r;
-    // the plan, checked: frontiers never decrease, a layer takes and emits at most N rows, nothing runs past the caches, the merge window stays inside its history
-    for (int l = 0; l <= L; ++l) {
-        const int lo = rows[2 * l], hi = rows[2 * l + 1];
-        if (lo < 0 || hi < lo || hi - lo > g.N || hi > g.Lmax) return MI_ERR_ARG;
-        if (l == 0 && hi - lo > C) return MI_ERR_ARG;
-        if (l > 0 && (hi > rows[2 * l - 1] || lo > rows[2 * l - 2] || rows[2 * l - 2] - lo > r || (!ends && hi != (rows[2 * l - 1] > r ? rows[2 * l - 1] - r : 0)))) return MI_ERR_ARG;
-        if (l > 0 && ends && hi != rows[2 * l - 1]) return MI_ERR_ARG;
-    }
-    const int n_out = rows[2 * L + 1] - rows[2 * L];
-    if (n_out > 0 && (!logits || !best || !ids || !n_ids)) return MI_ERR_ARG;
-    const Slots W{weights};
-    const float scale = 1.0f / sqrtf((float)g.hd);
-
-    // ---- front end on [2 history rows | the new rows] of each conv's input, no time padding: the history IS the left padding (zero at stream start)
-    const long wF = g.F, wA = (long)g.F1 * g.C1 / 2;                   // row widths in 4-byte words
-    if ((g.F1 * g.C1) % 2) return MI_ERR_UNSUPPORTED;
-    RUN(copy_rows(s.x_hist, 2 * wF, 0, 0, s.featcat, (4 * C + 2) * wF, 0, 0, 2, (int)wF, B, st));
-    RUN(copy_rows(feats, 4 * C * wF, 0, 0, s.featcat, (4 * C + 2) * wF, 2, 0, 4 * C, (int)wF, B, st));
-    RUN(copy_rows(s.featcat, (4 * C + 2) * wF, 4 * C, 0, s.x_hist, 2 * wF, 0, 0, 2, (int)wF, B, st));
-    RUN(mi_conv2d_first_gelu(s.featcat, W.Gf(G_CONV1_W), W.Gf(G_CONV1_B), s.act1n, B, 4 * C + 2, g.F, g.C1, 3, 2, 0, 2, 2 * C, g.F1, st));
-    RUN(copy_rows(s.c1_hist, 2 * wA, 0, 0, s.act1c, (2 * C + 2) * wA, 0, 0, 2, (int)wA, B, st));
-    RUN(copy_rows(s.act1n, 2 * C * wA, 0, 0, s.act1c, (2 * C + 2) * wA, 2, 0, 2 * C, (int)wA, B, st));
-    RUN(copy_rows(s.act1c, (2 * C + 2) * wA, 2 * C, 0, s.c1_hist, 2 * wA, 0, 0, 2, (int)wA, B, st));
-    RUN(mi_conv2d_cl_bf16(s.act1c, W.Gw(G_CONV2_W), W.Gf(G_CONV2_B), s.act2, B, 2 * C + 2, g.F1, g.C1, g.C2, 3, 3, 2, 0, 2, C, g.F2, 1, st));
-    const int Mc = B * C;
-    RUN(mi_gemm_bf16(s.act2, (long)g.F2 * g.C2, W.Gw(G_FEOUT_W), (long)g.F2 * g.C2, W.Gf(G_FEOUT_B), 1, s.feo, d, 1, nullptr, 0, 1.f, 0, Mc, d, g.F2 * g.C2, 0, 0, st));
-    RUN(mi_layernorm_chain(s.feo, d, nullptr, C, nullptr, nullptr, 0.f, nullptr, 0, W.Gf(G_FP_LN_G), W.Gf(G_FP_LN_B), c.ln_eps, s.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, Mc, d, st));
-    RUN(mi_gemm_bf16(s.a0, d, W.Gw(G_FP_W), d, W.Gf(G_FP_B), 1, s.fp, d, 1, nullptr, 0, 1.f, 0, Mc, d, d, 0, 0, st));
-    const int n0 = rows[1] - rows[0];
-    RUN(copy_rows(s.fp, (long)C * d, 0, 0, s.x, (long)n0 * d, 0, 0, n0, d, B, st));           // the first n0 of the C new frames are frames of the utterance(s)
-
-    // ---- the layers: x holds layer l's new input rows, compact (B, n_in, d)
-    for (int l = 0; l < L; ++l) {
-        const int p = rows[2 * l], a = rows[2 * l + 1], o0 = rows[2 * l + 2], o1 = rows[2 * l + 3];
-        const int n_in = a - p, n_o = o1 - o0, M = B * n_in, Mo = B * n_o;
-        const LayerState& t = ls[l];
-        const int Rp = r + g.N;                                            // the pending-residual ring: rows [o0, a) always fit
-        if (n_in > 0) {
-            // first LayerNorm(s) of the layer on its input rows (the previous layer's final_layer_norm output, or the feature projection)
-            if (c.use_macaron) {       // x += 0.5 * FFN(LN(x))   e_branchformer.py:271-273
-                RUN(mi_layernorm_chain(s.x, d, nullptr, n_in, nullptr, nullptr, 0.f, nullptr, 0, W.Lf(l, FF1_LN_G), W.Lf(l, FF1_LN_B), LEPS, s.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, M, d, st));
-                RUN(mi_gemm_bf16(s.a0, d, W.Lw(l, FF1_W1), d, W.Lf(l, FF1_B1), 1, s.h, I, 0, nullptr, 0, 1.f, 1, M, I, d, 0, 0, st));
-                RUN(mi_gemm_bf16(s.h, I, W.Lw(l, FF1_W2), I, W.Lf(l, FF1_B2), 1, s.x, d, 1, s.x, d, 0.5f, 0, M, d, I, 0, 0, st));
-            }
-            RUN(mi_layernorm_chain(s.x, d, nullptr, n_in, nullptr, nullptr, 0.f, nullptr, 0, W.Lf(l, ATT_LN_G), W.Lf(l, ATT_LN_B), LEPS, s.a1, d, nullptr, 0,
-                                   W.Lf(l, MLP_LN_G), W.Lf(l, MLP_LN_B), s.a2, d, M, d, st));
-            // the residual of the merge: rows [p, a) into the pending ring
-            RUN(copy_rows(s.x, (long)n_in * d, 0, 0, t.pend, (long)Rp * d, p, Rp, n_in, d, B, st));
-            // global branch: Q | K | V of the new rows, K | V appended to the cache, chunk attention over the cache
-            const bf16_t* qk_in = s.a1;
-            if (c.pos_type == 2) {
-                const float* cs = (const float*)pos_table;
-                RUN(mi_rotary_bf16(s.a1, d, s.a1r, d, cs + (size_t)p * g.hd, cs + ((size_t)g.Lmax + p) * g.hd, M, n_in, g.H, g.hd, st));
-                qk_in = s.a1r;
-                RUN(mi_gemm_bf16(qk_in, d, W.Lw(l, ATT_WQK), d, W.Lf(l, ATT_BQK), 1, s.qk, 3 * d, 0, nullptr, 0, 1.f, 0, M, 2 * d, d, 0, 0, st));
-                RUN(mi_gemm_bf16(s.a1, d, W.Lw(l, ATT_WV), d, W.Lf(l, ATT_BV), 1, s.qk + 2 * d, 3 * d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
-            } else {
-                RUN(mi_gemm_bf16(s.a1, d, W.Lw(l, ATT_WQK), d, W.Lf(l, ATT_BQK), 1, s.qk, 3 * d, 0, nullptr, 0, 1.f, 0, M, 3 * d, d, 0, 0, st));
-            }
-            // cache rows [p, a) = the [K | V] columns of the new rows (d words out of rows 3d/2 words apart)
-            RUN(copy_rows_ld(s.qk + d, (long)n_in * 3 * d / 2, 3 * d / 2, 0, 0, t.kv, (long)g.Lmax * d, d, p, 0, n_in, d, B, st));
-            const bf16_t* posp = c.pos_type == 1 ? s.posp + (size_t)l * g.Lmax * d : nullptr;
-            if (!posp && (g.hd == 64 || g.hd == 128)) {
-                // without a relative term the full forward's own kernel takes a cache (Tk != T, the causal diagonal at the end): the same key tiles, the same MFMA
-                // sums per (query, key) — the streamed contexts are the full forward's bit for bit as long as no query of a wave moves the softmax reference late
-                RUN(mi_attention_qkv_bf16(s.qk, 3 * d, t.kv, 2 * d, t.kv + d, 2 * d, nullptr, 0, nullptr, nullptr, nullptr, s.ctx, d, B, n_in, a, (long)g.Lmax * 2 * d, g.H, g.hd,
-                                          scale, 1, st));
-            } else {                  // relative positions (mi_attention_qkv_bf16 refuses them with Tk != T) and head size 16
-                RUN(mi_attention_chunk_bf16(s.qk, 3 * d, t.kv, 2 * d, t.kv + d, 2 * d, (long)g.Lmax * 2 * d, posp, d, posp ? W.Lf(l, ATT_U) : nullptr, posp ? W.Lf(l, ATT_V) : nullptr,
-                                            s.ctx, d, B, n_in, a, g.H, g.hd, scale, g.hd == 16 ? 1 : (g.hd == 64 ? 2 : 3), st));       // the full forward's kernel for this shape
-            }
-            RUN(mi_gemm_bf16(s.ctx, d, W.Lw(l, ATT_WO), d, W.Lf(l, ATT_BO), 1, s.cat, 2 * d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
-            // local branch: cgMLP with the stateful CSGU conv
-            RUN(mi_gemm_bf16(s.a2, d, W.Lw(l, MLP_W1), d, W.Lf(l, MLP_B1), 1, s.h, I, 0, nullptr, 0, 1.f, 1, M, I, d, 0, 0, st));
-            RUN(mi_row_stats_bf16(s.h + I / 2, I, I / 2, LEPS, s.stats, M, st));
-            if (!c.csgu_linear) {
-                RUN(mi_dwconv_stream_bf16(s.h + I / 2, I, s.h, I, s.stats, W.Lf(l, CSGU_LN_G), W.Lf(l, CSGU_LN_B), W.Lf(l, CSGU_W), W.Lf(l, CSGU_B), t.csgu, t.csgu_stats, nullptr,
-                                          s.s, I / 2, B, I / 2, g.Kc, g.dil, g.Hc, g.Hc, p, n_in, p, n_in, 0, c.csgu_act, st));
-            } else {
-                RUN(mi_dwconv_stream_bf16(s.h + I / 2, I, nullptr, 0, s.stats, W.Lf(l, CSGU_LN_G), W.Lf(l, CSGU_LN_B), W.Lf(l, CSGU_W), W.Lf(l, CSGU_B), t.csgu, t.csgu_stats, nullptr,
-                                          s.cv, I / 2, B, I / 2, g.Kc, g.dil, g.Hc, g.Hc, p, n_in, p, n_in, 2, 0, st));
-                RUN(mi_gemm_bf16(s.cv, I / 2, W.Lw(l, CSGU_LIN_W), I / 2, W.Lf(l, CSGU_LIN_B), 1, s.lin, I / 2, 0, nullptr, 0, 1.f, 0, M, I / 2, I / 2, 0, 0, st));
-                RUN(mi_gate_act_mul_bf16(s.h, I, s.lin, I / 2, s.s, I / 2, M, I / 2, c.csgu_act, st));
-            }
-            RUN(mi_gemm_bf16(s.s, I / 2, W.Lw(l, MLP_W2), I / 2, W.Lf(l, MLP_B2), 1, s.cat + d, 2 * d, 0, nullptr, 0, 1.f, 0, M, d, I / 2, 0, 0, st));
-        }
-        if (n_in == 0 && n_o == 0) continue;
-        // merge: push the new cat rows, m2 = cat + dwconv(cat) for the rows whose lookahead is complete (all pending ones in the last step)
-        RUN(mi_dwconv_stream_bf16(s.cat, 2 * d, nullptr, 0, nullptr, nullptr, nullptr, W.Lf(l, MRG_DW_W), W.Lf(l, MRG_DW_B), t.cat, nullptr, ends, s.m2, 2 * d,
-                                  B, 2 * d, g.Km, 1, r, 2 * r, p, n_in, o0, n_o, 1, 0, st));
-        if (n_o == 0) continue;
-        RUN(copy_rows(t.pend, (long)Rp * d, o0, Rp, s.res, (long)n_o * d, 0, 0, n_o, d, B, st));
-        RUN(mi_gemm_bf16(s.m2, 2 * d, W.Lw(l, MRG_W), 2 * d, W.Lf(l, MRG_B), 1, s.xo, d, 1, s.res, d, 1.0f, 0, Mo, d, 2 * d, 0, 0, st));
-        if (c.use_macaron) {   // e_branchformer.py:307-309
-            RUN(mi_layernorm_chain(s.xo, d, nullptr, n_o, nullptr, nullptr, 0.f, nullptr, 0, W.Lf(l, FF2_LN_G), W.Lf(l, FF2_LN_B), LEPS, s.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, Mo, d, st));
-            RUN(mi_gemm_bf16(s.a0, d, W.Lw(l, FF2_W1), d, W.Lf(l, FF2_B1), 1, s.h, I, 0, nullptr, 0, 1.f, 1, Mo, I, d, 0, 0, st));
-            RUN(mi_gemm_bf16(s.h, I, W.Lw(l, FF2_W2), I, W.Lf(l, FF2_B2), 1, s.xo, d, 1, s.xo, d, 0.5f, 0, Mo, d, I, 0, 0, st));
-        }
-        if (l + 1 < L)         // final_layer_norm (:312): the next layer's input rows
-            RUN(mi_layernorm_chain(s.xo, d, nullptr, n_o, W.Lf(l, FIN_LN_G), W.Lf(l, FIN_LN_B), LEPS, s.x, d, nullptr, nullptr, 0.f, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, Mo, d, st));
-        else                   // chained with encoder.layer_norm -> the head's input
-            RUN(mi_layernorm_chain(s.xo, d, nullptr, n_o, W.Lf(l, FIN_LN_G), W.Lf(l, FIN_LN_B), LEPS, nullptr, 0, W.Gf(G_ENC_LN_G), W.Gf(G_ENC_LN_B), c.ln_eps, s.hid, d, nullptr, 0,
-                                   nullptr, nullptr, nullptr, 0, Mo, d, st));
-    }
-    if (n_out == 0) return MI_OK;
-    // ---- CTC head, per-frame classes, collapse with the carried class
-    const int Mo = B * n_out;
-    RUN(mi_gemm_bf16(s.hid, d, W.Gw(G_HEAD_W), d, W.Gf(G_HEAD_B), 1, logits, g.ldl, 1, nullptr, 0, 1.f, 0, Mo, g.V1, d, 0, 0, st));
-    RUN(mi_row_argmax(logits, g.ldl, 0, g.V1, best, Mo, st));
-    return mi_ctc_collapse_stream(best, B, n_out, ends, rows[2 * L], c.V, s.prev, ids, n_ids, st);
+    const LockStep at{g.B, g.L, rows, ends, st};
+    const Step<LockStep> step(c, g, state, weights, at, pos_table, st);
+    if (step.s.bytes > state_bytes || !plan_ok(g, rows, 2, ends != nullptr)) return MI_ERR_ARG;
+    return step.run(feats, logits, best, ids, n_ids);
 }

@@ -1,7 +1,7 @@
 // What the lock-step stream step (stream.hip) and the session pool (stream_pool.hip) share, written once: the bodies of the three kernels that hold per-stream
-// position — chunk attention, the stateful depthwise conv, the CTC collapse with a carried class — and the layout of the state.  A lock-step kernel hands a body the
-// batch-wide scalars of its call, a pool kernel the entry of its slot's descriptor: the arithmetic of a row is the same instructions either way, which is what the
-// pool's bit-equality with a stream of one rests on.  Internal: nothing here is exported.
+// position — chunk attention, the stateful depthwise conv, the CTC collapse with a carried class —, the layout of the state and the check of a step's plan (the launch
+// sequence of a step is stream_step.hpp's).  A lock-step kernel hands a body the batch-wide scalars of its call, a pool kernel the entry of its slot's descriptor: the
+// arithmetic of a row is the same instructions either way, which is what the pool's bit-equality with a stream of one rests on.  Internal: nothing here is exported.
 #pragma once
 #include "ebf_layout.hpp"
 
@@ -297,6 +297,18 @@ inline St carve_state(const mi_ebf_config& c, const Geo& g, void* base, LayerSta
 
 inline bool supported(const mi_ebf_config& c, const Geo& g) {
     return !c.extra_layers && !c.layer_mixing && !c.context_mode && (g.hd == 16 || g.hd == 64 || g.hd == 128) && g.Lmax <= 8192 && g.L <= 64;
+}
+
+// Are (lo, hi) of entries 0 .. L (entry l at lo_hi[l * stride], the lock-step step's plan or a record of a pool step) a step streaming.plan could have produced, in a
+// finish or not?  Frontiers never decrease, an entry holds at most N rows (entry 0: C), none past the caches, the merge window stays inside its history, a layer emits up to a_l - r (finish: a_l).
+inline bool plan_ok(const Geo& g, const int* lo_hi, int stride, bool finish) {
+    for (int l = 0; l <= g.L; ++l) {
+        const int lo = lo_hi[l * stride], hi = lo_hi[l * stride + 1];
+        const int plo = l ? lo_hi[(l - 1) * stride] : lo, phi = l ? lo_hi[(l - 1) * stride + 1] : hi;      // the entry before
+        if (lo < 0 || hi < lo || hi - lo > (l ? g.N : g.C) || hi > g.Lmax) return false;
+        if (l && (hi > phi || lo > plo || plo - lo > g.r || hi != (finish ? phi : (phi > g.r ? phi - g.r : 0)))) return false;
+    }
+    return true;
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
 // Streaming session pool for the causal E-Branchformer + CTC models: S slots over the state of stream.hip (whose header states what a stream step computes), each with
 // a position of its own.  The kernels here are the per-slot forms of stream.hip's: they take a device table of per-slot descriptors where those take batch-wide scalars,
-// and run the same bodies (stream_common.hpp).
+// and run the same bodies (stream_common.hpp).  The launch sequence of a step is stream_step.hpp's, the one the lock-step stream runs: mi_ebf_stream_step_slots hands
+// it the PerSlot policy below, through which that body copies rows, rotates, attends, convolves and collapses at every slot's own position.
 //
 // Semantics (normative)
 //  * The state is mi_ebf_stream_state_bytes' for cfg.B = S slots: every persistent piece is (S, ...), the scratch holds S * (C + L*r) rows.
@@ -23,7 +24,7 @@
 //  * No atomics; a session's result does not depend on the other slots, on its slot index or on idle steps (every kernel here works per slot, the GEMMs per row).
 #include <vector>
 
-#include "stream_common.hpp"
+#include "stream_step.hpp"
 
 namespace {
 
@@ -228,32 +229,20 @@ struct Rec {
     int n(int l) const { return hi(l) - lo(l); }
 };
 
-// streaming.plan's invariants per slot (what mi_ebf_stream_step checks of its one plan), distinct slots, prefix-sum offsets
+// streaming.plan's invariants per slot (plan_ok, which mi_ebf_stream_step asks of its one plan), distinct slots, a finish at the slot's own end, prefix-sum offsets
 int check_records(const Geo& g, const int* rec, int A) {
     if (!rec || A < 1 || A > g.B) return MI_ERR_ARG;
-    const int L = g.L, r = g.r;
-    unsigned long long seen[4] = {0, 0, 0, 0};
+    const int L = g.L;
+    std::vector<char> seen(g.B, 0);
     std::vector<long> sum(L + 1, 0);
     for (int i = 0; i < A; ++i) {
         const Rec e{rec + (long)i * RW(L)};
-        if (e.slot() < 0 || e.slot() >= g.B) return MI_ERR_ARG;
-        if (e.slot() < 256) {
-            if ((seen[e.slot() >> 6] >> (e.slot() & 63)) & 1ull) return MI_ERR_ARG;
-            seen[e.slot() >> 6] |= 1ull << (e.slot() & 63);
-        } else {
-            for (int j = 0; j < i; ++j)
-                if (rec[(long)j * RW(L)] == e.slot()) return MI_ERR_ARG;
-        }
+        if (e.slot() < 0 || e.slot() >= g.B || seen[e.slot()]++) return MI_ERR_ARG;
         const bool fin = e.end() >= 0;
-        if (e.end() < -1 || (fin && e.end() != e.hi(0))) return MI_ERR_ARG;
+        if (e.end() < -1 || (fin && e.end() != e.hi(0)) || !plan_ok(g, e.w + 2, 3, fin)) return MI_ERR_ARG;
         for (int l = 0; l <= L; ++l) {
-            const int lo = e.lo(l), hi = e.hi(l);
-            if (lo < 0 || hi < lo || hi - lo > g.N || hi > g.Lmax) return MI_ERR_ARG;
-            if (l == 0 && hi - lo > g.C) return MI_ERR_ARG;
-            if (l > 0 && (hi > e.hi(l - 1) || lo > e.lo(l - 1) || e.lo(l - 1) - lo > r)) return MI_ERR_ARG;
-            if (l > 0 && hi != (fin ? e.hi(l - 1) : (e.hi(l - 1) > r ? e.hi(l - 1) - r : 0))) return MI_ERR_ARG;
             if (e.off(l) != sum[l]) return MI_ERR_ARG;
-            sum[l] += hi - lo;
+            sum[l] += e.n(l);
         }
     }
     return MI_OK;
@@ -299,6 +288,42 @@ void expand(const Geo& g, const int* rec, int A, int* t) {
 }
 
 bool slot_ok(int s, int slots) { return s >= 0 && s < slots; }
+
+// Where the A active slots of a pool step stand (stream_step.hpp's policy): each at rows of its own — the sections of the step's table on the device —, with the host
+// sums and maxima of the records, which size the launches
+struct PerSlot {
+    int A, L; const int* table; hipStream_t st;
+    std::vector<int> tot, mostn, mostk;      // per entry: the rows of all records, the most of one; per layer: the most keys of a record that has queries
+    PerSlot(const int* records, int A_, int L_, const int* table_, hipStream_t st_) : A(A_), L(L_), table(table_), st(st_), tot(L_ + 1, 0), mostn(L_ + 1, 0), mostk(L_, 0) {
+        for (int i = 0; i < A; ++i)
+            for (int l = 0; l <= L; ++l) {
+                const Rec e{records + (long)i * RW(L)};
+                tot[l] += e.n(l);
+                mostn[l] = e.n(l) > mostn[l] ? e.n(l) : mostn[l];
+                if (l < L && e.n(l) > 0 && e.hi(l) > mostk[l]) mostk[l] = e.hi(l);
+            }
+    }
+    const int* front(int sec) const { return table + front_at(A, sec); }
+    const int* layer(int l, int sec) const { return table + layer_at(A, L, l) + (long)A * sec; }      // sec: L_PEND_IN ..
+    int streams() const { return A; }
+    int rows(int l) const { return tot[l]; }
+    int history_in_front(const void* hist, void* cat, int n_new, int W) const { return copy_rows_slots(hist, 2L * W, W, cat, (long)(n_new + 2) * W, W, front(0), A, 2, W, st); }
+    int new_rows_behind(int conv, const void* src, void* cat, int n_new, int W) const { return copy_rows_slots(src, (long)n_new * W, W, cat, (long)(n_new + 2) * W, W, front(conv ? 3 : 1), A, n_new, W, st); }
+    int history_back(int conv, const void* cat, int n_new, void* hist, int W) const { return copy_rows_slots(cat, (long)(n_new + 2) * W, W, hist, 2L * W, W, front(conv ? 4 : 2), A, 2, W, st); }
+    int first_frames(const float* fp, float* x, int C, int d) const { return copy_rows_slots(fp, (long)C * d, d, x, 0, d, front(5), A, mostn[0], d, st); }
+    int pending_in(int l, const float* x, float* pend, int Rp, int d) const { return copy_rows_slots(x, 0, d, pend, (long)Rp * d, d, layer(l, L_PEND_IN), A, mostn[l], d, st); }
+    int pending_out(int l, const float* pend, float* res, int Rp, int d) const { return copy_rows_slots(pend, (long)Rp * d, d, res, 0, d, layer(l, L_PEND_OUT), A, mostn[l + 1], d, st); }
+    int kv_append(int l, const bf16_t* kv, bf16_t* cache, int Lmax, int d) const { return copy_rows_slots(kv, 0, 3 * d / 2, cache, (long)Lmax * d, d, layer(l, L_KV), A, mostn[l], d, st); }
+    int rotary(int l, const bf16_t* x, bf16_t* out, int d, const float* cs, const float* sn, int H, int hd) const { return rotary_slots(x, d, out, d, cs, sn, layer(l, L_ROT), A, mostn[l], H, hd, st); }
+    int attention(int l, const AttnArgs& a, int hd) const { return attention_chunk_slots(a, layer(l, L_ATT), A, tot[l], mostk[l], hd, st); }
+    int csgu_conv(int l, const DwsArgs& a) const { return dwconv_stream_slots(a, layer(l, L_CSGU), A, st); }
+    int merge_conv(int l, const DwsArgs& a) const { return dwconv_stream_slots(a, layer(l, L_MERGE), A, st); }
+    int collapse(const int* best, int blank, int* prev, int* ids, int* n_ids) const {
+        hipLaunchKernelGGL(ctc_collapse_slots_kernel, dim3(A), dim3(64), 0, st, best, blank, prev, ids, n_ids, table + collapse_at(A, L));
+        MI_CHECK_LAUNCH();
+        return MI_OK;
+    }
+};
 
 }  // namespace
 
@@ -445,7 +470,7 @@ extern "C" int mi_ebf_stream_slots_table(const mi_ebf_config* cfg, int chunk_fra
     return (int)words;
 }
 
-// One step of the pool.  cfg.B = slots; feats (A, 4*C, F) fp32, record i's chunk (a tail zero-padded); records (HOST) and table (DEVICE: mi_ebf_stream_slots_table's
+// One step of the pool (stream_step.hpp).  cfg.B = slots; feats (A, 4*C, F) fp32, record i's chunk (a tail zero-padded); records (HOST) and table (DEVICE: mi_ebf_stream_slots_table's
 // words for these records, table_len >= their count) as the header says; pos_table as mi_ebf_stream_step's.  Outputs compact in record order (header).  sum n_out = 0:
 // nothing is written.
 extern "C" int mi_ebf_stream_step_slots(const mi_ebf_config* cfg, const void* const* weights, int chunk_frames, int max_frames, const void* pos_table, void* state,
@@ -459,109 +484,8 @@ extern "C" int mi_ebf_stream_step_slots(const mi_ebf_config* cfg, const void* co
     if (!c.logits_f32 || (c.pos_type == 2 && !pos_table) || c.pos_type < 0 || c.pos_type > 2) return MI_ERR_ARG;
     RUN(check_records(g, records, A));
     if (table_len < table_words(A, g.L)) return MI_ERR_ARG;
-    LayerState ls[64];
-    const St s = carve_state(c, g, state, ls);
-    if (s.bytes > state_bytes) return MI_ERR_ARG;
-    const int C = g.C, d = g.d, I = g.I, L = g.L, r = g.r, RWL = RW(L);
-    // host sums and maxima of the records: what sizes the launches
-    std::vector<int> tot(L + 1, 0), mostn(L + 1, 0), mostk(L, 0);
-    for (int i = 0; i < A; ++i) {
-        const Rec e{records + (long)i * RWL};
-        for (int l = 0; l <= L; ++l) {
-            tot[l] += e.n(l);
-            mostn[l] = e.n(l) > mostn[l] ? e.n(l) : mostn[l];
-            if (l < L && e.n(l) > 0 && e.hi(l) > mostk[l]) mostk[l] = e.hi(l);
-        }
-    }
-    const int n_out = tot[L];
-    if (n_out > 0 && (!logits || !best || !ids || !n_ids)) return MI_ERR_ARG;
-    const Slots W{weights};
-    const float scale = 1.0f / sqrtf((float)g.hd);
-
-    // ---- front end on [2 history rows | the new rows] of each conv's input for the A active slots, as mi_ebf_stream_step's for its B streams
-    const long wF = g.F, wA = (long)g.F1 * g.C1 / 2;                   // row widths in 4-byte words
-    if ((g.F1 * g.C1) % 2 || (d % 2)) return MI_ERR_UNSUPPORTED;
-    RUN(copy_rows_slots(s.x_hist, 2 * wF, wF, s.featcat, (4 * C + 2) * wF, wF, table + front_at(A, 0), A, 2, (int)wF, st));
-    RUN(copy_rows_slots(feats, 4 * C * wF, wF, s.featcat, (4 * C + 2) * wF, wF, table + front_at(A, 1), A, 4 * C, (int)wF, st));
-    RUN(copy_rows_slots(s.featcat, (4 * C + 2) * wF, wF, s.x_hist, 2 * wF, wF, table + front_at(A, 2), A, 2, (int)wF, st));
-    RUN(mi_conv2d_first_gelu(s.featcat, W.Gf(G_CONV1_W), W.Gf(G_CONV1_B), s.act1n, A, 4 * C + 2, g.F, g.C1, 3, 2, 0, 2, 2 * C, g.F1, st));
-    RUN(copy_rows_slots(s.c1_hist, 2 * wA, wA, s.act1c, (2 * C + 2) * wA, wA, table + front_at(A, 0), A, 2, (int)wA, st));
-    RUN(copy_rows_slots(s.act1n, 2 * C * wA, wA, s.act1c, (2 * C + 2) * wA, wA, table + front_at(A, 3), A, 2 * C, (int)wA, st));
-    RUN(copy_rows_slots(s.act1c, (2 * C + 2) * wA, wA, s.c1_hist, 2 * wA, wA, table + front_at(A, 4), A, 2, (int)wA, st));
-    RUN(mi_conv2d_cl_bf16(s.act1c, W.Gw(G_CONV2_W), W.Gf(G_CONV2_B), s.act2, A, 2 * C + 2, g.F1, g.C1, g.C2, 3, 3, 2, 0, 2, C, g.F2, 1, st));
-    const int Mc = A * C;
-    RUN(mi_gemm_bf16(s.act2, (long)g.F2 * g.C2, W.Gw(G_FEOUT_W), (long)g.F2 * g.C2, W.Gf(G_FEOUT_B), 1, s.feo, d, 1, nullptr, 0, 1.f, 0, Mc, d, g.F2 * g.C2, 0, 0, st));
-    RUN(mi_layernorm_chain(s.feo, d, nullptr, C, nullptr, nullptr, 0.f, nullptr, 0, W.Gf(G_FP_LN_G), W.Gf(G_FP_LN_B), c.ln_eps, s.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, Mc, d, st));
-    RUN(mi_gemm_bf16(s.a0, d, W.Gw(G_FP_W), d, W.Gf(G_FP_B), 1, s.fp, d, 1, nullptr, 0, 1.f, 0, Mc, d, d, 0, 0, st));
-    RUN(copy_rows_slots(s.fp, (long)C * d, d, s.x, 0, d, table + front_at(A, 5), A, mostn[0], d, st));
-
-    // ---- the layers: x holds layer l's new input rows of all active slots, compact (sum n_in, d)
-    for (int l = 0; l < L; ++l) {
-        const int M = tot[l], Mo = tot[l + 1];
-        if (M == 0 && Mo == 0) continue;
-        const LayerState& t = ls[l];
-        const int* tl = table + layer_at(A, L, l);
-        const int Rp = r + g.N;                                            // the pending-residual ring: rows [o0, a) always fit
-        if (M > 0) {
-            if (c.use_macaron) {       // x += 0.5 * FFN(LN(x))   e_branchformer.py:271-273
-                RUN(mi_layernorm_chain(s.x, d, nullptr, M, nullptr, nullptr, 0.f, nullptr, 0, W.Lf(l, FF1_LN_G), W.Lf(l, FF1_LN_B), LEPS, s.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, M, d, st));
-                RUN(mi_gemm_bf16(s.a0, d, W.Lw(l, FF1_W1), d, W.Lf(l, FF1_B1), 1, s.h, I, 0, nullptr, 0, 1.f, 1, M, I, d, 0, 0, st));
-                RUN(mi_gemm_bf16(s.h, I, W.Lw(l, FF1_W2), I, W.Lf(l, FF1_B2), 1, s.x, d, 1, s.x, d, 0.5f, 0, M, d, I, 0, 0, st));
-            }
-            RUN(mi_layernorm_chain(s.x, d, nullptr, M, nullptr, nullptr, 0.f, nullptr, 0, W.Lf(l, ATT_LN_G), W.Lf(l, ATT_LN_B), LEPS, s.a1, d, nullptr, 0,
-                                   W.Lf(l, MLP_LN_G), W.Lf(l, MLP_LN_B), s.a2, d, M, d, st));
-            // the residual of the merge: each slot's rows [p, a) into its pending ring
-            RUN(copy_rows_slots(s.x, 0, d, t.pend, (long)Rp * d, d, tl + (long)A * L_PEND_IN, A, mostn[l], d, st));
-            // global branch: Q | K | V of the new rows, K | V appended to each slot's cache at its own p, chunk attention over the caches
-            if (c.pos_type == 2) {
-                const float* cs = (const float*)pos_table;
-                RUN(rotary_slots(s.a1, d, s.a1r, d, cs, cs + (size_t)g.Lmax * g.hd, tl + (long)A * L_ROT, A, mostn[l], g.H, g.hd, st));
-                RUN(mi_gemm_bf16(s.a1r, d, W.Lw(l, ATT_WQK), d, W.Lf(l, ATT_BQK), 1, s.qk, 3 * d, 0, nullptr, 0, 1.f, 0, M, 2 * d, d, 0, 0, st));
-                RUN(mi_gemm_bf16(s.a1, d, W.Lw(l, ATT_WV), d, W.Lf(l, ATT_BV), 1, s.qk + 2 * d, 3 * d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
-            } else {
-                RUN(mi_gemm_bf16(s.a1, d, W.Lw(l, ATT_WQK), d, W.Lf(l, ATT_BQK), 1, s.qk, 3 * d, 0, nullptr, 0, 1.f, 0, M, 3 * d, d, 0, 0, st));
-            }
-            RUN(copy_rows_slots(s.qk + d, 0, 3 * d / 2, t.kv, (long)g.Lmax * d, d, tl + (long)A * L_KV, A, mostn[l], d, st));
-            const bf16_t* posp = c.pos_type == 1 ? s.posp + (size_t)l * g.Lmax * d : nullptr;
-            AttnArgs at{s.qk, 3L * d, t.kv, t.kv + d, 2L * d, (long)g.Lmax * 2 * d, posp, d, posp ? W.Lf(l, ATT_U) : nullptr, posp ? W.Lf(l, ATT_V) : nullptr, s.ctx, d,
-                        0, 0, g.H, 0, 0, g.hd == 16 ? 1 : ((g.hd == 64 && posp) ? 2 : 3), scale};      // the walk of the full forward's kernel for this shape
-            RUN(attention_chunk_slots(at, tl + (long)A * L_ATT, A, M, mostk[l], g.hd, st));
-            RUN(mi_gemm_bf16(s.ctx, d, W.Lw(l, ATT_WO), d, W.Lf(l, ATT_BO), 1, s.cat, 2 * d, 0, nullptr, 0, 1.f, 0, M, d, d, 0, 0, st));
-            // local branch: cgMLP with the stateful CSGU conv
-            RUN(mi_gemm_bf16(s.a2, d, W.Lw(l, MLP_W1), d, W.Lf(l, MLP_B1), 1, s.h, I, 0, nullptr, 0, 1.f, 1, M, I, d, 0, 0, st));
-            RUN(mi_row_stats_bf16(s.h + I / 2, I, I / 2, LEPS, s.stats, M, st));
-            DwsArgs cg{s.h + I / 2, I, c.csgu_linear ? nullptr : s.h, I, s.stats, W.Lf(l, CSGU_LN_G), W.Lf(l, CSGU_LN_B), W.Lf(l, CSGU_W), W.Lf(l, CSGU_B), t.csgu, t.csgu_stats, nullptr,
-                       c.csgu_linear ? s.cv : s.s, I / 2, g.B, I / 2, g.Kc, g.dil, g.Hc, g.Hc, 0, 0, 0, 0, c.csgu_linear ? 2 : 0, c.csgu_linear ? 0 : c.csgu_act};
-            RUN(dwconv_stream_slots(cg, tl + (long)A * L_CSGU, A, st));
-            if (c.csgu_linear) {
-                RUN(mi_gemm_bf16(s.cv, I / 2, W.Lw(l, CSGU_LIN_W), I / 2, W.Lf(l, CSGU_LIN_B), 1, s.lin, I / 2, 0, nullptr, 0, 1.f, 0, M, I / 2, I / 2, 0, 0, st));
-                RUN(mi_gate_act_mul_bf16(s.h, I, s.lin, I / 2, s.s, I / 2, M, I / 2, c.csgu_act, st));
-            }
-            RUN(mi_gemm_bf16(s.s, I / 2, W.Lw(l, MLP_W2), I / 2, W.Lf(l, MLP_B2), 1, s.cat + d, 2 * d, 0, nullptr, 0, 1.f, 0, M, d, I / 2, 0, 0, st));
-        }
-        // merge: push each slot's new cat rows, m2 = cat + dwconv(cat) for the rows whose lookahead is complete (all pending ones of a slot that finishes)
-        DwsArgs mg{s.cat, 2L * d, nullptr, 0, nullptr, nullptr, nullptr, W.Lf(l, MRG_DW_W), W.Lf(l, MRG_DW_B), t.cat, nullptr, nullptr, s.m2, 2L * d,
-                   g.B, 2 * d, g.Km, 1, r, 2 * r, 0, 0, 0, 0, 1, 0};
-        RUN(dwconv_stream_slots(mg, tl + (long)A * L_MERGE, A, st));
-        if (Mo == 0) continue;
-        RUN(copy_rows_slots(t.pend, (long)Rp * d, d, s.res, 0, d, tl + (long)A * L_PEND_OUT, A, mostn[l + 1], d, st));
-        RUN(mi_gemm_bf16(s.m2, 2 * d, W.Lw(l, MRG_W), 2 * d, W.Lf(l, MRG_B), 1, s.xo, d, 1, s.res, d, 1.0f, 0, Mo, d, 2 * d, 0, 0, st));
-        if (c.use_macaron) {   // e_branchformer.py:307-309
-            RUN(mi_layernorm_chain(s.xo, d, nullptr, Mo, nullptr, nullptr, 0.f, nullptr, 0, W.Lf(l, FF2_LN_G), W.Lf(l, FF2_LN_B), LEPS, s.a0, d, nullptr, 0, nullptr, nullptr, nullptr, 0, Mo, d, st));
-            RUN(mi_gemm_bf16(s.a0, d, W.Lw(l, FF2_W1), d, W.Lf(l, FF2_B1), 1, s.h, I, 0, nullptr, 0, 1.f, 1, Mo, I, d, 0, 0, st));
-            RUN(mi_gemm_bf16(s.h, I, W.Lw(l, FF2_W2), I, W.Lf(l, FF2_B2), 1, s.xo, d, 1, s.xo, d, 0.5f, 0, Mo, d, I, 0, 0, st));
-        }
-        if (l + 1 < L)         // final_layer_norm (:312): the next layer's input rows
-            RUN(mi_layernorm_chain(s.xo, d, nullptr, Mo, W.Lf(l, FIN_LN_G), W.Lf(l, FIN_LN_B), LEPS, s.x, d, nullptr, nullptr, 0.f, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, Mo, d, st));
-        else                   // chained with encoder.layer_norm -> the head's input
-            RUN(mi_layernorm_chain(s.xo, d, nullptr, Mo, W.Lf(l, FIN_LN_G), W.Lf(l, FIN_LN_B), LEPS, nullptr, 0, W.Gf(G_ENC_LN_G), W.Gf(G_ENC_LN_B), c.ln_eps, s.hid, d, nullptr, 0,
-                                   nullptr, nullptr, nullptr, 0, Mo, d, st));
-    }
-    if (n_out == 0) return MI_OK;
-    // ---- CTC head, per-frame classes, collapse with each slot's carried class
-    RUN(mi_gemm_bf16(s.hid, d, W.Gw(G_HEAD_W), d, W.Gf(G_HEAD_B), 1, logits, g.ldl, 1, nullptr, 0, 1.f, 0, n_out, g.V1, d, 0, 0, st));
-    RUN(mi_row_argmax(logits, g.ldl, 0, g.V1, best, n_out, st));
-    hipLaunchKernelGGL(ctc_collapse_slots_kernel, dim3(A), dim3(64), 0, st, best, c.V, s.prev, ids, n_ids, table + collapse_at(A, L));
-    MI_CHECK_LAUNCH();
-    return MI_OK;
+    const PerSlot at(records, A, g.L, table, st);
+    const Step<PerSlot> step(c, g, state, weights, at, pos_table, st);
+    if (step.s.bytes > state_bytes) return MI_ERR_ARG;
+    return step.run(feats, logits, best, ids, n_ids);
 }

@@ -82,47 +82,49 @@ def _check_streamable(engine, n, chunk_frames, max_frames, what, count):
     return c
 
 
-class EncoderStream:
-    """State of B streams advanced in lock-step through a causal encoder + CTC head (mi_ebf_stream_step).  Created by `EBranchformerEngine.stream`."""
+def _tail_lengths(tail_lengths, B: int, n: int, what: str) -> list:
+    """`tail_lengths` of a finish -> B counts in 0..n (default: n each)"""
+    lens = [n] * B if tail_lengths is None else [int(v) for v in (tail_lengths.tolist() if isinstance(tail_lengths, torch.Tensor) else tail_lengths)]
+    if len(lens) != B or min(lens) < 0 or max(lens) > n:
+        raise ValueError(f"{what}: tail_lengths must be {B} counts in 0..{n}")
+    return lens
 
-    def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
-        c = _check_streamable(engine, batch, chunk_frames, max_frames, "stream()", "batch")
-        self.engine, self.B, self.C, self.max_frames = engine, int(batch), int(chunk_frames), int(max_frames)
+
+class _StreamState:
+    """What `EncoderStream` (n = B streams) and `StreamPool` (n = S slots) hold alike: the geometry of a step, the config struct and the device state of
+    mi_ebf_stream_state_bytes / mi_ebf_stream_reset with its position table."""
+
+    def __init__(self, engine, n: int, chunk_frames: int, max_frames: int, what: str, count: str):
+        c = _check_streamable(engine, n, chunk_frames, max_frames, what, count)
+        self.engine, self._n, self.C, self.max_frames = engine, int(n), int(chunk_frames), int(max_frames)
         self.L = c["num_hidden_layers"]
         self.r = (c.get("merge_conv_kernel", 31) - 1) // 2
         self.F = c.get("num_fbanks", 80)
         self.lookahead = self.L * self.r                # encoder frames between a frame and the last one it depends on
-        self.n_feat = 0
-        self.total = 0                                  # frames emitted so far (per stream, lock-step)
-        self.finished = False
-        self._state = None
-        self._cs = None
-        self.beam = None                                # beams=W: the prefix beam search walks the emitted frames too (ops.CtcBeamStream)
-        if beams is not None:
-            from . import ops
-            self.beam = ops.CtcBeamStream(self.B, self.max_frames, beams=beams, token_topk=token_topk, nbest=nbest, blank=c["vocab_size"], pad_id=-1, dtype=torch.int32,
-                                          return_frames=True)
-        elif token_topk is not None or nbest != 1:
-            raise ValueError("stream(): token_topk and nbest belong to beams=")
+        self._state = self._cs = self._pos = None
 
-    # ------------------------------------------------------------------ state
     def state_bytes(self) -> int:
         return int(_lib.lib().mi_ebf_stream_state_bytes(C.byref(self._config()), self.C, self.max_frames))
 
     def _config(self):
         if self._cs is None:
-            cs = self.engine._config_struct(self.B, SUBSAMPLING * self.C, self.F)
+            cs = self.engine._config_struct(self._n, SUBSAMPLING * self.C, self.F)
             cs.ln_fold = cs.wide_tiles = cs.branch_overlap = 0
             cs.logits_f32 = 1
             self._cs = cs
         return self._cs
 
+    def _may_rebuild(self):
+        """called before a state is built again because the engine's weights changed: raise to refuse"""
+
     def _ensure_state(self):
         e = self.engine
         if e._table is None:
-            raise RuntimeError("EncoderStream: load_state_dict() on the engine first")
+            raise RuntimeError(f"{type(self).__name__}: load_state_dict() on the engine first")
         if self._state is not None and self._version == e.weights_version:
             return
+        if self._state is not None:
+            self._may_rebuild()
         c, dev = e.cfg, e.device
         nbytes = self.state_bytes()
         if nbytes == 0:
@@ -143,6 +145,24 @@ class EncoderStream:
         rc = _lib.lib().mi_ebf_stream_reset(C.byref(self._config()), self.engine._table, self.C, self.max_frames, None if self._pos is None else self._pos.data_ptr(),
                                             self._state.data_ptr(), self._state.numel(), torch.cuda.current_stream().cuda_stream)
         _lib.check(rc, "mi_ebf_stream_reset")
+
+
+class EncoderStream(_StreamState):
+    """State of B streams advanced in lock-step through a causal encoder + CTC head (mi_ebf_stream_step).  Created by `EBranchformerEngine.stream`."""
+
+    def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
+        super().__init__(engine, batch, chunk_frames, max_frames, "stream()", "batch")
+        self.B, c = self._n, engine.cfg
+        self.n_feat = 0
+        self.total = 0                                  # frames emitted so far (per stream, lock-step)
+        self.finished = False
+        self.beam = None                                # beams=W: the prefix beam search walks the emitted frames too (ops.CtcBeamStream)
+        if beams is not None:
+            from . import ops
+            self.beam = ops.CtcBeamStream(self.B, self.max_frames, beams=beams, token_topk=token_topk, nbest=nbest, blank=c["vocab_size"], pad_id=-1, dtype=torch.int32,
+                                          return_frames=True)
+        elif token_topk is not None or nbest != 1:
+            raise ValueError("stream(): token_topk and nbest belong to beams=")
 
     def reset(self):
         """back to the start of B new streams (histories and caches zero, no carried class)"""
@@ -206,9 +226,7 @@ class EncoderStream:
         n = 0 if tail is None else int(tail.shape[1])
         if tail is not None and (tail.dim() != 3 or tail.shape[0] != B or tail.shape[2] != self.F or n > W):
             raise ValueError(f"EncoderStream.finish: the tail is ({B}, 0..{W}, {self.F}), got {tuple(tail.shape)}")
-        lens = [n] * B if tail_lengths is None else [int(v) for v in (tail_lengths.tolist() if isinstance(tail_lengths, torch.Tensor) else tail_lengths)]
-        if len(lens) != B or min(lens) < 0 or max(lens) > n:
-            raise ValueError(f"EncoderStream.finish: tail_lengths must be {B} counts in 0..{n}")
+        lens = _tail_lengths(tail_lengths, B, n, "EncoderStream.finish")
         dev = self.engine.device
         buf = torch.zeros((B, W, self.F), dtype=torch.float32, device=dev)
         if n:
@@ -244,7 +262,7 @@ def pool_table(actions, C: int, L: int, r: int):
     return records, totals
 
 
-class StreamPool:
+class StreamPool(_StreamState):
     """S slots over one stream state, each a session with a position of its own: `open` a slot, `step` any subset of the open slots — each feeds a chunk or finishes, the
     others stay idle and untouched —, a finished slot is free again.  Created by `EBranchformerEngine.stream_pool`.
 
@@ -255,20 +273,14 @@ class StreamPool:
     Concatenated over its calls, a session's logits and ids are those of `engine.stream(1, C, max_frames)` fed the same pieces, whatever the other slots do."""
 
     def __init__(self, engine, slots: int, chunk_frames: int, max_frames: int, *, beams=None):
-        c = _check_streamable(engine, slots, chunk_frames, max_frames, "stream_pool()", "slots")
+        super().__init__(engine, slots, chunk_frames, max_frames, "stream_pool()", "slots")
         if beams is not None:
             raise NotImplementedError("stream_pool(): beams= is not a constructor keyword of the pool: the prefix beam search per slot is switched on by a method, "
                                       "stream_pool(...).with_beams(beams, token_topk=None, nbest=1), before the first session is opened")
-        self.engine, self.S, self.C, self.max_frames = engine, int(slots), int(chunk_frames), int(max_frames)
-        self.L = c["num_hidden_layers"]
-        self.r = (c.get("merge_conv_kernel", 31) - 1) // 2
-        self.F = c.get("num_fbanks", 80)
-        self.lookahead = self.L * self.r
+        self.S = self._n
         self.is_open = [False] * self.S
         self.n_feat = [0] * self.S                      # feature frames the slot's session has had
         self.total = [0] * self.S                       # frames it has emitted
-        self._state = None
-        self._cs = None
         self.beam = None                                # with_beams(): the prefix beam search walks every slot's emitted frames too (ops.CtcBeamPool)
 
     def with_beams(self, beams, *, token_topk=None, nbest=1):
@@ -285,43 +297,9 @@ class StreamPool:
                                     dtype=torch.int32, return_frames=True)
         return self
 
-    # ------------------------------------------------------------------ state
-    def _config(self):
-        if self._cs is None:
-            cs = self.engine._config_struct(self.S, SUBSAMPLING * self.C, self.F)
-            cs.ln_fold = cs.wide_tiles = cs.branch_overlap = 0
-            cs.logits_f32 = 1
-            self._cs = cs
-        return self._cs
-
-    def state_bytes(self) -> int:
-        return int(_lib.lib().mi_ebf_stream_state_bytes(C.byref(self._config()), self.C, self.max_frames))
-
-    def _ensure_state(self):
-        e = self.engine
-        if e._table is None:
-            raise RuntimeError("StreamPool: load_state_dict() on the engine first")
-        if self._state is not None and self._version == e.weights_version:
-            return
-        if self._state is not None and any(self.is_open):
+    def _may_rebuild(self):
+        if any(self.is_open):
             raise RuntimeError("StreamPool: the engine's weights changed while sessions were open")
-        c, dev = e.cfg, e.device
-        nbytes = self.state_bytes()
-        if nbytes == 0:
-            raise RuntimeError("mi_ebf_stream_state_bytes refused the configuration")
-        self._state = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        d, H = c["hidden_size"], c["num_attention_heads"]
-        ptype = c.get("position_embeddings_type", "relative")
-        self._pos = None
-        if ptype == "relative":
-            self._pos = relative_position_table(self.max_frames, d)[: self.max_frames].flip(0).to(dev).to(torch.bfloat16).contiguous()
-        elif ptype == "rotary":
-            cos, sin = rotary_tables(self.max_frames, d // H, c.get("rotary_embedding_base", 10000))
-            self._pos = torch.cat([cos.reshape(-1), sin.reshape(-1)]).to(dev).contiguous()
-        self._version = e.weights_version
-        rc = _lib.lib().mi_ebf_stream_reset(C.byref(self._config()), e._table, self.C, self.max_frames, None if self._pos is None else self._pos.data_ptr(),
-                                            self._state.data_ptr(), self._state.numel(), torch.cuda.current_stream().cuda_stream)
-        _lib.check(rc, "mi_ebf_stream_reset")
 
     # ------------------------------------------------------------------ sessions
     def open(self) -> int:
@@ -342,16 +320,20 @@ class StreamPool:
         self.n_feat[sid] = self.total[sid] = 0
         return sid
 
+    def _check_named(self, sid, first, finish, what, first_name):
+        """slot `sid` of a step's or push's two dicts: named once, and holding an open session"""
+        if sid in first and sid in finish:
+            raise ValueError(f"{what}: slot {sid} is named in both {first_name} and finish")
+        if not isinstance(sid, int) or not 0 <= sid < self.S or not self.is_open[sid]:
+            raise RuntimeError(f"{what}: slot {sid} holds no open session (free or finished): open() starts one")
+
     def actions(self, feed=None, finish=None):
         """the checked actions of a step, ordered by slot -> [(slot, n_prev, n, finish, tensor or None)]"""
         feed, finish = dict(feed or {}), dict(finish or {})
         W = SUBSAMPLING * self.C
         acts = []
         for sid in sorted(set(feed) | set(finish)):
-            if sid in feed and sid in finish:
-                raise ValueError(f"StreamPool.step: slot {sid} is named in both feed and finish")
-            if not isinstance(sid, int) or not 0 <= sid < self.S or not self.is_open[sid]:
-                raise RuntimeError(f"StreamPool.step: slot {sid} holds no open session (free or finished): open() starts one")
+            self._check_named(sid, feed, finish, "StreamPool.step", "feed")
             if sid in feed:
                 x = feed[sid]
                 if x is None or tuple(x.shape) != (W, self.F):
@@ -629,9 +611,7 @@ class AudioStream:
             tail = torch.zeros((self.B, 0), dtype=torch.float32)
         tail = self._samples(tail, "AudioStream.finish")
         n = int(tail.shape[1])
-        lens = [n] * self.B if tail_lengths is None else [int(v) for v in (tail_lengths.tolist() if isinstance(tail_lengths, torch.Tensor) else tail_lengths)]
-        if len(lens) != self.B or min(lens) < 0 or max(lens) > n:
-            raise ValueError(f"AudioStream.finish: tail_lengths must be {self.B} counts in 0..{n}")
+        lens = _tail_lengths(tail_lengths, self.B, n, "AudioStream.finish")
         self._room(self.n + max(lens))
         steps = audio_pieces(self.n, lens, self.stream.n_feat, self.C, finish=True)
         return self._run(tail.reshape(-1), n, lens, steps)
@@ -673,10 +653,7 @@ class AudioPool:
         audio, finish = dict(audio or {}), dict(finish or {})
         pieces = {}
         for sid in sorted(set(audio) | set(finish)):
-            if sid in audio and sid in finish:
-                raise ValueError(f"AudioPool.push: slot {sid} is named in both audio and finish")
-            if not isinstance(sid, int) or not 0 <= sid < self.S or not self.pool.is_open[sid]:
-                raise RuntimeError(f"AudioPool.push: slot {sid} holds no open session (free or finished): open() starts one")
+            self.pool._check_named(sid, audio, finish, "AudioPool.push", "audio")
             pieces[sid] = audio[sid] if sid in audio else finish[sid]
         if not pieces:
             return {}

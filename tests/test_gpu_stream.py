@@ -207,6 +207,45 @@ def test_refusals_on_the_device(batch3):
         st.feed(x[:, :15].to(DEV))
 
 
+def test_step_refuses_bad_plans(tiny):
+    """the plan check the lock-step step shares with the pool's records, from the lock-step side: six malformed `rows` (L = 2, r = 15, C = 2, max_frames = 40; each
+    breaks one rule) return MI_ERR_ARG before any launch — the state stays bit for bit — and the same six as one pool record fail mi_ebf_stream_slots_table (host only)"""
+    import ctypes as C
+    from huggingface_asr_amd import _lib
+    eng = tiny["eng"]
+    st = eng.stream(1, 2, 40)
+    st.feed(tiny["x"][:1, :8].to(DEV))                      # one good step: rows (0, 2), (0, 0), (0, 0)
+    cs, lib = st._config(), _lib.lib()
+    feats = torch.zeros((1, 8, 80), device=DEV)
+    lbuf, ints = torch.zeros((32, cs.logits_ld), device=DEV), torch.zeros((3, 32), dtype=torch.int32, device=DEV)
+    ends = torch.tensor([4], dtype=torch.int32, device=DEV)
+    bad = [([(4, 2), (0, 0), (0, 0)], False),               # a frontier that decreases
+           ([(2, 5), (0, 0), (0, 0)], False),               # hi - lo > C at entry 0
+           ([(39, 41), (24, 26), (9, 11)], False),          # hi past max_frames
+           ([(2, 4), (0, 1), (0, 0)], False),               # a layer emitting more than a_l - r without ends
+           ([(2, 4), (0, 4), (0, 3)], True),                # hi != the previous hi with ends
+           ([(-1, 1), (0, 0), (0, 0)], False)]              # a negative lo
+    good = plan(16, 2, st.L, st.r, False)
+    assert (st.L, st.r) == (2, 15) and good == [(2, 4), (0, 0), (0, 0)]
+
+    def table(rows, fin):
+        rec = torch.tensor([0, rows[0][1] if fin else -1] + [v for lo, hi in rows for v in (lo, hi, 0)], dtype=torch.int32)
+        return lib.mi_ebf_stream_slots_table(C.byref(cs), 2, 40, rec.data_ptr(), 1, None, 0)
+
+    assert table(good, False) > 0                           # the same call takes a plan that is one
+    torch.cuda.synchronize()
+    before = st._state.clone()
+    for rows, fin in bad:
+        flat = (C.c_int * 6)(*[v for lo_hi in rows for v in lo_hi])
+        rc = lib.mi_ebf_stream_step(C.byref(cs), eng._table, 2, 40, None if st._pos is None else st._pos.data_ptr(), st._state.data_ptr(), st._state.numel(), feats.data_ptr(),
+                                    flat, ends.data_ptr() if fin else None, lbuf.data_ptr(), ints[0].data_ptr(), ints[1].data_ptr(), ints[2].data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream)
+        assert rc == _lib.ERR_ARG, (rows, fin, rc)
+        assert table(rows, fin) == _lib.ERR_ARG, (rows, fin)
+    torch.cuda.synchronize()
+    assert torch.equal(st._state, before)                   # nothing was launched
+
+
 def test_model_stream_equals_engine_stream():
     from huggingface_asr_amd.configuration_ebranchformer import Wav2Vec2EBranchformerConfig
     from huggingface_asr_amd.engine import cfg_from_hf
