@@ -86,6 +86,15 @@ SIGNATURES = {
     "mi_ctc_beam_stream_walk": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp],
     "mi_ctc_beam_stream_reset_slot": [vp, sz, i32, i32, i32, i32, vp],
     "mi_ctc_beam_stream_walk_slots": [vp, i64, i32, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp],
+    # contextual biasing: each counterpart's arguments, then bias_col, bias_tab, S, A1, weight, credit before the stream
+    "mi_ctc_beam_walk_bias": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp, i32, vp, vp, vp, vp, vp, i32, i32, f32, vp, vp],
+    "mi_ctc_beam_bias_stream_state_bytes": [i32, i32, i32],
+    "mi_ctc_beam_bias_stream_reset": [vp, sz, i32, i32, i32, vp],
+    "mi_ctc_beam_bias_stream_walk": [vp, i64, i64, i32, i32, i32, i32, vp, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                     vp, vp, i32, i32, f32, vp, vp],
+    "mi_ctc_beam_bias_stream_reset_slot": [vp, sz, i32, i32, i32, i32, vp],
+    "mi_ctc_beam_bias_stream_walk_slots": [vp, i64, i32, i32, i32, i32, i64, i32, i32, i32, vp, vp, vp, vp, vp, sz, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp,
+                                           i32, vp, vp, i32, i32, f32, vp, vp],
     "mi_ctc_align_workspace_bytes": [i32, i32, i32],
     "mi_ctc_align": [vp, i64, i64, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, sz, vp, vp, vp, vp, vp, vp, vp],
     "mi_gemm_argmax_workspace_floats": [i32, i32],
@@ -270,7 +279,7 @@ def lib():
             fn.argtypes = args
             fn.restype = sz if name in ("mi_ebf_workspace_bytes", "mi_ctc_bwd_workspace_bytes", "mi_gemm_tn_workspace_bytes", "mi_layernorm_bwd_workspace_floats",
                                           "mi_colsum_workspace_floats", "mi_conv2d_first_bwd_workspace_floats", "mi_conv2d_s2k3_dgrad_elems", "mi_conv2d_first_wgrad_workspace_floats", "mi_embed_tokens_bwd_workspace_bytes",
-                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes", "mi_ctc_beam_stream_state_bytes", "mi_ctc_align_workspace_bytes",
+                                          "mi_gpt2_step_workspace_bytes", "mi_decoder_step_taps_workspace_bytes", "mi_mix_ce_bwd_workspace_floats", "mi_linear_rows_workspace_bytes", "mi_gemm_lse_workspace_floats", "mi_gemm_argmax_workspace_floats", "mi_ctc_beam_workspace_bytes", "mi_ctc_beam_stream_state_bytes", "mi_ctc_beam_bias_stream_state_bytes", "mi_ctc_align_workspace_bytes",
                                           "mi_attention_f32_workspace_bytes", "mi_ebf_f32_workspace_bytes", "mi_ebf_stream_state_bytes", "mi_linear_rows_f32_workspace_bytes", "mi_decoder_step_f32_workspace_bytes", "mi_fbank_stream_state_bytes") else i32
         h.mi_profile_create.argtypes = [i32]; h.mi_profile_create.restype = i32
         h.mi_profile_enable.argtypes = [i32]; h.mi_profile_enable.restype = None

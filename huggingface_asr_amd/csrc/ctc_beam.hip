@@ -173,45 +173,13 @@ __global__ __launch_bounds__(CUT_THREADS) void ctc_cut_kernel(CutArgs p) {
 }
 
 // ---- launch B
-struct WalkArgs {
-    const void* x; long ld_t, ld_b; int dtype;
-    int B, T, V1;
-    const int* lengths;
-    int blank; long pad_id;
-    int W, K, nbest;
-    const float* lse; const float* lpb; const float* cut_lp; const int* cut_id;
-    int4* arena; long arena_stride;                                    // per utterance: 1 + T W nodes (parent, token, frame, length)
-    u64* table; long table_stride;                                     // per utterance: the (parent node, token) -> node table
-    void* tokens; int* n_tokens; float* scores; int* frames;
-};
-
-// the frame step (walk_frame) and the backtrace (walk_backtrace) are ctc_walk_step.hpp's: ctc_beam_stream.hip walks with the same ones
+// the arguments (WalkArgs), the utterance's walk (walk_utterance), the frame step (walk_frame) and the backtrace (walk_backtrace) are ctc_walk_step.hpp's: the stream and
+// pool kernels walk with the same step, and ctc_beam_bias.hip's ctc_bias_walk is this kernel with the bias policy
 template <typename TOK>
 __global__ __launch_bounds__(1024) void ctc_walk_kernel(WalkArgs p) {
     __shared__ WalkLds L;
-    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const int W = p.W, T = p.T, nbest = p.nbest;
-    const int n_b = p.lengths ? min(max(p.lengths[b], 0), T) : T;
-    int4* arena = p.arena + (long)b * p.arena_stride;
-    u64* table = p.table + (long)b * p.table_stride;
-    unsigned H = 2;                                                    // this utterance's table: a power of two >= 2 (1 + n_b W) words (<= table_stride)
-    while (H < 2u * (1u + (unsigned)n_b * (unsigned)W)) H <<= 1;
-    for (unsigned i = tid; i < H; i += nt) __hip_atomic_store(&table[i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tid == 0) {
-        Beam& s = L.beams[0];
-        s.pb[0] = 0.f; s.pnb[0] = NEG_INF; s.sc[0] = 0.f; s.node[0] = 0; s.last[0] = -1; s.parent[0] = -1; s.len[0] = 0;
-        arena[0] = make_int4(-1, -1, -1, 0);
-        L.n_nodes[0] = 1;
-    }
-    __syncthreads();
-
-    const WalkIn q{p.x, p.dtype, W, p.K, min(p.K, p.V1 - 1), p.lse, p.lpb, p.cut_lp, p.cut_id, arena, p.arena_stride, table, H};
-    int n = 1, cur = 0;
-    for (int t = 0; t < n_b && n > 0; ++t, cur ^= 1) n = walk_frame(L, q, cur, n, (long)b * T + t, (long)b * p.ld_b + (long)t * p.ld_t, t);
-
-    // ---- the n best, backtraced; rows that do not exist
-    walk_backtrace<TOK>(L, L.beams[cur], n, nbest, T, arena, p.arena_stride, p.pad_id, (TOK*)p.tokens + (long)b * nbest * T,
-                        p.frames ? p.frames + (long)b * nbest * T : nullptr, p.n_tokens + (long)b * nbest, p.scores + (long)b * nbest);
+    int n;
+    walk_utterance<TOK>(L, p, NoBias{}, blockIdx.x, n);
 }
 
 }  // namespace
@@ -239,16 +207,11 @@ extern "C" int mi_ctc_beam_walk(const void* logits, long ld_row, long ld_batch, 
                                 int nbest, const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* workspace, size_t workspace_bytes,
                                 void* tokens, int tokens_dtype, int* n_tokens, float* scores, int* frames, hipStream_t stream) {
     MI_ENTER();
-    if (!logits || !lse || !lp_blank || !cut_lp || !cut_id || !workspace || !tokens || !n_tokens || !scores || B <= 0 || T <= 0 || V1 < 2 || W < 1 || W > CB_MAXW || K < 1 ||
-        K > CB_MAXK || nbest < 1 || nbest > W || blank < 0 || blank >= V1 || (dtype != 0 && dtype != 1) || (tokens_dtype != 0 && tokens_dtype != 1))
-        return MI_ERR_ARG;
-    if (!walk_sizes_ok(T, W, V1)) return MI_ERR_UNSUPPORTED;
-    if (workspace_bytes < mi_ctc_beam_workspace_bytes(B, T, W) || (reinterpret_cast<uintptr_t>(workspace) & 15)) return MI_ERR_ARG;
-    const long nodes = 1 + (long)T * W, words = table_words(T, W);
-    WalkArgs a{logits, ld_row, ld_batch, dtype, B, T, V1, lengths, blank, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id,
-               (int4*)workspace, nodes, (u64*)((char*)workspace + align16((size_t)B * nodes * sizeof(int4))), words, tokens, n_tokens, scores, frames};
-    const int Kk = K < V1 - 1 ? K : V1 - 1;
-    const dim3 block(W * (Kk + 1) <= 1024 ? 256 : 1024);
+    WalkArgs a;
+    dim3 block;
+    const int rc = walk_prepare(logits, ld_row, ld_batch, dtype, B, T, V1, lengths, blank, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id, workspace, workspace_bytes,
+                                mi_ctc_beam_workspace_bytes(B, T, W), tokens, tokens_dtype, n_tokens, scores, frames, a, block);
+    if (rc != MI_OK) return rc;
     if (tokens_dtype == 0) hipLaunchKernelGGL(ctc_walk_kernel<int>, dim3(B), block, 0, stream, a);
     else hipLaunchKernelGGL(ctc_walk_kernel<long>, dim3(B), block, 0, stream, a);
     MI_CHECK_LAUNCH();

@@ -31,16 +31,12 @@
 //
 // Budget (hipcc --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage; tests/test_stream_pool_beam_cpu.py reads it from the built code object):
 //   ctc_pool_beam_kernel   256 or 1024 threads, <= 128 VGPRs, 44576 B of LDS (the lock-step kernel's); no scratch
-#include <vector>
-
 #include "common.hpp"
 #include "radix_select.hpp"
 #include "ctc_beam_stream_body.hpp"
 #include "../../include/hfasr_hip.h"
 
 namespace {
-
-constexpr int REC_WORDS = 5;                                           // slot, row0, n, final, out
 
 struct PoolArgs {
     StreamState st; StreamIo io;
@@ -61,10 +57,9 @@ __global__ __launch_bounds__(64) void ctc_pool_reset_slot_kernel(StreamState st,
 template <typename TOK>
 __global__ __launch_bounds__(1024) void ctc_pool_beam_kernel(PoolArgs p) {
     __shared__ WalkLds L;
-    const int* rec = p.records + (long)blockIdx.x * REC_WORDS;
-    const int slot = rec[0], row0 = rec[1], n = rec[2], final = rec[3], out = rec[4];
-    if (slot < 0 || slot >= p.S || row0 < 0 || n < 0 || (long)row0 + n > p.rows || out >= p.R) return;      // (the host has refused it: block-uniform, before any barrier)
-    stream_beam_call<TOK>(L, p.st, p.io, slot, (long)row0 * p.io.ld_t, row0, n, final != 0, out);
+    int slot, row0, n, final, out;
+    if (!pool_record(p.records, p.S, p.rows, p.R, slot, row0, n, final, out)) return;      // (the host has refused it: block-uniform, before any barrier)
+    stream_beam_call<TOK>(L, p.st, p.io, NoBias{}, slot, (long)row0 * p.io.ld_t, row0, n, final != 0, out);
 }
 
 }  // namespace
@@ -86,32 +81,13 @@ extern "C" int mi_ctc_beam_stream_walk_slots(const void* logits, long ld_row, in
                                              const int* records_host, int A, const int* records_dev, int* committed, int* committed_frames, int* n_committed, int* n_new,
                                              void* tokens, int tokens_dtype, int* n_tokens, float* scores, int* frames, int R, hipStream_t stream) {
     MI_ENTER();
-    if (!state || !committed || !committed_frames || !n_committed || !n_new || !records_host || !records_dev || S <= 0 || A <= 0 || A > S || rows < 0 || R < 0 || R > A ||
-        max_frames <= 0 || V1 < 2 || W < 1 || W > CB_MAXW || K < 1 || K > CB_MAXK || nbest < 1 || nbest > W || blank < 0 || blank >= V1 || (dtype != 0 && dtype != 1) ||
-        (tokens_dtype != 0 && tokens_dtype != 1))
-        return MI_ERR_ARG;
-    if (rows > 0 && (!logits || !lse || !lp_blank || !cut_lp || !cut_id)) return MI_ERR_ARG;
-    if (R > 0 && (!tokens || !n_tokens || !scores)) return MI_ERR_ARG;
-    if (!tokens && frames) return MI_ERR_ARG;
-    if (!walk_sizes_ok(max_frames, W, V1)) return MI_ERR_UNSUPPORTED;
-    if (state_bytes < mi_ctc_beam_stream_state_bytes(S, max_frames, W) || (reinterpret_cast<uintptr_t>(state) & 15)) return MI_ERR_ARG;
-    std::vector<char> slot_seen(S, 0), out_seen(R, 0);
-    for (int i = 0; i < A; ++i) {
-        const int* r = records_host + (long)i * REC_WORDS;
-        const int slot = r[0], row0 = r[1], n = r[2], final = r[3], out = r[4];
-        if (slot < 0 || slot >= S || slot_seen[slot]) return MI_ERR_ARG;
-        if (row0 < 0 || n < 0 || (long)row0 + n > rows) return MI_ERR_ARG;
-        if ((final != 0 && final != 1) || out < -1 || out >= R || (final && out < 0)) return MI_ERR_ARG;
-        if (out >= 0 && out_seen[out]) return MI_ERR_ARG;
-        slot_seen[slot] = 1;
-        if (out >= 0) out_seen[out] = 1;
-    }
-    PoolArgs a{stream_state_at(state, S, max_frames, W),
-               StreamIo{logits, ld_row, dtype, V1, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id, committed, committed_frames, n_committed, n_new, tokens, n_tokens,
-                        scores, frames},
-               records_dev, S, rows, R};
-    const int Kk = K < V1 - 1 ? K : V1 - 1;
-    const dim3 block(W * (Kk + 1) <= 1024 ? 256 : 1024);
+    PoolArgs a{};
+    const int rc = pool_prepare(logits, ld_row, dtype, rows, V1, blank, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id, state, state_bytes,
+                                stream_state_bytes(S, max_frames, W), S, max_frames, records_host, A, records_dev, committed, committed_frames, n_committed, n_new, tokens,
+                                tokens_dtype, n_tokens, scores, frames, R, a.st, a.io);
+    if (rc != MI_OK) return rc;
+    a.records = records_dev; a.S = S; a.rows = rows; a.R = R;
+    const dim3 block = walk_block(W, K, V1);
     if (tokens_dtype == 0) hipLaunchKernelGGL(ctc_pool_beam_kernel<int>, dim3(A), block, 0, stream, a);
     else hipLaunchKernelGGL(ctc_pool_beam_kernel<long>, dim3(A), block, 0, stream, a);
     MI_CHECK_LAUNCH();

@@ -69,14 +69,13 @@ __global__ __launch_bounds__(1024) void ctc_stream_beam_kernel(StreamArgs p) {
     __shared__ WalkLds L;
     const int b = blockIdx.x, T = p.T;
     const int n_call = p.n_valid ? min(max(p.n_valid[b], 0), T) : T;
-    stream_beam_call<TOK>(L, p.st, p.io, b, (long)b * p.ld_b, (long)b * T, n_call, p.final, p.io.tokens ? b : -1);
+    stream_beam_call<TOK>(L, p.st, p.io, NoBias{}, b, (long)b * p.ld_b, (long)b * T, n_call, p.final, p.io.tokens ? b : -1);
 }
 
 }  // namespace
 
 extern "C" size_t mi_ctc_beam_stream_state_bytes(int B, int max_frames, int W) {
-    if (!stream_sizes_ok(B, max_frames, W)) return 0;
-    return stream_head_bytes(B) + align16((size_t)B * (1 + (size_t)max_frames * W) * sizeof(int4)) + (size_t)B * table_words(max_frames, W) * sizeof(u64);
+    return stream_state_bytes(B, max_frames, W);
 }
 
 extern "C" int mi_ctc_beam_stream_reset(void* state, size_t state_bytes, int B, int max_frames, int W, hipStream_t stream) {
@@ -96,22 +95,13 @@ extern "C" int mi_ctc_beam_stream_walk(const void* logits, long ld_row, long ld_
                                        size_t state_bytes, int max_frames, int final, int* committed, int* committed_frames, int* n_committed, int* n_new,
                                        void* tokens, int tokens_dtype, int* n_tokens, float* scores, int* frames, hipStream_t stream) {
     MI_ENTER();
-    if (!state || !committed || !committed_frames || !n_committed || !n_new || B <= 0 || T_call < 0 || max_frames <= 0 || V1 < 2 || W < 1 || W > CB_MAXW || K < 1 ||
-        K > CB_MAXK || nbest < 1 || nbest > W || blank < 0 || blank >= V1 || (dtype != 0 && dtype != 1) || (tokens_dtype != 0 && tokens_dtype != 1) ||
-        (final != 0 && final != 1))
-        return MI_ERR_ARG;
-    if (T_call > 0 && (!logits || !lse || !lp_blank || !cut_lp || !cut_id)) return MI_ERR_ARG;
-    if (tokens && (!n_tokens || !scores)) return MI_ERR_ARG;
-    if (!tokens && (frames || final)) return MI_ERR_ARG;               // the final call always returns the n best
-    if (!walk_sizes_ok(max_frames, W, V1)) return MI_ERR_UNSUPPORTED;
-    if ((long)B * T_call >= (1l << 31)) return MI_ERR_UNSUPPORTED;
-    if (state_bytes < mi_ctc_beam_stream_state_bytes(B, max_frames, W) || (reinterpret_cast<uintptr_t>(state) & 15)) return MI_ERR_ARG;
-    StreamArgs a{stream_state_at(state, B, max_frames, W),
-                 StreamIo{logits, ld_row, dtype, V1, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id, committed, committed_frames, n_committed, n_new, tokens, n_tokens,
-                          scores, frames},
-                 ld_batch, B, T_call, n_valid, final};
-    const int Kk = K < V1 - 1 ? K : V1 - 1;
-    const dim3 block(W * (Kk + 1) <= 1024 ? 256 : 1024);
+    StreamArgs a{};
+    const int rc = stream_prepare(logits, ld_row, dtype, B, T_call, V1, blank, pad_id, W, K, nbest, lse, lp_blank, cut_lp, cut_id, state, state_bytes,
+                                  stream_state_bytes(B, max_frames, W), max_frames, final, committed, committed_frames, n_committed, n_new, tokens, tokens_dtype, n_tokens,
+                                  scores, frames, a.st, a.io);
+    if (rc != MI_OK) return rc;
+    a.ld_b = ld_batch; a.B = B; a.T = T_call; a.n_valid = n_valid; a.final = final;
+    const dim3 block = walk_block(W, K, V1);
     if (tokens_dtype == 0) hipLaunchKernelGGL(ctc_stream_beam_kernel<int>, dim3(B), block, 0, stream, a);
     else hipLaunchKernelGGL(ctc_stream_beam_kernel<long>, dim3(B), block, 0, stream, a);
     MI_CHECK_LAUNCH();

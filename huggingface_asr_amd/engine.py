@@ -295,7 +295,7 @@ class EBranchformerEngine:
         return feats, cs, T2, ws, pos, posp, compute
 
     def transcribe(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None = None, *, span="valid", pad_id=0, slot=0, want_hidden=False, return_frames=False,
-                   dtype=torch.int64, beams=None, token_topk=None, nbest=1):
+                   dtype=torch.int64, beams=None, token_topk=None, nbest=1, bias=None):
         """CTC transcription on the device, greedy or (with `beams`) by prefix beam search.
         beams=None: feats (B,T,F) -> dict(tokens (B,T2) `dtype` = the token ids then pad_id, n_tokens (B) int32, best (B,T2) int32 = the
         per-frame classes, inner_len, outer_len[, frames (B,T2) int32 = the frame each token starts at, then -1][, last_hidden]).  Blank = the last class.
@@ -305,15 +305,20 @@ class EBranchformerEngine:
         classes per frame, None = min(W, V)): tokens / n_tokens[/ frames] are the best hypothesis' (tokens (B,T2)), and the dict gains nbest_tokens (B,nbest,T2),
         nbest_n (B,nbest), scores (B,nbest) fp32[, nbest_frames (B,nbest,T2)]; no `best`.
         precision="fp32": the fp32 head GEMM writes its logits into a scratch, mi_row_argmax reads it and mi_ctc_collapse follows; `head_argmax` / `head_lse` are
-        ignored in this mode (there is no fused fp32 head).  beams=W runs ops.ctc_beam_decode over the fp32 logits as above."""
+        ignored in this mode (there is no fused fp32 head).  beams=W runs ops.ctc_beam_decode over the fp32 logits as above.
+        bias (a ctc_bias.CtcBias for this model's V + 1 classes, blank V; needs beams): contextual biasing of that search (csrc/ctc_beam_bias.hip): the dict gains
+        credit (B) int32, the best hypothesis' credited tokens, and nbest_credit (B,nbest)."""
         if span not in ("valid", "all"):
             raise ValueError(f"transcribe: span must be 'valid' or 'all', got {span!r}")
+        self._check_bias("transcribe", bias, beams)
         if beams is not None:
             fwd = self.forward(feats, feat_lengths, want_hidden=want_hidden, want_logits=True, slot=slot)
             bo = ops.ctc_beam_decode(fwd["logits"], self.cfg["vocab_size"], pad_id, fwd["outer_len"] if span == "valid" else None, beams=beams, token_topk=token_topk,
-                                     nbest=nbest, return_frames=return_frames, dtype=dtype)
+                                     nbest=nbest, return_frames=return_frames, dtype=dtype, bias=bias)
             out = dict(tokens=bo["tokens"][:, 0], n_tokens=bo["n_tokens"][:, 0], nbest_tokens=bo["tokens"], nbest_n=bo["n_tokens"], scores=bo["scores"],
                        inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
+            if bias is not None:
+                out.update(credit=bo["credit"][:, 0], nbest_credit=bo["credit"])
             if return_frames:
                 out.update(frames=bo["frames"][:, 0], nbest_frames=bo["frames"])
             if want_hidden:
@@ -353,6 +358,19 @@ class EBranchformerEngine:
             out["last_hidden"] = hidden
         return out
 
+    def _check_bias(self, what, bias, beams):
+        """bias= on the host, before any launch: it needs beams, is a ctc_bias.CtcBias, and was built for this model's classes and blank"""
+        if bias is None:
+            return
+        from .ctc_bias import CtcBias
+        if not isinstance(bias, CtcBias):
+            raise TypeError(f"{what}: bias is a ctc_bias.CtcBias (model.bias_context builds one), got {type(bias).__name__}")
+        if beams is None:
+            raise ValueError(f"{what}: bias= biases the prefix beam search: it needs beams=")
+        V = self.cfg["vocab_size"]
+        if bias.vocab != V + 1 or bias.blank != V:
+            raise ValueError(f"{what}: the bias context was built for vocab {bias.vocab}, blank {bias.blank}; this model has {V + 1} classes, blank {V}")
+
     def align(self, feats: torch.Tensor, feat_lengths: torch.Tensor | None, labels: torch.Tensor, *, span="valid", slot=0):
         """CTC forced alignment of `labels` (B, U) int64 (negative entries are padding) to feats (B,T,F): the forward that yields fp32-or-`logits_dtype` logits — with
         their row log-sum-exp out of the head's epilogue where `head_lse` is on, else (and in precision="fp32") by ops.row_lse — then ops.ctc_align over them.
@@ -368,16 +386,18 @@ class EBranchformerEngine:
         out.update(inner_len=fwd["inner_len"], outer_len=fwd["outer_len"])
         return out
 
-    def stream(self, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
+    def stream(self, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1, bias=None):
         """Streaming inference of a causal model (bf16): -> streaming.EncoderStream for `batch` streams advanced in lock-step, `chunk_frames` encoder frames (4x as many
         feature frames) per `feed`, K/V caches of `max_frames` encoder frames.  Fed an utterance piece by piece it returns forward()'s logits of that utterance alone, each
         frame num_hidden_layers * (merge_conv_kernel - 1) / 2 frames late (csrc/stream.hip; DESIGN.md §4 'Streaming').  Refused before any launch: a non-causal config
         (ValueError); precision="fp32", layer mixing, an additional layer (NotImplementedError).
         beams=W (1..64): the stream also walks the prefix beam search of transcribe(beams=) over the frames it emits (ops.CtcBeamStream, csrc/ctc_beam_stream.hip): `feed`
         and `finish` gain a "beam" entry — the committed tokens after every step, the `nbest` hypotheses at `finish` (and per step with feed(..., partial=True)) —, bit
-        for bit what ops.ctc_beam_decode gives on the concatenated logits.  Without beams nothing is allocated and no launch is added."""
+        for bit what ops.ctc_beam_decode gives on the concatenated logits.  Without beams nothing is allocated and no launch is added.
+        bias (a ctc_bias.CtcBias; needs beams): contextual biasing of that search, as transcribe(beams=, bias=); the "beam" dicts gain credit beside the n-best."""
         from .streaming import EncoderStream
-        return EncoderStream(self, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
+        self._check_bias("stream", bias, beams)
+        return EncoderStream(self, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, bias=bias)
 
     def stream_pool(self, slots: int, chunk_frames: int, max_frames: int, *, beams=None):
         """Streaming inference for sessions that start, idle and end on their own: -> streaming.StreamPool of `slots` slots over one state.  `open()` gives a free slot;
@@ -391,14 +411,15 @@ class EBranchformerEngine:
         return StreamPool(self, slots, chunk_frames, max_frames, beams=beams)
 
     def audio_stream(self, batch: int, chunk_frames: int, max_frames: int, *, normalize=None, global_means=None, global_stds=None, beams=None, token_topk=None, nbest=1,
-                     max_push_samples=None, tables=None):
+                     max_push_samples=None, tables=None, bias=None):
         """`stream` fed audio: -> streaming.AudioStream.  `push(samples (B, n))` takes fp32 samples in [-1, 1] or int16 PCM in pieces of any size, `finish(tail, lengths)`
         ends the streams; the stateful log-mel front end (csrc/fbank_stream.hip) gives, bit for bit, the features of fbank_gpu on the whole utterance with normalize=None
         or "global" (global_means / global_stds (F)), so the logits are those of `stream` fed these features in the pieces streaming.audio_pieces names.  Refusals as
         `stream`'s; normalize="utterance" raises NotImplementedError (utterance CMVN needs the whole utterance).  DESIGN.md §4 'Audio in'."""
         from .streaming import AudioStream
+        self._check_bias("audio_stream", bias, beams)                      # bias= as on `stream`
         return AudioStream(self, batch, chunk_frames, max_frames, normalize=normalize, global_means=global_means, global_stds=global_stds, beams=beams,
-                           token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, tables=tables)
+                           token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, tables=tables, bias=bias)
 
     def audio_pool(self, slots: int, chunk_frames: int, max_frames: int, *, normalize=None, global_means=None, global_stds=None, beams=None, max_push_samples=None,
                    tables=None):

@@ -276,13 +276,32 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
             return (loss, out["logits"]) + ((hidden_states,) if hidden_states is not None else ())
         return CausalLMOutput(loss=loss, logits=out["logits"], hidden_states=hidden_states, attentions=None)
 
-    def transcribe(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, span: str = "valid"):
+    def bias_context(self, phrases, weight: float, tokenizer=None):
+        """A phrase list for contextual biasing of the CTC prefix beam search (ctc_bias.CtcBias; DESIGN.md §4 'Contextual biasing') over this model's classes, blank =
+        config.vocab_size: `phrases` are lists of token ids, taken as they are, or strings, which go through `tokenizer(text, add_special_tokens=False).input_ids`;
+        `weight` is in log-probability units per credited token.  Pure host work; pass the result as bias= to transcribe / stream / audio_stream (with beams=) or to
+        stream_pool(...).with_beams(W, bias=) / audio_pool(...).with_beams(W, bias=)."""
+        from .ctc_bias import CtcBias
+        ids = []
+        for ph in phrases:
+            if isinstance(ph, str):
+                if tokenizer is None:
+                    raise ValueError("bias_context: a phrase given as text needs tokenizer=")
+                ph = tokenizer(ph, add_special_tokens=False).input_ids
+            ids.append(list(ph))
+        return CtcBias(ids, weight, self.config.vocab_size + 1, self.config.vocab_size)
+
+    def transcribe(self, input_values: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, span: str = "valid", *, beams=None, token_topk=None, nbest=1, bias=None):
         """CTC greedy transcription on the device (eval mode only): -> (tokens (B, T') int64 = each utterance's token ids then config.pad_token_id, n_tokens (B) int32).
         span "valid" cuts every utterance at its un-padded output length (the lengths the CTC loss is trained with); "all" counts every frame, which is what the
         reference's ctc_greedy_decode does with this model's logits.  Runs engine.transcribe: with `model._get_engine(device).head_argmax` on (the default), the head's argmax comes out of its GEMM and no logits tensor is produced; otherwise the head
-        GEMM fills an fp32 scratch and one argmax pass reads it (the same ids)."""
+        GEMM fills an fp32 scratch and one argmax pass reads it (the same ids).
+        beams=W (with token_topk, nbest, and bias = a `bias_context`): the CTC prefix beam search instead, -> engine.transcribe's dict (tokens, n_tokens, nbest_tokens,
+        nbest_n, scores[, credit, nbest_credit], inner_len, outer_len); token_topk, nbest and bias without beams are refused (ValueError)."""
         if span not in ("valid", "all"):
             raise ValueError(f"transcribe: span must be 'valid' or 'all', got {span!r}")
+        if beams is None and (token_topk is not None or nbest != 1 or bias is not None):
+            raise ValueError("transcribe: token_topk, nbest and bias belong to beams=")
         if self.training:
             raise RuntimeError("transcribe() is an inference call: put the model in eval mode first (model.eval())")
         if not input_values.is_cuda:
@@ -292,6 +311,8 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
             raise ValueError("transcribe: config.pad_token_id is not set")
         eng = self._get_engine(input_values.device)
         feat_len = attention_mask.sum(-1).to(torch.int32) if attention_mask is not None else None
+        if beams is not None:
+            return eng.transcribe(input_values, feat_len, span=span, pad_id=int(pad), beams=beams, token_topk=token_topk, nbest=nbest, bias=bias)
         out = eng.transcribe(input_values, feat_len, span=span, pad_id=int(pad))
         return out["tokens"], out["n_tokens"]
 
@@ -316,22 +337,22 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
         out = eng.align(input_values, feat_len, labels.to(input_values.device), span=span)
         return CTCAlignment(path=out["path"], score=out["score"], start=out["start"], end=out["end"], token_lp=out["token_lp"], n_tokens=out["tgt_len"])
 
-    def stream(self, batch: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, token_topk=None, nbest=1):
+    def stream(self, batch: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, token_topk=None, nbest=1, bias=None):
         """Streaming inference of a causal model (config.is_causal; eval mode only): -> streaming.EncoderStream over this model's weights — `feed` whole chunks of
         4 * chunk_frames feature frames for `batch` streams in lock-step, `finish` the rest; the concatenated logits are forward()'s of each utterance alone, the ids its
         greedy transcription.  A frame becomes final num_hidden_layers * (merge_conv_kernel - 1) / 2 frames late (DESIGN.md §4 'Streaming').  beams / token_topk /
-        nbest: the prefix beam search on the stream, as EBranchformerEngine.stream takes them."""
+        nbest / bias: the prefix beam search on the stream and its contextual biasing (a `bias_context`), as EBranchformerEngine.stream takes them."""
         if self.training:
             raise RuntimeError("stream() is an inference call: put the model in eval mode first (model.eval())")
         dev = device if device is not None else next(self.parameters()).device
         if torch.device(dev).type != "cuda":
             raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
-        return self._get_engine(dev).stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
+        return self._get_engine(dev).stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, bias=bias)
 
     def stream_pool(self, slots: int, chunk_frames: int, max_frames: int, device=None, *, beams=None):
         """Streaming inference for sessions that start, idle and end on their own (eval mode only): -> streaming.StreamPool over this model's weights, as
-        EBranchformerEngine.stream_pool describes it (DESIGN.md §4 'Session pool'); `.with_beams(W, token_topk=None, nbest=1)` on it adds the CTC prefix beam search per
-        slot ('Beam search on the pool')."""
+        EBranchformerEngine.stream_pool describes it (DESIGN.md §4 'Session pool'); `.with_beams(W, token_topk=None, nbest=1, bias=None)` on it adds the CTC prefix beam search per
+        slot ('Beam search on the pool'), with bias = a `bias_context` its contextual biasing, one context for the pool."""
         if self.training:
             raise RuntimeError("stream_pool() is an inference call: put the model in eval mode first (model.eval())")
         dev = device if device is not None else next(self.parameters()).device
@@ -349,15 +370,16 @@ class Wav2Vec2EBranchformerForCTC(PreTrainedModel):
             raise RuntimeError("Wav2Vec2EBranchformerForCTC (HIP): the model must be on the GPU; there is no CPU fallback")
         return self._get_engine(dev), settings
 
-    def audio_stream(self, feature_extractor, batch: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, token_topk=None, nbest=1, max_push_samples=None):
+    def audio_stream(self, feature_extractor, batch: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, token_topk=None, nbest=1, max_push_samples=None,
+                     bias=None):
         """`stream` fed audio (eval mode only): -> streaming.AudioStream.  feature_size, norm_type and the global statistics are read from the project's
         `CustomFeatureExtractor`; an extractor with utterance CMVN is refused (NotImplementedError: it needs the whole utterance), one whose feature_size is not
-        config.num_fbanks too (ValueError).  The streamed features are those of `feature_extractor.extract_on_device(wave, default_transform=False)`."""
+        config.num_fbanks too (ValueError).  The streamed features are those of `feature_extractor.extract_on_device(wave, default_transform=False)`.  bias as `stream`."""
         eng, settings = self._audio_engine(feature_extractor, device, "audio_stream()")
-        return eng.audio_stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, **settings)
+        return eng.audio_stream(batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, max_push_samples=max_push_samples, bias=bias, **settings)
 
     def audio_pool(self, feature_extractor, slots: int, chunk_frames: int, max_frames: int, device=None, *, beams=None, max_push_samples=None):
-        """`stream_pool` fed audio (eval mode only): -> streaming.AudioPool; the extractor is read as `audio_stream` reads it.  `.with_beams(W, ...)` as on `stream_pool`."""
+        """`stream_pool` fed audio (eval mode only): -> streaming.AudioPool; the extractor is read as `audio_stream` reads it.  `.with_beams(W, ..., bias=)` as on `stream_pool`."""
         eng, settings = self._audio_engine(feature_extractor, device, "audio_pool()")
         return eng.audio_pool(slots, chunk_frames, max_frames, beams=beams, max_push_samples=max_push_samples, **settings)
 

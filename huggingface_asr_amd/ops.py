@@ -624,12 +624,35 @@ def ctc_beam_cut(logits, blank, token_topk, lengths=None):
     return dict(lse=lse, lp_blank=lpb, lp=lp, ids=ids)
 
 
-def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=None, nbest=1, return_frames=False, dtype=torch.int64):
+def _ctc_bias_type(what, bias):
+    """bias=: None or a ctc_bias.CtcBias (TypeError otherwise)"""
+    from .ctc_bias import CtcBias
+    if bias is not None and not isinstance(bias, CtcBias):
+        raise TypeError(f"{what}: bias is a ctc_bias.CtcBias or None, got {type(bias).__name__}")
+    return bias
+
+
+def _ctc_bias_fits(what, bias, V1, blank):
+    """a context built for another vocabulary or blank is refused on the host, before anything touches the device"""
+    if bias is not None and (bias.vocab != V1 or bias.blank != int(blank)):
+        raise ValueError(f"{what}: the bias context was built for vocab {bias.vocab}, blank {bias.blank}; the logits have {V1} classes, blank {blank}")
+
+
+def _ctc_bias_args(bias, dev):
+    """the context arguments of a biased entry: bias_col, bias_tab, S, A1, weight"""
+    col, tab = bias.to(dev)
+    return col.data_ptr(), tab.data_ptr(), bias.S, bias.A1, bias.weight
+
+
+def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=None, nbest=1, return_frames=False, dtype=torch.int64, bias=None):
     """CTC prefix beam search (csrc/ctc_beam.hip states the semantics: the sum over alignments, not the flashlight decoder's max) of logits (B, T, V+1) f32|bf16
     (last dim contiguous, any row / batch strides) with `beams` <= 64 hypotheses per utterance over the `token_topk` <= 64 best non-blank classes of every frame
     (None: min(beams, V), as the reference passes beam_size_token = beam_size).  -> dict(tokens (B, nbest, T) `dtype` = each hypothesis' ids then pad_id, best first,
     n_tokens (B, nbest) int32, scores (B, nbest) fp32 = log of the summed alignment probability[, frames (B, nbest, T) int32 = the frame at which each token's prefix
-    entered the beam, then -1]); hypotheses that do not exist: 0 tokens, score -inf.  lengths (B): frames that count per utterance (None: all).  Two launches."""
+    entered the beam, then -1]); hypotheses that do not exist: 0 tokens, score -inf.  lengths (B): frames that count per utterance (None: all).  Two launches.
+    bias (a ctc_bias.CtcBias built for these V + 1 classes and this blank): contextual biasing, csrc/ctc_beam_bias.hip — hypotheses are selected and ranked by
+    score + weight * credit, scores stay the CTC log-probabilities, and the dict gains credit (B, nbest) int32 (0 for hypotheses that do not exist)."""
+    _ctc_bias_type("ctc_beam_decode", bias)
     if not isinstance(beams, int) or isinstance(beams, bool) or not isinstance(nbest, int) or isinstance(nbest, bool):
         raise TypeError("ctc_beam_decode: beams and nbest are ints")
     if token_topk is not None and (not isinstance(token_topk, int) or isinstance(token_topk, bool)):
@@ -644,6 +667,7 @@ def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=No
         raise TypeError("ctc_beam_decode: token dtype int32 or int64")
     if not isinstance(logits, torch.Tensor) or logits.dim() != 3:
         raise TypeError("ctc_beam_decode: (B, T, V+1) fp32 / bf16 logits")
+    _ctc_bias_fits("ctc_beam_decode", bias, logits.shape[2], blank)
     logits = _ctc_beam_logits(logits, blank, "ctc_beam_decode")
     B, T, V1 = logits.shape
     K = min(beams, V1 - 1) if token_topk is None else token_topk
@@ -659,11 +683,15 @@ def ctc_beam_decode(logits, blank, pad_id, lengths=None, *, beams, token_topk=No
     n = torch.empty((B, nbest), device=dev, dtype=torch.int32)
     scores = torch.empty((B, nbest), device=dev, dtype=torch.float32)
     frames = torch.empty((B, nbest, T), device=dev, dtype=torch.int32) if return_frames else None
-    rc = L.mi_ctc_beam_walk(logits.data_ptr(), logits.stride(1), logits.stride(0), 0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(lengths), int(blank), int(pad_id),
-                            beams, K, nbest, cut["lse"].data_ptr(), cut["lp_blank"].data_ptr(), cut["lp"].data_ptr(), cut["ids"].data_ptr(), ws.data_ptr(), nbytes,
-                            tokens.data_ptr(), int(dtype == torch.int64), n.data_ptr(), scores.data_ptr(), _p(frames), _stream())
-    _lib.check(rc, "mi_ctc_beam_walk")
+    args = (logits.data_ptr(), logits.stride(1), logits.stride(0), 0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(lengths), int(blank), int(pad_id),
+            beams, K, nbest, cut["lse"].data_ptr(), cut["lp_blank"].data_ptr(), cut["lp"].data_ptr(), cut["ids"].data_ptr(), ws.data_ptr(), nbytes,
+            tokens.data_ptr(), int(dtype == torch.int64), n.data_ptr(), scores.data_ptr(), _p(frames))
     out = dict(tokens=tokens, n_tokens=n, scores=scores)
+    if bias is None:
+        _lib.check(L.mi_ctc_beam_walk(*args, _stream()), "mi_ctc_beam_walk")
+    else:
+        out["credit"] = torch.empty((B, nbest), device=dev, dtype=torch.int32)
+        _lib.check(L.mi_ctc_beam_walk_bias(*args, *_ctc_bias_args(bias, dev), out["credit"].data_ptr(), _stream()), "mi_ctc_beam_walk_bias")
     if return_frames:
         out["frames"] = frames
     return out
@@ -703,13 +731,19 @@ class CtcBeamStream:
     object's own buffers: the next call updates them in place.  With partial=True, and always with final=True, also tokens (B, nbest, max_frames) `dtype`, n_tokens,
     scores[, frames] as ctc_beam_decode returns them; after final=True committed[:n_committed] is hypothesis 0.  Without them a call does no backtrace.
     mi_ctc_beam_cut on the call's rows, then mi_ctc_beam_stream_walk: two launches, no host synchronisation.  The object counts T_call per call as the frames walked
-    (an upper bound when n_valid is given: the counts stay on the device) and refuses, before any launch, a call that could pass max_frames."""
+    (an upper bound when n_valid is given: the counts stay on the device) and refuses, before any launch, a call that could pass max_frames.
+    bias (a ctc_bias.CtcBias for the logits' V + 1 classes and this blank): contextual biasing as ctc_beam_decode(bias=) — csrc/ctc_beam_bias_stream.hip; the state
+    grows by 512 B per stream, the walk is mi_ctc_beam_bias_stream_walk, and credit (B, nbest) int32 comes wherever the n-best do."""
 
-    def __init__(self, batch, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False):
+    def __init__(self, batch, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False, bias=None):
         _beam_stream_args("CtcBeamStream", "batch", "stream", batch, max_frames, beams, token_topk, nbest, blank, dtype)
+        self.bias = _ctc_bias_type("CtcBeamStream", bias)
+        if bias is not None and bias.blank != blank:
+            raise ValueError(f"CtcBeamStream: the bias context was built for blank {bias.blank}, not {blank}")
         self.B, self.max_frames, self.beams, self.token_topk, self.nbest = batch, max_frames, beams, token_topk, nbest
         self.blank, self.pad_id, self.dtype, self.return_frames = blank, int(pad_id), dtype, bool(return_frames)
-        self.state_bytes = int(_lib.lib().mi_ctc_beam_stream_state_bytes(batch, max_frames, beams))
+        self._fn = "mi_ctc_beam_stream" if bias is None else "mi_ctc_beam_bias_stream"      # the entries' common prefix: _state_bytes, _reset, _walk
+        self.state_bytes = int(getattr(_lib.lib(), self._fn + "_state_bytes")(batch, max_frames, beams))
         if self.state_bytes == 0:
             raise ValueError(f"CtcBeamStream: {max_frames} frames x {beams} beams is beyond the node table (max_frames * beams < 2^22 - 2)")
         self.walked = 0                            # host upper bound of the frames any stream has walked
@@ -727,8 +761,8 @@ class CtcBeamStream:
         self._reset_device()
 
     def _reset_device(self):
-        rc = _lib.lib().mi_ctc_beam_stream_reset(self._state.data_ptr(), self.state_bytes, self.B, self.max_frames, self.beams, _stream())
-        _lib.check(rc, "mi_ctc_beam_stream_reset")
+        rc = getattr(_lib.lib(), self._fn + "_reset")(self._state.data_ptr(), self.state_bytes, self.B, self.max_frames, self.beams, _stream())
+        _lib.check(rc, self._fn + "_reset")
         self.committed.fill_(self.pad_id)
         self.committed_frames.fill_(-1)
         self.n_committed.zero_()
@@ -753,10 +787,14 @@ class CtcBeamStream:
             n_valid = torch.tensor([int(v) for v in n_valid], dtype=torch.int32)
         if n_valid is not None and tuple(n_valid.shape) != (B,):
             raise ValueError(f"CtcBeamStream.feed: n_valid: expected shape ({B},), got {tuple(n_valid.shape)}")
+        _ctc_bias_fits("CtcBeamStream.feed", self.bias, V1, self.blank)
         if self.walked + T > self.max_frames:
             raise RuntimeError(f"CtcBeamStream.feed: {self.walked} + {T} frames exceed max_frames={self.max_frames}")
         _req(logits)
         dev = logits.device
+        extra = ()
+        if self.bias is not None:
+            extra = _ctc_bias_args(self.bias, dev)
         if T and logits.stride(2) != 1:
             logits = logits.contiguous()
         K = min(self.beams, V1 - 1) if self.token_topk is None else self.token_topk
@@ -770,12 +808,15 @@ class CtcBeamStream:
         n = torch.empty((B, nb), device=dev, dtype=torch.int32) if want else None
         scores = torch.empty((B, nb), device=dev, dtype=torch.float32) if want else None
         frames = torch.empty((B, nb, M), device=dev, dtype=torch.int32) if want and self.return_frames else None
-        rc = _lib.lib().mi_ctc_beam_stream_walk(logits.data_ptr() if T else None, logits.stride(1) if T else 0, logits.stride(0) if T else 0,
-                                                0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(n_valid), self.blank, self.pad_id, self.beams, K, nb,
-                                                _p(cut["lse"]), _p(cut["lp_blank"]), _p(cut["lp"]), _p(cut["ids"]), self._state.data_ptr(), self.state_bytes, M, int(bool(final)),
-                                                self.committed.data_ptr(), self.committed_frames.data_ptr(), self.n_committed.data_ptr(), self.n_new.data_ptr(),
-                                                _p(tokens), int(self.dtype == torch.int64), _p(n), _p(scores), _p(frames), _stream())
-        _lib.check(rc, "mi_ctc_beam_stream_walk")
+        credit = torch.empty((B, nb), device=dev, dtype=torch.int32) if want and self.bias is not None else None
+        if self.bias is not None:
+            extra = (*extra, _p(credit))
+        rc = getattr(_lib.lib(), self._fn + "_walk")(logits.data_ptr() if T else None, logits.stride(1) if T else 0, logits.stride(0) if T else 0,
+                                                     0 if logits.dtype == torch.float32 else 1, B, T, V1, _p(n_valid), self.blank, self.pad_id, self.beams, K, nb,
+                                                     _p(cut["lse"]), _p(cut["lp_blank"]), _p(cut["lp"]), _p(cut["ids"]), self._state.data_ptr(), self.state_bytes, M,
+                                                     int(bool(final)), self.committed.data_ptr(), self.committed_frames.data_ptr(), self.n_committed.data_ptr(),
+                                                     self.n_new.data_ptr(), _p(tokens), int(self.dtype == torch.int64), _p(n), _p(scores), _p(frames), *extra, _stream())
+        _lib.check(rc, self._fn + "_walk")
         self.V1 = V1
         self.walked += T
         self.finished = bool(final)
@@ -784,6 +825,8 @@ class CtcBeamStream:
             out.update(tokens=tokens, n_tokens=n, scores=scores)
             if self.return_frames:
                 out["frames"] = frames
+            if credit is not None:
+                out["credit"] = credit
         return out
 
 
@@ -799,15 +842,20 @@ class CtcBeamPool:
     the next call that names the slot and cleared by its next `open`.  For the records with final or partial also tokens (R, nbest, max_frames) `dtype`, n_tokens,
     scores (R, nbest)[, frames], compact in record order, and rows {slot: row}.  mi_ctc_beam_cut over the compact rows (skipped without rows), then
     mi_ctc_beam_stream_walk_slots: at most two launches, no host synchronisation.  `walked[slot]` counts a session's frames exactly (every row of a record is valid);
-    a record that would pass max_frames, or names a slot that is not open or already final, is refused before any launch."""
+    a record that would pass max_frames, or names a slot that is not open or already final, is refused before any launch.
+    bias (a ctc_bias.CtcBias): contextual biasing, one context per pool shared by all slots (csrc/ctc_beam_bias_pool.hip); credit (R, nbest) comes beside scores."""
 
     REC_WORDS = 5
 
-    def __init__(self, slots, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False):
+    def __init__(self, slots, max_frames, *, beams, token_topk=None, nbest=1, blank, pad_id, dtype=torch.int64, return_frames=False, bias=None):
         _beam_stream_args("CtcBeamPool", "slots", "slot", slots, max_frames, beams, token_topk, nbest, blank, dtype)
+        self.bias = _ctc_bias_type("CtcBeamPool", bias)                    # one context per pool, shared by all slots
+        if bias is not None and bias.blank != blank:
+            raise ValueError(f"CtcBeamPool: the bias context was built for blank {bias.blank}, not {blank}")
         self.S, self.max_frames, self.beams, self.token_topk, self.nbest = slots, max_frames, beams, token_topk, nbest
         self.blank, self.pad_id, self.dtype, self.return_frames = blank, int(pad_id), dtype, bool(return_frames)
-        self.state_bytes = int(_lib.lib().mi_ctc_beam_stream_state_bytes(slots, max_frames, beams))
+        self._fn = "mi_ctc_beam_stream" if bias is None else "mi_ctc_beam_bias_stream"      # the entries' common prefix: _state_bytes, _reset, _reset_slot, _walk_slots
+        self.state_bytes = int(getattr(_lib.lib(), self._fn + "_state_bytes")(slots, max_frames, beams))
         if self.state_bytes == 0:
             raise ValueError(f"CtcBeamPool: {max_frames} frames x {beams} beams is beyond the node table (max_frames * beams < 2^22 - 2)")
         self.walked = [0] * slots                  # frames the slot's session has walked
@@ -823,8 +871,8 @@ class CtcBeamPool:
         self.committed_frames = torch.full((S, M), -1, device=dev, dtype=torch.int32)
         self.n_committed = torch.zeros((S,), device=dev, dtype=torch.int32)
         self.n_new = torch.zeros((S,), device=dev, dtype=torch.int32)
-        rc = _lib.lib().mi_ctc_beam_stream_reset(self._state.data_ptr(), self.state_bytes, S, M, self.beams, _stream())
-        _lib.check(rc, "mi_ctc_beam_stream_reset")
+        rc = getattr(_lib.lib(), self._fn + "_reset")(self._state.data_ptr(), self.state_bytes, S, M, self.beams, _stream())
+        _lib.check(rc, self._fn + "_reset")
 
     def open(self, slot):
         """the slot back to a stream start: its beam state (mi_ctc_beam_stream_reset_slot: one launch and a memset of the slot's node table), its committed row to pad,
@@ -832,8 +880,8 @@ class CtcBeamPool:
         if not isinstance(slot, int) or isinstance(slot, bool) or not 0 <= slot < self.S:
             raise ValueError(f"CtcBeamPool.open: slot {slot!r} outside [0, {self.S})")
         if self._state is not None:
-            rc = _lib.lib().mi_ctc_beam_stream_reset_slot(self._state.data_ptr(), self.state_bytes, self.S, self.max_frames, self.beams, slot, _stream())
-            _lib.check(rc, "mi_ctc_beam_stream_reset_slot")
+            rc = getattr(_lib.lib(), self._fn + "_reset_slot")(self._state.data_ptr(), self.state_bytes, self.S, self.max_frames, self.beams, slot, _stream())
+            _lib.check(rc, self._fn + "_reset_slot")
             self.committed[slot].fill_(self.pad_id)
             self.committed_frames[slot].fill_(-1)
             self.n_committed[slot].zero_()
@@ -874,9 +922,13 @@ class CtcBeamPool:
         rows, V1 = logits.shape
         if V1 < 2 or self.blank >= V1 or (self.V1 is not None and V1 != self.V1):
             raise ValueError(f"CtcBeamPool.step: logits of (rows, {self.V1 or 'V+1'}) with blank {self.blank} inside, got {tuple(logits.shape)}")
+        _ctc_bias_fits("CtcBeamPool.step", self.bias, V1, self.blank)
         recs, outs = self.records(records, rows)
         _req(logits)
         dev = logits.device
+        extra = ()
+        if self.bias is not None:
+            extra = _ctc_bias_args(self.bias, dev)
         if rows and logits.stride(1) != 1:
             logits = logits.contiguous()
         A, R, nb, M = len(recs), len(outs), self.nbest, self.max_frames
@@ -899,12 +951,15 @@ class CtcBeamPool:
         n = torch.empty((R, nb), device=dev, dtype=torch.int32) if R else None
         scores = torch.empty((R, nb), device=dev, dtype=torch.float32) if R else None
         frames = torch.empty((R, nb, M), device=dev, dtype=torch.int32) if R and self.return_frames else None
-        rc = _lib.lib().mi_ctc_beam_stream_walk_slots(logits.data_ptr() if rows else None, logits.stride(0) if rows else 0, 0 if logits.dtype == torch.float32 else 1, rows, V1,
-                                                      self.blank, self.pad_id, self.beams, K, nb, _p(lse), _p(lpb), _p(lp), _p(ids), self._state.data_ptr(), self.state_bytes,
-                                                      self.S, M, host.data_ptr(), A, records_dev.data_ptr(), self.committed.data_ptr(), self.committed_frames.data_ptr(),
-                                                      self.n_committed.data_ptr(), self.n_new.data_ptr(), _p(tokens), int(self.dtype == torch.int64), _p(n), _p(scores),
-                                                      _p(frames), R, _stream())
-        _lib.check(rc, "mi_ctc_beam_stream_walk_slots")
+        credit = torch.empty((R, nb), device=dev, dtype=torch.int32) if R and self.bias is not None else None
+        if self.bias is not None:
+            extra = (*extra, _p(credit))
+        rc = getattr(_lib.lib(), self._fn + "_walk_slots")(logits.data_ptr() if rows else None, logits.stride(0) if rows else 0, 0 if logits.dtype == torch.float32 else 1, rows,
+                                                           V1, self.blank, self.pad_id, self.beams, K, nb, _p(lse), _p(lpb), _p(lp), _p(ids), self._state.data_ptr(),
+                                                           self.state_bytes, self.S, M, host.data_ptr(), A, records_dev.data_ptr(), self.committed.data_ptr(),
+                                                           self.committed_frames.data_ptr(), self.n_committed.data_ptr(), self.n_new.data_ptr(), _p(tokens),
+                                                           int(self.dtype == torch.int64), _p(n), _p(scores), _p(frames), R, *extra, _stream())
+        _lib.check(rc, self._fn + "_walk_slots")
         self.V1 = V1
         for slot, _, cnt, final, _ in recs:
             self.walked[slot] += cnt
@@ -915,6 +970,8 @@ class CtcBeamPool:
             out.update(tokens=tokens, n_tokens=n, scores=scores)
             if self.return_frames:
                 out["frames"] = frames
+            if credit is not None:
+                out["credit"] = credit
         return out
 
 

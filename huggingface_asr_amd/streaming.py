@@ -150,8 +150,9 @@ class _StreamState:
 class EncoderStream(_StreamState):
     """State of B streams advanced in lock-step through a causal encoder + CTC head (mi_ebf_stream_step).  Created by `EBranchformerEngine.stream`."""
 
-    def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1):
+    def __init__(self, engine, batch: int, chunk_frames: int, max_frames: int, *, beams=None, token_topk=None, nbest=1, bias=None):
         super().__init__(engine, batch, chunk_frames, max_frames, "stream()", "batch")
+        engine._check_bias("stream()", bias, beams)     # bias= (ctc_bias.CtcBias): contextual biasing of the beam search; "beam" then holds credit beside the n-best
         self.B, c = self._n, engine.cfg
         self.n_feat = 0
         self.total = 0                                  # frames emitted so far (per stream, lock-step)
@@ -160,7 +161,7 @@ class EncoderStream(_StreamState):
         if beams is not None:
             from . import ops
             self.beam = ops.CtcBeamStream(self.B, self.max_frames, beams=beams, token_topk=token_topk, nbest=nbest, blank=c["vocab_size"], pad_id=-1, dtype=torch.int32,
-                                          return_frames=True)
+                                          return_frames=True, bias=bias)
         elif token_topk is not None or nbest != 1:
             raise ValueError("stream(): token_topk and nbest belong to beams=")
 
@@ -283,18 +284,20 @@ class StreamPool(_StreamState):
         self.total = [0] * self.S                       # frames it has emitted
         self.beam = None                                # with_beams(): the prefix beam search walks every slot's emitted frames too (ops.CtcBeamPool)
 
-    def with_beams(self, beams, *, token_topk=None, nbest=1):
+    def with_beams(self, beams, *, token_topk=None, nbest=1, bias=None):
         """Switches on the CTC prefix beam search per slot (ops.CtcBeamPool, csrc/ctc_beam_pool.hip) -> the pool itself.  Every session then walks `beams` (1..64)
         hypotheses over the `token_topk` best classes of the frames it emits, as `engine.stream(1, C, max_frames, beams=, token_topk=, nbest=)` would for the same
         pieces — bit for bit —, and `step` adds "beam" to every named slot's dict.  Allowed only while no session is open (RuntimeError); the checks are those of
         `engine.stream(beams=)` (ValueError / TypeError; max_frames * beams < 2^22 - 2).  Nothing is allocated before the first device step.  Per step the beam adds
         two kernels (the token cut over the step's compact logits and one walk block per named slot), one small copy (the step's counts) and no transfer: its records
-        ride behind the descriptor table."""
+        ride behind the descriptor table.  bias (a ctc_bias.CtcBias): contextual biasing, one context for the pool, shared by all slots (csrc/ctc_beam_bias_pool.hip);
+        a slot's "beam" then holds credit (nbest) beside its n-best."""
+        self.engine._check_bias("with_beams", bias, beams)
         if any(self.is_open):
             raise RuntimeError("StreamPool.with_beams: sessions are open; the beam search is switched on before the first open()")
         from . import ops
         self.beam = ops.CtcBeamPool(self.S, self.max_frames, beams=beams, token_topk=token_topk, nbest=nbest, blank=self.engine.cfg["vocab_size"], pad_id=-1,
-                                    dtype=torch.int32, return_frames=True)
+                                    dtype=torch.int32, return_frames=True, bias=bias)
         return self
 
     def _may_rebuild(self):
@@ -445,6 +448,8 @@ class StreamPool(_StreamState):
                 if sid in bout["rows"]:
                     row = bout["rows"][sid]
                     b.update(tokens=bout["tokens"][row], n_tokens=bout["n_tokens"][row], scores=bout["scores"][row], frames=bout["frames"][row])
+                    if "credit" in bout:
+                        b["credit"] = bout["credit"][row]
                 out[sid]["beam"] = b
         return out
 
@@ -549,8 +554,8 @@ class AudioStream:
     offline equivalent of a streamed session is `extract_on_device(..., default_transform=False)`."""
 
     def __init__(self, engine, batch, chunk_frames, max_frames, *, normalize=None, global_means=None, global_stds=None, beams=None, token_topk=None, nbest=1,
-                 max_push_samples=None, tables=None):
-        self.stream = EncoderStream(engine, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest)
+                 max_push_samples=None, tables=None, bias=None):
+        self.stream = EncoderStream(engine, batch, chunk_frames, max_frames, beams=beams, token_topk=token_topk, nbest=nbest, bias=bias)
         self.B, self.C = self.stream.B, self.stream.C
         self.fb = _front_end(engine, self.B, self.C, self.stream.F, normalize, global_means, global_stds, max_push_samples, tables, "audio_stream()")
         self.n = 0                                      # samples every stream has had
@@ -635,9 +640,9 @@ class AudioPool:
 
     seconds = staticmethod(seconds)
 
-    def with_beams(self, beams, *, token_topk=None, nbest=1):
+    def with_beams(self, beams, *, token_topk=None, nbest=1, bias=None):
         """`StreamPool.with_beams` on the wrapped pool -> this pool: every step dict of a slot then holds "beam"; `push(..., partial=)` asks for the n-best so far"""
-        self.pool.with_beams(beams, token_topk=token_topk, nbest=nbest)
+        self.pool.with_beams(beams, token_topk=token_topk, nbest=nbest, bias=bias)
         return self
 
     def open(self) -> int:

@@ -315,6 +315,35 @@ int mi_ctc_beam_stream_walk_slots(const void* logits, long ld_row, int dtype, in
                                   const float* lp_blank, const float* cut_lp, const int* cut_id, void* state, size_t state_bytes, int S, int max_frames,
                                   const int* records_host, int A, const int* records_dev, int* committed, int* committed_frames, int* n_committed, int* n_new,
                                   void* tokens, int tokens_dtype, int* n_tokens, float* scores, int* frames, int R, mi_stream_t stream);
+/* ---- Contextual biasing of the CTC prefix beam search (csrc/ctc_beam_bias.hip, whose header states the semantics): the three searches above with a phrase list.  A
+ * hypothesis is selected and ranked by score + weight (float)n, n the credit of its label prefix in the phrase automaton; `scores` stay the CTC log-probabilities.
+ * The context, the same arguments in every entry: bias_col (V1) int32 a token's alphabet column (0: in no phrase), bias_tab (S, A1) int32 the word (dn << 16) | next
+ * per (state, column), 1 <= S <= 4096, 1 <= A1 <= 1024, S A1 <= 2^20, weight finite (huggingface_asr_amd/ctc_bias.py compiles them).  The kernels clamp every index
+ * they read from the tables into the tables.  credit: int32, a row of nbest beside every row of scores = n per hypothesis, 0 for rows that do not exist.
+ * mi_ctc_beam_walk_bias: mi_ctc_beam_walk (the cut is mi_ctc_beam_cut as it is; the same workspace) with the context and credit (B, nbest).
+ * mi_ctc_beam_bias_stream_state_bytes: mi_ctc_beam_stream_state_bytes + 512 B: behind the unbiased state, per stream the carried (state, credit) of its 64 hypotheses.
+ * mi_ctc_beam_bias_stream_reset / _walk: mi_ctc_beam_stream_reset / _walk on that state; credit (B, nbest) is written wherever the n best are (required with tokens).
+ * mi_ctc_beam_bias_stream_reset_slot / _walk_slots: mi_ctc_beam_stream_reset_slot / _walk_slots on that state (S slots; the automaton's states are S_bias); credit
+ * (R, nbest), required with R > 0.  One context per pool; a stream or session keeps its context from start to end.
+ * MI_ERR_ARG before any launch: whatever the unbiased counterpart refuses, null tables, S, A1 or S A1 outside the limits, a weight that is not finite, a missing credit.
+ * MI_ERR_UNSUPPORTED as the counterpart.  With weight = 0 every output equals the counterpart's, bit for bit. */
+int mi_ctc_beam_walk_bias(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T, int V1, const int* lengths, int blank, long pad_id, int W, int K,
+                          int nbest, const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* workspace, size_t workspace_bytes, void* tokens,
+                          int tokens_dtype, int* n_tokens, float* scores, int* frames, const int* bias_col, const int* bias_tab, int S, int A1, float weight, int* credit,
+                          mi_stream_t stream);
+size_t mi_ctc_beam_bias_stream_state_bytes(int B, int max_frames, int W);
+int mi_ctc_beam_bias_stream_reset(void* state, size_t state_bytes, int B, int max_frames, int W, mi_stream_t stream);
+int mi_ctc_beam_bias_stream_walk(const void* logits, long ld_row, long ld_batch, int dtype, int B, int T_call, int V1, const int* n_valid, int blank, long pad_id, int W,
+                                 int K, int nbest, const float* lse, const float* lp_blank, const float* cut_lp, const int* cut_id, void* state, size_t state_bytes,
+                                 int max_frames, int final, int* committed, int* committed_frames, int* n_committed, int* n_new, void* tokens, int tokens_dtype,
+                                 int* n_tokens, float* scores, int* frames, const int* bias_col, const int* bias_tab, int S, int A1, float weight, int* credit,
+                                 mi_stream_t stream);
+int mi_ctc_beam_bias_stream_reset_slot(void* state, size_t state_bytes, int S, int max_frames, int W, int slot, mi_stream_t stream);
+int mi_ctc_beam_bias_stream_walk_slots(const void* logits, long ld_row, int dtype, int rows, int V1, int blank, long pad_id, int W, int K, int nbest, const float* lse,
+                                       const float* lp_blank, const float* cut_lp, const int* cut_id, void* state, size_t state_bytes, int S, int max_frames,
+                                       const int* records_host, int A, const int* records_dev, int* committed, int* committed_frames, int* n_committed, int* n_new,
+                                       void* tokens, int tokens_dtype, int* n_tokens, float* scores, int* frames, int R, const int* bias_col, const int* bias_tab,
+                                       int S_bias, int A1, float weight, int* credit, mi_stream_t stream);
 /* ---- CTC forced alignment (csrc/ctc_align.hip, whose header states the exact semantics): the best (Viterbi) path of a given transcript, one launch, one block per
  * utterance.  Arguments as mi_ctc_loss_fwd: logits (B, T, V1) fp32 (dtype 0) / bf16 (1) with element strides (ld_b, ld_t), lse (B*T) the rows' log-sum-exp, labels
  * (B, U) int64 (negative entries are padding wherever they stand), in_len (B) int32 clamped to [0, T].  Out: path (B, T) int32 = the class of every frame t < n_b on
