@@ -265,11 +265,12 @@ __global__ __launch_bounds__(512, 2) void gemm8p_kernel(GemmArgs p) {
     float ln_r = 0.f, ln_t = 0.f;        // LNF: (rstd, rstd * mean) of row tid >> 1, kept in two registers across the K loop; shared through LDS in the epilogue
     if constexpr (LNF) {
         const int n4 = p.ln_npart == 1 ? 1 : p.ln_npart >> 2;
-        const float w1 = n4 > 1 ? 1.f : 0.f, w2 = n4 > 2 ? 1.f : 0.f, w3 = n4 > 3 ? 1.f : 0.f;          // records beyond n4 were clamped re-loads: weight 0
-        const float wz = p.ln_npart == 1 ? 0.f : 1.f;                                                     // one pair: only (.x, .y) of record 0 ...
-        const float wl = (p.ln_npart == 1 && (tid & 1)) ? 0.f : 1.f;                                      // ... and only on the row's first lane
-        float sm = wl * (((lnv[0].x + wz * lnv[0].z) + w1 * (lnv[1].x + lnv[1].z)) + (w2 * (lnv[2].x + lnv[2].z) + w3 * (lnv[3].x + lnv[3].z)));
-        float sq = wl * (((lnv[0].y + wz * lnv[0].w) + w1 * (lnv[1].y + lnv[1].w)) + (w2 * (lnv[2].y + lnv[2].w) + w3 * (lnv[3].y + lnv[3].w)));
+        // What does not count is dropped with a SELECT, never with a weight of 0 (0 * NaN = NaN, and the floats of a record beyond the row's pairs are the caller's):
+        // records beyond n4 were clamped re-loads; one pair: only (.x, .y) of record 0, and only on the row's first lane.  The conditions are uniform but for the lane bit.
+        const bool one = p.ln_npart == 1, own = !(one && (tid & 1));
+        auto pick = [](bool on, float v) { return on ? v : 0.f; };
+        float sm = pick(own, ((lnv[0].x + pick(!one, lnv[0].z)) + pick(n4 > 1, lnv[1].x + lnv[1].z)) + (pick(n4 > 2, lnv[2].x + lnv[2].z) + pick(n4 > 3, lnv[3].x + lnv[3].z)));
+        float sq = pick(own, ((lnv[0].y + pick(!one, lnv[0].w)) + pick(n4 > 1, lnv[1].y + lnv[1].w)) + (pick(n4 > 2, lnv[2].y + lnv[2].w) + pick(n4 > 3, lnv[3].y + lnv[3].w)));
         sm += dpp_f32<0xB1, 0xF>(0.f, sm);                  // quad_perm [1,0,3,2]: lane ^ 1 holds the row's other half
         sq += dpp_f32<0xB1, 0xF>(0.f, sq);
         const float mean = sm / (float)p.K;

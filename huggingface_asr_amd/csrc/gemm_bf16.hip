@@ -275,6 +275,7 @@ extern "C" int mi_conv2d_cl_geo_bf16(const void* in, const void* weight, const f
 // ---- LayerNorm folded into the GEMMs around it (encoder.hip `ln_fold` path; algebra in gemm_args.hpp).
 // Consumer: C (M,N) bf16 = act(LN(x) W^T + b) computed as act(rstd * (xb Wf^T) - rstd * mu * colsum + cbias), xb = bf16(x) (M,K), Wf = bf16(W diag(gamma)) (N,K),
 // colsum_n = sum_k Wf[n,k], cbias = W beta + b; `stats`: per-row partial (sum, sumsq) pairs of x, row stride 32 floats, `npart` pairs (1 | 4..16 in steps of 4).
+// Only floats 0 .. 2 npart - 1 of a record count; npart = 1 loads floats 2 and 3 with them and drops their values with a select, so they may hold anything (hfasr_hip.h).
 // Runs on the 256x256 phase kernel only: N % 256 == 0, K % 64 == 0, K >= 128; MI_ERR_UNSUPPORTED otherwise (the caller keeps the LayerNorm kernel + plain GEMM).
 extern "C" int mi_gemm_lnfold_bf16(const void* xb, long lda, const void* Wf, long ldw, const float* colsum, const float* cbias, const float* stats, int npart, float eps,
                                    void* C, long ldc, int act, int M, int N, int K, hipStream_t stream) {

@@ -106,7 +106,11 @@ int mi_gemm_act_bwd_bf16(const void* dY, long ldy, const void* Wt, long ldw, con
  *      LN(x) W^T + b = rstd (bf16(x) W'^T) - rstd mu s + (W beta + b),  W' = bf16(W diag(gamma)),  s_n = sum_k W'[n,k].
  * mi_gemm_lnfold_bf16: the consumer GEMM (256x256 phase kernel; MI_ERR_UNSUPPORTED for shapes it does not take); stats = per-row partial (sum, sumsq) pairs of x, row stride
  *   32 floats, npart pairs.  mi_gemm_resid_stats_f32: the producer — C fp32 = resid + alpha (A W^T + b), plus C2 = bf16(C) and the partial statistics of the rows it stores
- *   (one pair per 32 columns; 128x128 phase kernel).  mi_layernorm_fold: y = [LN](mask(x)) as fp32 + bf16 + statistics pair 0 (npart = 1). */
+ *   (one pair per 32 columns; 128x128 phase kernel).  mi_layernorm_fold: y = [LN](mask(x)) as fp32 + bf16 + statistics pair 0 (npart = 1).
+ *   The statistics record: row m owns floats [32 m, 32 m + 32) of `stats` (16-B aligned), pair s = floats 2 s (sum) and 2 s + 1 (sum of squares); npart = 1 or 4, 8, 12, 16.
+ *   mi_gemm_lnfold_bf16 reads floats 0 .. 2 npart - 1 of the records of rows 0 .. M - 1 and no other row's; with npart = 1 its 16-B load also covers floats 2 and 3 of the
+ *   record, whose VALUES it ignores: they, like every float from 2 npart on, may hold anything, NaN and Inf bit patterns included, and need not be initialised.  The producers
+ *   write exactly the pairs they own — mi_layernorm_fold floats 0 and 1, mi_gemm_resid_stats_f32 floats 0 .. 2 (N / 32) - 1 (variant 40: 2 (N / 64) - 1) — of rows 0 .. M - 1. */
 int mi_gemm_lnfold_bf16(const void* xb, long lda, const void* Wf, long ldw, const float* colsum, const float* cbias, const float* stats, int npart, float eps,
                         void* C, long ldc, int act, int M, int N, int K, mi_stream_t stream);
 int mi_gemm_resid_stats_f32(const void* A, long lda, const void* W, long ldw, const float* bias, float* C, long ldc, const float* resid, long ldr, float alpha,
